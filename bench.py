@@ -1,16 +1,22 @@
 #!/usr/bin/env python3
 """Throughput / latency bench of the PPG->wav hot path on MI355X (driver contract: see the task brief).
 
-  python bench.py [--gpus N] [--steps K] [--warmup W] [--workload e2e|infer|corpus|train]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--workload e2e|infer|corpus|train] [--full] [--dump-outputs DIR]
 
 The metric is BASELINE.json's: 22.05 kHz (hop 256) audio samples per second END TO END (PPG -> wav) and the real-time
 factor at batch = 1.  The DEFAULT run therefore times the metric's own configuration: one 200-frame utterance per step,
 host PPG [200 x 5816] in -> Tacotron2 -> WaveGlow -> Denoiser -> device wav out (SURVEY.md 8d config 1 at hop 256);
-`value` = samples / s of that step, `realtime_factor` = value / 22050, `roofline` = the executed-FLOP fraction of the fp32
-MFMA peak reached by the dominant kernel (the fused WaveNet layer) INSIDE that run, from hipEvents around each flow's run of its
-launches in the timed steps.  The other BASELINE configs are sub-keys of the same JSON line, each with its own steps /
+`value` = samples / s of that step, `realtime_factor` = value / 22050, `ms_per_step` = host clock over the K timed steps / K.
+A plain run does only that: set up, warm up, time K steps, print one JSON line.
+
+--full adds everything else to the same JSON line: `roofline` = the executed-FLOP fraction of the fp32 MFMA peak reached by the
+dominant kernel (the fused WaveNet layer) INSIDE that run, from hipEvents around each flow's run of its launches in the timed
+steps; `stage_ms` / `stage_roofline` from one further step; the other BASELINE configs as sub-keys, each with its own steps /
 ms_per_step / roofline: `waveglow_batch8` (configs[1]), `end_to_end_batch16_ragged` (configs[2], one batch at a time and
 software-pipelined), plus `reference_rate_config`, `train_step`, `cpu_baseline`.
+
+--dump-outputs DIR writes what the last timed step computed (the waveform(s) a caller receives, the loss and a sample of the
+updated parameters for --workload train) as DIR/<name>.npy; same arguments, same inputs.
 
 --workload (what one "step" is, and what `value` counts; every workload names its BASELINE.json config):
   e2e     (default) end-to-end PPG -> mel -> wav (Tacotron2 + WaveGlow + Denoiser), host PPG in, device wav out;
@@ -28,11 +34,11 @@ software-pipelined), plus `reference_rate_config`, `train_step`, `cpu_baseline`.
 With --gpus N > 1 it runs one rank per GPU: either launched under torch.distributed.run (RANK / LOCAL_RANK / WORLD_SIZE /
 MASTER_* in the env), or -- when WORLD_SIZE is not set -- it spawns the N ranks itself (the one-process-per-GPU launcher
 pattern of the reference's distributed.py:145-170).  The world size and the number of ranks RCCL actually sees are asserted
-to equal --gpus.  An N > 1 run of the default workload also carries short `train_dp` and `corpus_dp` entries (the two
-configs whose collectives matter), so one 8-GPU invocation measures them too; --no-extra skips them.
+to equal --gpus.  An N > 1 --full run of the default workload also carries short `train_dp` and `corpus_dp` entries (the
+two configs whose collectives matter), so one 8-GPU invocation measures them too; --no-extra skips them.
 
-  cpu_baseline  the CPU oracle (a port of the reference's PyTorch-CPU path) timed on this host's cores on a bounded sample
-                (rank 0, N=1 only): end to end on the SAME config-1 input as `value`, pinned to 16 cores, 3 runs after a
+  cpu_baseline  (--full) the CPU oracle (a port of the reference's PyTorch-CPU path) timed on this host's cores on a bounded
+                sample (rank 0, N=1 only): end to end on the SAME config-1 input as `value`, pinned to 16 cores, 3 runs after a
                 warm-up (median, min and max stated).
 """
 import argparse
@@ -187,7 +193,7 @@ def cpu_model_name():
 def cpu_baseline(log):
     """Bounded CPU sample in subprocesses (configs 1-3 end to end, median of 3 after a warm-up, core count
     and CPU model stated).  A 256-thread oneDNN run of these small convolutions is pathologically slow; the thread count is swept
-    over 16 / 32 / 64 / 128 on config 1 in every run and the best is what is reported."""
+    over 16 / 32 / 64 / 128 (at most the CPUs this process may use) on config 1 in every run and the best is what is reported."""
     import subprocess
 
     def run(mode, threads, limit):
@@ -200,7 +206,10 @@ def cpu_baseline(log):
         return d
     # the thread count is SWEPT on the headline's own case (config 1, ~1 s per run) and the best is reported with its count:
     # 16 threads were the best of {16, 32} in round 2; whether more of the host's cores help is measured here, every run
-    ncpu = os.cpu_count() or 1
+    # (never more threads than this process may use: its CPU affinity, and OMP_NUM_THREADS where the host sets it)
+    ncpu = len(os.sched_getaffinity(0)) if hasattr(os, "sched_getaffinity") else (os.cpu_count() or 1)
+    if os.environ.get("OMP_NUM_THREADS", "").isdigit() and int(os.environ["OMP_NUM_THREADS"]) > 0:
+        ncpu = min(ncpu, int(os.environ["OMP_NUM_THREADS"]))
     sweep, res = {}, {}
     for t in sorted(set(min(v, ncpu) for v in (16, 32, 64, 128))):
         try:
@@ -661,26 +670,33 @@ class InferWorkload(object):
         self.mel = synth.synthetic_mel(self.B, self.T, seed=1234 + rank).to(dev)
         self.samples = world * self.B * self.T * HOP
         self.audio = None
+        self.full = bool(getattr(args, "full", True))
 
     def step(self, i):
         self.audio = self.model.infer(self.mel, sigma=0.6, seed=1000 + i)
 
+    def outputs(self):
+        return {"audio": self.audio.float().cpu().numpy()}
+
     def start_timed(self):
-        L = self.flib.load()
-        self.flib.check(L.facppg_wg_set_profiling(self.model._handle(self.dev), 1))
+        if self.full:      # hipEvents around the layer launches of the timed steps, for the roofline
+            L = self.flib.load()
+            self.flib.check(L.facppg_wg_set_profiling(self.model._handle(self.dev), 1))
 
     def finish(self, out, elapsed, steps):
-        flib, L = self.flib, self.flib.load()
-        ms, n = flib.ctypes.c_float(), flib.ctypes.c_int()
-        flib.check(L.facppg_wg_last_layer_ms(self.model._handle(self.dev), flib.ctypes.byref(ms), flib.ctypes.byref(n)))
-        layer_ms, layer_n = ms.value, n.value
-        flib.check(L.facppg_wg_set_profiling(self.model._handle(self.dev), 0))
         assert os.environ.get("FACPPG_BENCH_NO_CHECK") or torch.isfinite(self.audio).all()
         standard = (self.B, self.T) == (BATCH, FRAMES)
         out["config"] = {"workload": "%sWaveGlow.infer batch=%d, mel 80x%d, hop=%d (%d Hz), fp32, sigma=0.6, device "
                                      "Philox noise; the vocoder stage (98.8 %% of the FLOPs) of the PPG->wav path; seeded synthetic weights "
                                      "(no checkpoints ship with the reference)" % ("BASELINE configs[1]: " if standard else "", self.B, self.T, HOP, SR),
                          "per_gpu_batch": self.B, "global_batch": self.B * self.world, "parallelism": "dp%d" % self.world}
+        if not self.full:
+            return
+        flib, L = self.flib, self.flib.load()
+        ms, n = flib.ctypes.c_float(), flib.ctypes.c_int()
+        flib.check(L.facppg_wg_last_layer_ms(self.model._handle(self.dev), flib.ctypes.byref(ms), flib.ctypes.byref(n)))
+        layer_ms, layer_n = ms.value, n.value
+        flib.check(L.facppg_wg_set_profiling(self.model._handle(self.dev), 0))
         out["roofline"] = wn_layer_roofline(self.model, layer_ms, layer_n, self.B * self.T * HOP // 8,
                                             "k_wn_layer" if standard else "k_wn_layer_b%d_t%d" % (self.B, self.T))
 
@@ -694,6 +710,7 @@ class E2EWorkload(object):
         lens = [200] if args.e2e_batch == 1 else config3_lengths(args.e2e_batch, 7 + rank)
         self.e = EndToEnd(dev, lens, seed0=1000 * rank, waveglow=waveglow)
         self.world, self.dev, self.steps = world, dev, args.steps
+        self.full = bool(getattr(args, "full", True))
         # back-to-back batches, software-pipelined (facppg.pipeline.synthesize_stream): the acoustic model of step i+1 runs
         # under the vocoder of step i.  The batch-1 case is the metric's latency figure: one utterance at a time, no overlap.
         self.overlap = bool(args.e2e_overlap) and len(lens) > 1
@@ -708,10 +725,16 @@ class E2EWorkload(object):
     def step(self, i):
         self.out = next(self.gen) if self.overlap else self.e.step(i)
 
+    def outputs(self):
+        import numpy as np
+        wavs, tout = self.out
+        return {"audio": torch.cat([w.reshape(-1) for w in wavs]).float().cpu().numpy(),
+                "mel_frames": np.asarray([int(t) for t in tout], dtype=np.float64)}
+
     def start_timed(self):
         # hipEvent pairs around every flow's fused-WN-layer launches of the timed steps (created here, recorded on the launch stream)
         from facppg import lib as flib
-        if len(self.e.lens) == 1:
+        if self.full and len(self.e.lens) == 1:
             flib.check(flib.load().facppg_wg_set_profiling(self.e.waveglow._handle(self.dev), max(2, self.steps)))
 
     def finish(self, out, elapsed, steps):
@@ -720,6 +743,12 @@ class E2EWorkload(object):
                                  "step i's WaveGlow + denoiser; every step's acoustic model and vocoder are inside the timed region "
                                  "(stage_ms below: one further, un-overlapped step)") if self.overlap else "none: one batch at a time"
         b1 = len(self.e.lens) == 1
+        out["config"] = {"workload": "BASELINE configs[2]: " + self.e.describe() if not b1 else
+                         "the metric's own case, real-time factor at batch = 1 (SURVEY.md 8d config 1 at the metric's 22.05 kHz / hop 256): "
+                         + self.e.describe() + "; one utterance per step, nothing overlapped across steps",
+                         "per_gpu_batch": len(self.e.lens), "global_batch": len(self.e.lens) * self.world, "parallelism": "dp%d" % self.world}
+        if not self.full:
+            return
         if b1:
             L, h = flib.load(), self.e.waveglow._handle(self.dev)
             ms, n = flib.ctypes.c_float(), flib.ctypes.c_int()
@@ -772,10 +801,6 @@ class E2EWorkload(object):
                     "hbm_GBps": byts / (ms * 1e-3) / 1e9, "hbm_frac": byts / (ms * 1e-3) / 1e9 / 8000.0,
                     "measured": "hipEvents around every seed pass of one further end-to-end step (not the one of stage_ms), on the seed stream, while the decoder "
                                 "holds %d of the %d CUs (passes that start after the decoder's end have the chip)" % (dec_wgs, n_cu)}
-        out["config"] = {"workload": "BASELINE configs[2]: " + self.e.describe() if not b1 else
-                         "the metric's own case, real-time factor at batch = 1 (SURVEY.md 8d config 1 at the metric's 22.05 kHz / hop 256): "
-                         + self.e.describe() + "; one utterance per step, nothing overlapped across steps",
-                         "per_gpu_batch": len(self.e.lens), "global_batch": len(self.e.lens) * self.world, "parallelism": "dp%d" % self.world}
         out["stage_ms"] = {k: v for k, v in st.items() if k != "total"}
         out["stage_ms_total"] = st["total"]
         cs = self.e.waveglow.__dict__.get("_facppg_cond_stream") if b1 else None
@@ -819,6 +844,12 @@ class CorpusWorkload(object):
         self.gathered = sc.collect(wavs, ids, self.world)
         return self.gathered
 
+    def outputs(self):
+        import numpy as np
+        ids = sorted(self.gathered)
+        return {"audio": torch.cat([self.gathered[i].reshape(-1).float().cpu() for i in ids]).numpy(),
+                "samples_per_utterance": np.asarray([self.gathered[i].numel() for i in ids], dtype=np.float64)}
+
     def start_timed(self):
         pass
 
@@ -846,22 +877,24 @@ class TrainWorkload(object):
         self.mel, self.audio = train_batch(dev, self.B, seed=1 + rank)
         self.exchange = None
         self.baseline_ms = None
+        self.full = bool(getattr(args, "full", True))
         if dist is not None:
-            # what the exchange COSTS a step: the same graphed step without it, timed first on this rank (a throw-away
-            # model of the same shape; 3 steps to capture, then the median of 6)
-            from waveglow.optim import Adam as _Adam
-            bm, bcrit = make_train_model(dev, "bf16")
-            bstep = GraphedTrainStep(bm, bcrit, _Adam(bm.parameters(), lr=1e-5), warmup=2)
-            ts = []
-            for i in range(10):
-                torch.cuda.synchronize(dev)
-                t0 = time.perf_counter()
-                bstep(self.mel, self.audio)
-                torch.cuda.synchronize(dev)
-                ts.append(time.perf_counter() - t0)
-            self.baseline_ms = sorted(ts[4:])[3] * 1e3 if bstep.graph is not None else None
-            del bstep, bm, bcrit
-            torch.cuda.empty_cache()
+            if self.full:
+                # what the exchange COSTS a step: the same graphed step without it, timed first on this rank (a throw-away
+                # model of the same shape; 3 steps to capture, then the median of 6)
+                from waveglow.optim import Adam as _Adam
+                bm, bcrit = make_train_model(dev, "bf16")
+                bstep = GraphedTrainStep(bm, bcrit, _Adam(bm.parameters(), lr=1e-5), warmup=2)
+                ts = []
+                for i in range(10):
+                    torch.cuda.synchronize(dev)
+                    t0 = time.perf_counter()
+                    bstep(self.mel, self.audio)
+                    torch.cuda.synchronize(dev)
+                    ts.append(time.perf_counter() - t0)
+                self.baseline_ms = sorted(ts[4:])[3] * 1e3 if bstep.graph is not None else None
+                del bstep, bm, bcrit
+                torch.cuda.empty_cache()
             broadcast_parameters(self.model, 0)
             self.exchange = GradientExchange(self.model, n_buckets=args.grad_buckets,
                                              grad_dtype=torch.bfloat16 if args.grad_dtype == "bf16" else None)
@@ -874,6 +907,13 @@ class TrainWorkload(object):
 
     def step(self, i):
         self.loss = self.stepper(self.mel, self.audio)
+
+    def outputs(self):
+        # the loss the step returns and a fixed sample of the parameters it updated (all of them: 350 MB)
+        import numpy as np
+        flat = torch.cat([p.detach().reshape(-1).float() for p in self.model.parameters()])
+        idx = torch.from_numpy(np.sort(np.random.Generator(np.random.PCG64(0)).integers(0, flat.numel(), DUMP_SAMPLE))).to(flat.device)
+        return {"loss": np.asarray([float(self.loss)], dtype=np.float64), "parameters_sample": flat[idx].cpu().numpy()}
 
     def start_timed(self):
         assert self.stepper.graph is not None or self.stepper.capture_failed, "need >= 3 warm-up steps before the timed region (capture)"
@@ -893,7 +933,7 @@ class TrainWorkload(object):
                          "graph_captured": self.stepper.graph is not None}
         out["tflops"] = flops / (ms * 1e-3) / 1e12
         out["frac_of_mfma_peak"] = out["tflops"] / (PEAK_BF16_MFMA_TFLOPS * self.world)
-        if self.exchange is not None:
+        if self.exchange is not None and self.full:
             # the exchange on its own, after the timed region (every rank gets here): all buckets launched, then waited for
             self.exchange.exchange()
             ex_ms = self.exchange.exchange_ms()
@@ -928,7 +968,7 @@ def isolated_extra(args, rank, world, dist, log, name, steps, warmup, timeout=60
             env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_PORT", "GROUP_RANK",
                                                                      "LOCAL_WORLD_SIZE", "ROLE_RANK", "TORCHELASTIC_RUN_ID")}
             cmd = [sys.executable, os.path.abspath(__file__), "--gpus", str(world), "--workload", name, "--steps", str(steps),
-                   "--warmup", str(warmup), "--no-extra", "--train-batch", str(args.train_batch), "--grad-buckets", str(args.grad_buckets),
+                   "--warmup", str(warmup), "--full", "--no-extra", "--train-batch", str(args.train_batch), "--grad-buckets", str(args.grad_buckets),
                    "--grad-dtype", args.grad_dtype, "--dist-backend", args.dist_backend, "--utterances", str(args.utterances),
                    "--corpus-batch", str(args.corpus_batch)]
             if args.share_gpu:
@@ -952,6 +992,28 @@ def isolated_extra(args, rank, world, dist, log, name, steps, warmup, timeout=60
     else:
         store.wait([key], datetime.timedelta(seconds=timeout + 120))
     return entry
+
+
+DUMP_BYTES = 64 << 20      # --dump-outputs: all files together
+DUMP_SAMPLE = 1 << 22      # elements kept of an output larger than its share of DUMP_BYTES
+
+
+def write_outputs(d, arrays, log):
+    """--dump-outputs: each array as d/<name>.npy in float32 (float64 where it was), so that two builds can be compared output
+    for output.  An array above its share of DUMP_BYTES is replaced by d/<name>_sample.npy: the elements of the flattened array
+    at a fixed sorted set of indices (PCG64(0)), the same from run to run for the same arguments."""
+    import numpy as np
+    os.makedirs(d, exist_ok=True)
+    share = DUMP_BYTES // max(1, len(arrays))
+    for name, a in arrays.items():
+        a = np.asarray(a)
+        a = a.astype(np.float64 if a.dtype == np.float64 else np.float32)
+        if a.nbytes > share:
+            k = min(DUMP_SAMPLE, share // a.itemsize)
+            a = a.reshape(-1)[np.sort(np.random.Generator(np.random.PCG64(0)).integers(0, a.size, k))]
+            name += "_sample"
+        np.save(os.path.join(d, name + ".npy"), a)
+        log("output %s: %s %s -> %s" % (name, a.dtype, tuple(a.shape), os.path.join(d, name + ".npy")))
 
 
 def timed_run(wl, steps, warmup, fence, dist, dev, backend):
@@ -989,11 +1051,16 @@ def main():
     ap.add_argument("--train-batch", type=int, default=3, help="train workload: per-GPU batch (config.json: 3)")
     ap.add_argument("--grad-buckets", type=int, default=3)
     ap.add_argument("--grad-dtype", choices=("fp32", "bf16"), default="fp32")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-e2e", action="store_true", help="skip the secondary end-to-end measurements (they use cooperative launches, "
-                    "which rocprofv3 on this stack does not survive)")
-    ap.add_argument("--no-train", action="store_true", help="skip the secondary training-step measurement")
-    ap.add_argument("--no-extra", action="store_true", help="N > 1 infer runs: skip the train_dp / corpus_dp entries")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure everything beyond the headline figure: roofline / stage breakdown, the other BASELINE configs, "
+                         "train_step, cpu_baseline, the train_dp / corpus_dp entries of N > 1 runs, the exchange cost of --workload train")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed to DIR/<name>.npy (float32 / float64, at most 64 MB in all)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline")
+    ap.add_argument("--no-e2e", action="store_true", help="--full: skip the secondary end-to-end measurements (they use cooperative "
+                    "launches, which rocprofv3 on this stack does not survive)")
+    ap.add_argument("--no-train", action="store_true", help="--full: skip the secondary training-step measurement")
+    ap.add_argument("--no-extra", action="store_true", help="--full, N > 1 infer runs: skip the train_dp / corpus_dp entries")
     ap.add_argument("--dist-backend", default="nccl", help=argparse.SUPPRESS)   # "gloo" + --share-gpu: 1-GPU dry run of the N>1 path
     ap.add_argument("--share-gpu", action="store_true", help=argparse.SUPPRESS)
     ap.add_argument("--force-dist", action="store_true", help=argparse.SUPPRESS)   # a process group even at N = 1: the RCCL code paths on ONE GPU
@@ -1057,6 +1124,9 @@ def main():
     log("%s workload ready; warmup" % args.workload)
     elapsed = timed_run(wl, args.steps, args.warmup, fence, dist, dev, args.dist_backend)
     log("timed region done: %.3f s" % elapsed)
+    if args.dump_outputs and rank == 0:
+        # (before finish(): with --full it runs further steps, which reuse the device buffers of the last timed one)
+        write_outputs(args.dump_outputs, wl.outputs(), log)
     value = wl.samples * args.steps / elapsed
     train = args.workload == "train"
     out = {
@@ -1069,7 +1139,7 @@ def main():
         "realtime_factor": value / (16000 if train else SR),
     }
     wl.finish(out, elapsed, args.steps)
-    secondary_ok = rank == 0 and world == 1 and headline and not args.force_dist
+    secondary_ok = args.full and rank == 0 and world == 1 and headline and not args.force_dist
     if secondary_ok and not args.no_e2e:
         # the other BASELINE configs next to the headline, each timed in this process with its own steps / ms_per_step / roofline
         try:
@@ -1096,7 +1166,7 @@ def main():
         if mel8 is not None:
             out["reference_rate_config"] = reference_rate_config(dev, mel8, log)
             del mel8
-    if dist is not None and (headline or args.workload == "infer") and not args.no_extra:
+    if args.full and dist is not None and (headline or args.workload == "infer") and not args.no_extra:
         # the two configs whose collectives matter, measured in the same multi-GPU invocation (short runs; a failure
         # is reported as null and never takes the primary figure down)
         del wl

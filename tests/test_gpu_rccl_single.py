@@ -24,7 +24,9 @@ def _bench(args, port):
     e = dict(os.environ, MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port), FACPPG_COOP_PLAIN="1")
     for k in ("RANK", "LOCAL_RANK", "WORLD_SIZE"):
         e.pop(k, None)
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--force-dist"] + args, capture_output=True, text=True, env=e, timeout=900)
+    # --full: the roofline, the train_dp / corpus_dp entries and the exchange cost these tests check are not in a plain run
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--force-dist", "--full"] + args, capture_output=True, text=True, env=e,
+                       timeout=900)
     assert r.returncode == 0, r.stderr[-3000:]
     return json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
 

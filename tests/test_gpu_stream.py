@@ -106,6 +106,18 @@ def test_blocks_that_time_out_are_redone_behind_the_decoder(vocoder, monkeypatch
     cs = wg.__dict__["_facppg_cond_stream"]
     assert seen["streamed"] and cs.void_blocks == 0 and np.array_equal(out, ref)
     monkeypatch.setenv("FACPPG_STREAM_WAIT_MS", "0.001")
+    # The frames must really be late.  The collectors start with the encoder and test the limit only every few hundred polls,
+    # and the first frame follows about a millisecond later: a fast encoder wins that race and no block times out.  A spin
+    # kernel behind the encoder, on the stream the decoder is launched on, holds the frames back for milliseconds.
+    from facppg import lib as flib
+    L = flib.load()
+    encode = L.facppg_taco_encode
+
+    def late_encode(*a):
+        rc = encode(*a)
+        torch.cuda._sleep(20_000_000)
+        return rc
+    monkeypatch.setattr(L, "facppg_taco_encode", late_encode)
     out, t_out, seen = run(taco, wg, den, ppg, em, dm, zs, True, monkeypatch)
     print("blocks", cs.cuts, "void", cs.void_blocks, "seeded frames", cs.seeded)
     assert seen["streamed"] and cs.void_blocks > 0 and cs.seeded < 160

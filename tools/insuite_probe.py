@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Why does bench.py's batch-1 headline run at 0.23 of the fp32 MFMA peak (0.20 ms per layer launch instead of 0.08) when it is a
 subprocess of the whole GPU test suite (tests/test_gpu_rccl_single.py), and at ~0.55 on its own?  The child is always
-`bench.py --steps 3 --warmup 2 --no-train --no-cpu-baseline [--force-dist]`; what varies is what the PARENT process holds on the GPU
+`bench.py --full --steps 3 --warmup 2 --no-train --no-cpu-baseline [--force-dist]`; what varies is what the PARENT process holds on the GPU
 while it waits.  A sampler thread logs the shader clock (rocm-smi) while the child runs.
 
   python tools/insuite_probe.py            all variants, one line each
@@ -43,7 +43,7 @@ def child(extra, port, child_env=None):
     th = threading.Thread(target=sample)
     th.start()
     t0 = time.time()
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "3", "--warmup", "2", "--no-train", "--no-cpu-baseline"] + extra,
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--steps", "3", "--warmup", "2", "--no-train", "--no-cpu-baseline"] + extra,
                        capture_output=True, text=True, env=env, timeout=900)
     stop.set()
     th.join()
