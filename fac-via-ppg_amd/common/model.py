@@ -19,11 +19,27 @@ Extensions over the reference signature (defaults reproduce it):
     step_limits    B integers: utterance b stops after min(step_limits[b], max_decoder_steps) frames at the
                    latest (per-utterance max_decoder_steps of a padded batch)
 """
+import collections
+
 import torch
 from torch import nn
 
 from common.layers import ConvNorm, LinearNorm
 from facppg import lib as _lib
+
+# One decoder launch as facppg_taco_decode reports it: mode 'single', 'coop' or 'split', its workgroups, and whether it published
+# its frames to the call's frame consumer.
+DecoderLaunch = collections.namedtuple("DecoderLaunch", "mode workgroups streamed")
+
+
+class InferenceOutputs(list):
+    """What Tacotron2.inference returns: the reference's [mel, mel_post, gate, alignments], carrying what THIS call did --
+    out_lengths (Tout per utterance, long, on the host) and launch (DecoderLaunch) -- so that calls on a shared model do not
+    read each other's results."""
+
+    def __init__(self, outputs, out_lengths, launch):
+        super(InferenceOutputs, self).__init__(outputs)
+        self.out_lengths, self.launch = out_lengths, launch
 
 
 class LocationLayer(nn.Module):
@@ -178,8 +194,8 @@ class Tacotron2(nn.Module):
         self._release()
         return super(Tacotron2, self).train(mode)
 
-    # CUs the decoder may occupy (facppg_taco_set_decoder_workgroups); 0 = the whole device.  facppg.pipeline.synthesize_stream
-    # sets it while the decoder runs under the previous batch's vocoder.
+    # CUs the decoder may occupy (facppg_taco_decode_opts.max_workgroups) unless a call says otherwise; 0 = the whole device.
+    # facppg.pipeline.synthesize_stream bounds its own calls while the decoder runs under the previous batch's vocoder.
     decoder_workgroups = 0
 
     def _handle(self, dev):
@@ -201,15 +217,12 @@ class Tacotron2(nn.Module):
         return out
 
     def last_decoder_launch(self):
-        """(mode, workgroups) of the most recent decoder launch (facppg_taco_last_decoder_launch): mode is 'single', 'coop' or
-        'split'."""
-        h = self.__dict__.get("_facppg_handle")
-        if h is None:
+        """(mode, workgroups) of the most recent decoder launch on this model: mode is 'single', 'coop' or 'split'.  For
+        single-threaded callers (tests, tools); a caller that shares the model reads the ``launch`` of inference's result."""
+        launch = self.__dict__.get("_last_launch")
+        if launch is None:
             raise _lib.FacppgError("last_decoder_launch: no inference has run on this model yet")
-        c = _lib.ctypes
-        mode, wgs = c.c_int(), c.c_int()
-        _lib.check(_lib.load().facppg_taco_last_decoder_launch(h[0], c.byref(mode), c.byref(wgs)))
-        return ("single", "coop", "split")[mode.value], wgs.value
+        return launch.mode, launch.workgroups
 
     def _apply(self, fn, *a, **k):
         self._release()
@@ -260,10 +273,13 @@ class Tacotron2(nn.Module):
         return enc_m, dec_m
 
     def inference(self, inputs, lengths=None, dropout_masks=None, seed=None, utterance_seeds=None, step_limits=None, timer=None,
-                  while_decoding=None, frame_consumer=None):
+                  while_decoding=None, frame_consumer=None, decoder_workgroups=None):
         """inputs [B, n_symbols, Tin] (GPU fp32) -> [mel, mel_post, gate, alignments]
         = [B,80,Tout], [B,80,Tout], [B,Tout,1], [B,Tout,Tin]  (model.py:597-610).  For B > 1 the
-        outputs are zero beyond each utterance's own Tout, kept in ``self.last_output_lengths``.
+        outputs are zero beyond each utterance's own Tout, kept in the result's ``out_lengths`` (InferenceOutputs).
+        Everything the call needs goes in as an argument and what it did comes back with the result: concurrent calls on one
+        model do not see each other's settings or results.
+        decoder_workgroups: the CUs the decoder may occupy (None: the model's ``decoder_workgroups``).
         while_decoding: optional callable run on the host after the decoder has been enqueued and before its output lengths
         are read back (facppg.pipeline checks the vocoder's packed weights there: ~0.4 ms that would otherwise sit between the
         acoustic model and the vocoder with the GPU idle).
@@ -325,29 +341,23 @@ class Tacotron2(nn.Module):
         gate = arena[offs[3]:offs[3] + sizes[3]].view(B, steps)
         align = arena[offs[4]:offs[4] + sizes[4]].view(B, steps, Tin)
         out_len = arena[offs[5]:offs[5] + sizes[5]].view(torch.int32)
-        _lib.check(L.facppg_taco_set_decoder_workgroups(h, int(self.decoder_workgroups)))
-        streaming = False
+        opts = _lib.TacoDecodeOpts(max_workgroups=int(self.decoder_workgroups if decoder_workgroups is None else decoder_workgroups))
         if frame_consumer is not None and B == 1:
             words = frame_consumer.begin(self, h, dev, steps, Tin)          # (zeroed on this stream, ahead of the decoder launch)
-            _lib.check(L.facppg_taco_set_frame_stream(h, _lib.ptr(words), steps if words is not None else 0))
+            if words is not None:
+                opts.frame_words_dev, opts.frame_words_frames = words.data_ptr(), steps
         with torch.cuda.device(dev):
             _lib.check(L.facppg_taco_encode(h, _lib.ptr(x), _lib.ptr(lt), _lib.ptr(enc_m), seed, B, Tin, _lib.ptr(memory),
                                             _lib.ptr(pm), _lib.ptr(ws), ws.numel(), st))
             if timer is not None:
                 timer.mark("encoder")
-            try:
-                _lib.check(L.facppg_taco_decode(h, _lib.ptr(memory), _lib.ptr(pm), _lib.ptr(lt), _lib.ptr(sl), _lib.ptr(dec_m), seed, B, Tin,
-                                                steps, _lib.ptr(mel), _lib.ptr(gate), _lib.ptr(align), _lib.ptr(out_len),
-                                                _lib.ptr(ws), ws.numel(), st))
-            finally:
-                if frame_consumer is not None and B == 1:     # (whatever happened: no later decode publishes into this call's buffer)
-                    L.facppg_taco_set_frame_stream(h, None, 0)
+            _lib.check(L.facppg_taco_decode(h, _lib.ptr(memory), _lib.ptr(pm), _lib.ptr(lt), _lib.ptr(sl), _lib.ptr(dec_m), seed, B, Tin,
+                                            steps, _lib.ptr(mel), _lib.ptr(gate), _lib.ptr(align), _lib.ptr(out_len),
+                                            _lib.ptr(ws), ws.numel(), _lib.ctypes.byref(opts), st))
+            launch = DecoderLaunch(("single", "coop", "split")[opts.mode], opts.workgroups, bool(opts.streamed))
             if frame_consumer is not None and B == 1:
-                flag = _lib.ctypes.c_int()
-                _lib.check(L.facppg_taco_last_decode_streamed(h, _lib.ctypes.byref(flag)))
-                streaming = bool(flag.value)
-                if streaming:
-                    frame_consumer.enqueue(out_len)            # its launches, gated on the frames, on its own stream
+                if launch.streamed:
+                    frame_consumer.enqueue(out_len, launch.workgroups)   # its launches, gated on the frames, on its own stream
                 else:
                     frame_consumer.cancel()
             if while_decoding is not None:                     # host work that needs no result of the decoder: the GPU is busy for
@@ -358,7 +368,7 @@ class Tacotron2(nn.Module):
             Tout = int(out_len_host.max())
             if Tout == int(self.decoder.max_decoder_steps):
                 print("Warning! Reached max decoder steps")     # model.py:527
-            mel_post = frame_consumer.finish(Tout, out_len) if streaming else None   # [1, NF, >= Tout] view: what is left of the postnet
+            mel_post = frame_consumer.finish(Tout, out_len) if launch.streamed else None   # [1, NF, >= Tout] view: what is left of the postnet
             if mel_post is None:
                 mel_post = torch.zeros_like(mel)
                 ws2 = torch.empty(L.facppg_taco_postnet_workspace_bytes(h, B, Tout), dtype=torch.uint8, device=dev)
@@ -366,6 +376,8 @@ class Tacotron2(nn.Module):
                                                  _lib.ptr(ws2), ws2.numel(), st))
             if timer is not None:
                 timer.mark("postnet")
-        self.last_output_lengths = out_len_host.to(torch.long)
-        self.last_memory = memory
-        return self.parse_output([mel[:, :, :Tout], mel_post[:, :, :Tout], gate[:, :Tout].unsqueeze(-1), align[:, :Tout]])
+        out_lengths = out_len_host.to(torch.long)
+        # (for single-threaded callers: tests, tools)
+        self.last_output_lengths, self.last_memory, self._last_launch = out_lengths, memory, launch
+        return InferenceOutputs(self.parse_output([mel[:, :, :Tout], mel_post[:, :, :Tout], gate[:, :Tout].unsqueeze(-1),
+                                                   align[:, :Tout]]), out_lengths, launch)

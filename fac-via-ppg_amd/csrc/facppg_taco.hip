@@ -34,12 +34,7 @@ struct facppg_taco {
   facppg_taco_config c;
   int device;
   int coop_limit;   // workgroups the cooperative (co-resident) kernels may use: from the occupancy calculator, see facppg_taco_create
-  int decoder_wg_limit;   // facppg_taco_set_decoder_workgroups: a tighter bound for the decoder alone (0 = none)
   int wall_khz;              // the device's constant-rate clock (facppg_taco_collect_frames bounds its wait in it)
-  unsigned long long* frame_stream;   // facppg_taco_set_frame_stream: tagged mel frames as the split decoder emits them (B = 1), or null
-  int frame_stream_frames;
-  int last_streamed;         // the most recent decode published its frames there
-  int last_mode, last_wgs;   // facppg_taco_last_decoder_launch: 0 one workgroup per utterance, 1 cooperative, 2 split; workgroups launched
   char* arena;
   // encoder
   float4 *pre0, *pre1, *conv[8], *wih;
@@ -1759,7 +1754,7 @@ extern "C" size_t facppg_taco_workspace_bytes(const facppg_taco* h, int B, int T
 }
 
 // Encoder.inference (model.py:237-249) + Attention.memory_layer (model.py:334).
-extern "C" int facppg_taco_encode(facppg_taco* h, const float* ppg_dev, const int32_t* lengths_dev, const uint8_t* masks_dev,
+extern "C" int facppg_taco_encode(const facppg_taco* h, const float* ppg_dev, const int32_t* lengths_dev, const uint8_t* masks_dev,
                                   uint64_t seed, int B, int Tin, float* memory_dev, float* pm_dev, void* ws_, size_t ws_bytes,
                                   void* stream_) {
   FACPPG_REQUIRE(h && ppg_dev && memory_dev && pm_dev && ws_, FACPPG_EINVAL, "NULL argument");
@@ -1894,12 +1889,13 @@ extern "C" int facppg_attention_window_mask(const int32_t* lengths_dev, int B, i
 }
 
 // Decoder.inference (model.py:489-535).
-extern "C" int facppg_taco_decode(facppg_taco* h, const float* memory_dev, const float* pm_dev, const int32_t* lengths_dev,
+extern "C" int facppg_taco_decode(const facppg_taco* h, const float* memory_dev, const float* pm_dev, const int32_t* lengths_dev,
                                   const int32_t* step_limits_dev, const uint8_t* masks_dev, uint64_t seed, int B, int Tin, int max_steps, float* mel_dev,
                                   float* gate_dev, float* align_dev, int32_t* out_lengths_dev, void* ws_, size_t ws_bytes,
-                                  void* stream_) {
+                                  facppg_taco_decode_opts* opts, void* stream_) {
   FACPPG_REQUIRE(h && memory_dev && pm_dev && mel_dev && gate_dev && out_lengths_dev && ws_, FACPPG_EINVAL, "NULL argument");
   FACPPG_REQUIRE(B > 0 && Tin > 0 && max_steps > 0, FACPPG_EINVAL, "bad B/Tin/max_steps");
+  FACPPG_REQUIRE(!opts || (opts->max_workgroups >= 0 && opts->frame_words_frames >= 0), FACPPG_EINVAL, "negative max_workgroups / frame_words_frames");
   FACPPG_REQUIRE(Tin <= 8192, FACPPG_EUNSUPPORTED, "Tin > 8192 does not fit the decoder's LDS state");
   const facppg_taco_config& c = h->c;
   hipStream_t s = (hipStream_t)stream_;
@@ -1913,7 +1909,7 @@ extern "C" int facppg_taco_decode(facppg_taco* h, const float* memory_dev, const
     masks = (const uint8_t*)(ws + w.mask);
   }
   DecArgs a;
-  a.melx = nullptr; h->last_streamed = 0;
+  a.melx = nullptr;
   a.dp0_t = h->dp0_t; a.dp1_t = h->dp1_t; a.att_t = h->att_t; a.att_b = h->att_b; a.dec_t = h->dec_t; a.dec_b = h->dec_b;
   a.q_t = h->q_t; a.proj_t = h->proj_t; a.proj_b = h->proj_b; a.loc_conv = h->loc_conv; a.loc_dense = h->loc_dense; a.v = h->v;
   a.xchg = (unsigned long long*)(ws + w.xchg);
@@ -1930,7 +1926,9 @@ extern "C" int facppg_taco_decode(facppg_taco* h, const float* memory_dev, const
   // slice width: the narrowest (most workgroups per utterance) that keeps B * NWG co-resident (coop_limit)
   // the decoder holds a CU's whole LDS per workgroup: a caller that runs it UNDER another stream's kernels (the vocoder of
   // the previous batch, facppg.pipeline.synthesize_stream) bounds the CUs it takes away from them
-  const int wg_limit = h->decoder_wg_limit > 0 && h->decoder_wg_limit < h->coop_limit ? h->decoder_wg_limit : h->coop_limit;
+  const int max_wgs = opts ? opts->max_workgroups : 0;
+  const int wg_limit = max_wgs > 0 && max_wgs < h->coop_limit ? max_wgs : h->coop_limit;
+  int launch_mode = 0, launch_wgs = B;   // reported in opts: 0 k_decoder (one workgroup per utterance), 1 k_decoder_coop, 2 k_decoder_split
   const char* mode = getenv("FACPPG_DECODER_MODE");
   int variant = -1;
   const char* force_u = getenv("FACPPG_DECODER_COOP_U");   // tests / tuning: a specific slice width
@@ -1974,11 +1972,11 @@ extern "C" int facppg_taco_decode(facppg_taco* h, const float* memory_dev, const
     void* args[] = {(void*)&a};
     const int groups = (B + NU - 1) / NU;
     a.nwk = h->split_nwk;
-    a.melx = (B == 1 && h->frame_stream && h->frame_stream_frames >= max_steps) ? h->frame_stream : nullptr;
-    h->last_streamed = a.melx != nullptr;
+    unsigned long long* words = opts ? (unsigned long long*)opts->frame_words_dev : nullptr;
+    a.melx = (B == 1 && words && opts->frame_words_frames >= max_steps) ? words : nullptr;
     a.dbg_flags = getenv("FACPPG_DECODER_NO_ROWS") ? 1 : 0;
     FACPPG_HIP_CHECK(launch_coop(fn, dim3(h->split_nwk + NU, groups), dim3(NTC), args, ssm, s));
-    h->last_mode = 2; h->last_wgs = (h->split_nwk + NU) * groups;
+    launch_mode = 2; launch_wgs = (h->split_nwk + NU) * groups;
     if (a.prof) {
       long long pr[32];
       FACPPG_HIP_CHECK(hipMemcpyAsync(pr, a.prof, sizeof(pr), hipMemcpyDeviceToHost, s));
@@ -2003,7 +2001,7 @@ extern "C" int facppg_taco_decode(facppg_taco* h, const float* memory_dev, const
       a.b0 = b0; a.att_coop = h->att_coop[cv]; a.dec_coop = h->dec_coop[cv]; a.U = h->coop_U[cv];
       void* args[] = {(void*)&a};
       FACPPG_HIP_CHECK(launch_coop(fn, dim3(h->coop_nwg[cv], nb), dim3(NTC), args, smem, s));
-      h->last_mode = 1; h->last_wgs = h->coop_nwg[cv] * nb;
+      launch_mode = 1; launch_wgs = h->coop_nwg[cv] * nb;
     }
     if (a.prof) {
       long long pr[16];
@@ -2015,14 +2013,14 @@ extern "C" int facppg_taco_decode(facppg_taco* h, const float* memory_dev, const
   } else {
     FACPPG_HIP_CHECK(hipFuncSetAttribute((const void*)k_decoder, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem));
     k_decoder<<<B, NT, smem, s>>>(a);
-    h->last_mode = 0; h->last_wgs = B;
   }
   FACPPG_HIP_CHECK(hipGetLastError());
+  if (opts) { opts->mode = launch_mode; opts->workgroups = launch_wgs; opts->streamed = a.melx != nullptr; }
   return FACPPG_OK;
 }
 
 // Postnet + residual (model.py:178-184, 604-605): mel_post = mel + postnet(mel).
-extern "C" int facppg_taco_postnet(facppg_taco* h, const float* mel_dev, const int32_t* out_lengths_dev, int B, int T, int ld,
+extern "C" int facppg_taco_postnet(const facppg_taco* h, const float* mel_dev, const int32_t* out_lengths_dev, int B, int T, int ld,
                                    float* mel_post_dev, void* ws_, size_t ws_bytes, void* stream_) {
   FACPPG_REQUIRE(h && mel_dev && mel_post_dev && ws_, FACPPG_EINVAL, "NULL argument");
   FACPPG_REQUIRE(B > 0 && T > 0 && ld >= T, FACPPG_EINVAL, "bad B/T/ld");
@@ -2059,12 +2057,6 @@ extern "C" size_t facppg_taco_postnet_workspace_bytes(const facppg_taco* h, int 
   if (!h || B <= 0 || T <= 0) return 0;
   const size_t sk = (size_t)16 * B * h->c.postnet_embedding_dim * T * 4;   // split-K partial sums
   return (size_t)2 * B * h->c.postnet_embedding_dim * T * 4 + sk;
-}
-
-extern "C" int facppg_taco_set_decoder_workgroups(facppg_taco* h, int max_workgroups) {
-  FACPPG_REQUIRE(h && max_workgroups >= 0, FACPPG_EINVAL, "NULL handle or negative limit");
-  h->decoder_wg_limit = max_workgroups;
-  return FACPPG_OK;
 }
 
 // ------------------------------------------------------------------------------------------
@@ -2115,18 +2107,6 @@ __global__ __launch_bounds__(256) void k_collect_frames(const unsigned long long
 }
 }  // namespace
 
-extern "C" int facppg_taco_set_frame_stream(facppg_taco* h, void* words_dev, int frames) {
-  FACPPG_REQUIRE(h && frames >= 0 && (words_dev || frames == 0), FACPPG_EINVAL, "NULL handle, or a NULL buffer with frames > 0");
-  h->frame_stream = (unsigned long long*)words_dev; h->frame_stream_frames = words_dev ? frames : 0;
-  return FACPPG_OK;
-}
-
-extern "C" int facppg_taco_last_decode_streamed(const facppg_taco* h, int* streamed) {
-  FACPPG_REQUIRE(h && streamed, FACPPG_EINVAL, "NULL argument");
-  *streamed = h->last_streamed;
-  return FACPPG_OK;
-}
-
 extern "C" int facppg_taco_collect_frames(const facppg_taco* h, const void* words_dev, const int32_t* out_length_dev, int frame_a,
                                           int frame_b, float* mel_dev, int ld, int32_t* void_flag_dev, const int32_t* prev_flag_dev,
                                           void* stream_) {
@@ -2155,7 +2135,7 @@ extern "C" size_t facppg_taco_postnet_stream_workspace_bytes(const facppg_taco* 
   return (n - 1) * PE * max_frames * 4 + (size_t)16 * PE * max_frames * 4;
 }
 
-extern "C" int facppg_taco_postnet_range(facppg_taco* h, const float* mel_dev, int ld, int f_prev, int f_new, int final_T,
+extern "C" int facppg_taco_postnet_range(const facppg_taco* h, const float* mel_dev, int ld, int f_prev, int f_new, int final_T,
                                          float* mel_post_dev, int ld_post, void* ws_, size_t ws_bytes, int max_frames,
                                          const int32_t* skip_dev, void* stream_) {
   FACPPG_REQUIRE(h && mel_dev && mel_post_dev && ws_, FACPPG_EINVAL, "NULL argument");
@@ -2190,12 +2170,6 @@ extern "C" int facppg_taco_postnet_range(facppg_taco* h, const float* mel_dev, i
     src_hi = hi > 0 ? hi : 0;   // the next layer reads this one's final columns only
     if (src_hi == 0) break;
   }
-  return FACPPG_OK;
-}
-
-extern "C" int facppg_taco_last_decoder_launch(const facppg_taco* h, int* mode, int* workgroups) {
-  FACPPG_REQUIRE(h && mode && workgroups, FACPPG_EINVAL, "NULL argument");
-  *mode = h->last_mode; *workgroups = h->last_wgs;
   return FACPPG_OK;
 }
 

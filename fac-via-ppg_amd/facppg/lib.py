@@ -38,6 +38,12 @@ class TacoConfig(ctypes.Structure):
         [("gate_threshold", ctypes.c_float), ("bn_eps", ctypes.c_float)]
 
 
+class TacoDecodeOpts(ctypes.Structure):
+    """facppg_taco_decode_opts (include/facppg.h): the inputs, then the launch report the call fills in."""
+    _fields_ = [("max_workgroups", ctypes.c_int32), ("frame_words_dev", ctypes.c_void_p), ("frame_words_frames", ctypes.c_int32),
+                ("mode", ctypes.c_int32), ("workgroups", ctypes.c_int32), ("streamed", ctypes.c_int32)]
+
+
 class WnWeights(ctypes.Structure):
     """facppg_wn_weights (include/facppg.h)."""
     _fields_ = [("start_w", ctypes.c_void_p), ("start_b", ctypes.c_void_p),
@@ -147,16 +153,13 @@ def _declare(lib):
         "facppg_taco_destroy": (None, [vp]),
         "facppg_taco_workspace_bytes": (sz, [vp, c.c_int, c.c_int]),
         "facppg_taco_decode_workspace_bytes": (sz, [vp, c.c_int, c.c_int]),
-        "facppg_taco_set_decoder_workgroups": (c.c_int, [vp, c.c_int]),
-        "facppg_taco_last_decoder_launch": (c.c_int, [vp, c.POINTER(c.c_int), c.POINTER(c.c_int)]),
-        "facppg_taco_set_frame_stream": (c.c_int, [vp, vp, c.c_int]),
-        "facppg_taco_last_decode_streamed": (c.c_int, [vp, c.POINTER(c.c_int)]),
         "facppg_taco_collect_frames": (c.c_int, [vp, vp, vp, c.c_int, c.c_int, vp, c.c_int, vp, vp, vp]),
         "facppg_taco_postnet_stream_workspace_bytes": (sz, [vp, c.c_int]),
         "facppg_taco_postnet_range": (c.c_int, [vp, vp, c.c_int, c.c_int, c.c_int, c.c_int, vp, c.c_int, vp, sz, c.c_int, vp, vp]),
         "facppg_taco_postnet_workspace_bytes": (sz, [vp, c.c_int, c.c_int]),
         "facppg_taco_encode": (c.c_int, [vp, vp, vp, vp, u64, c.c_int, c.c_int, vp, vp, vp, sz, vp]),
-        "facppg_taco_decode": (c.c_int, [vp, vp, vp, vp, vp, vp, u64, c.c_int, c.c_int, c.c_int, vp, vp, vp, vp, vp, sz, vp]),
+        "facppg_taco_decode": (c.c_int, [vp, vp, vp, vp, vp, vp, u64, c.c_int, c.c_int, c.c_int, vp, vp, vp, vp, vp, sz,
+                                         c.POINTER(TacoDecodeOpts), vp]),
         "facppg_taco_draw_dropout": (c.c_int, [vp, vp, c.c_int, c.c_int, c.c_int, vp, vp, vp]),
         "facppg_wg_draw_noise": (c.c_int, [vp, vp, c.c_int, c.c_int, vp, vp]),
         "facppg_taco_postnet": (c.c_int, [vp, vp, vp, c.c_int, c.c_int, c.c_int, vp, vp, sz, vp]),

@@ -57,7 +57,7 @@ class ConditioningStream(object):
     """One utterance at a time (the metric's "batch = 1" case): work that depends on the mel frames ALONE, done while the decoder
     is still producing them, on the ~180 CUs its launch leaves empty.
 
-    The split decoder publishes every frame the moment it exists (facppg_taco_set_frame_stream); on a second HIP stream, gated
+    The split decoder publishes every frame the moment it exists (facppg_taco_decode_opts); on a second HIP stream, gated
     on those frames (facppg_taco_collect_frames), this object runs per block of frames
       * the postnet as a streaming convolution stack (facppg_taco_postnet_range: same sums, same order, same bits as the one-shot
         launch) straight into the vocoder's zero-margined mel buffer, and
@@ -206,8 +206,9 @@ class ConditioningStream(object):
     def cancel(self):
         self.active = False
 
-    def enqueue(self, out_len):
-        """The decoder has been launched and publishes its frames: enqueue every planned block on the side stream."""
+    def enqueue(self, out_len, decoder_workgroups):
+        """The decoder has been launched (on ``decoder_workgroups`` CUs) and publishes its frames: enqueue every planned block on
+        the side stream."""
         from facppg import lib as _lib
         L = _lib.load()
         dev, steps = self.dev, self.steps
@@ -220,7 +221,7 @@ class ConditioningStream(object):
         # first launches behind the decoder on the main stream -- next to a pass's workgroups, where they crawl (3-5x, measured).
         n_cu = torch.cuda.get_device_properties(dev).multi_processor_count
         spare = int(os.environ.get("FACPPG_STREAM_SPARE_CUS", "8"))
-        bound = max(16, n_cu - self.tacotron.last_decoder_launch()[1] - spare) if spare >= 0 else 0
+        bound = max(16, n_cu - decoder_workgroups - spare) if spare >= 0 else 0
         self.n_launch = 0
         self.last_final, self.finals, self.flow_events = None, [], {}
 
@@ -385,20 +386,22 @@ def pad_ppgs(ppgs, device=None):
     return x, lens
 
 
-def _acoustic(ppgs, tacotron, seed, dropout_masks, utterance_seeds, step_limits, timer=None, while_decoding=None, consumer=None):
+def _acoustic(ppgs, tacotron, seed, dropout_masks, utterance_seeds, step_limits, timer=None, while_decoding=None, consumer=None,
+              decoder_workgroups=None):
     """PPG upload + Tacotron2.inference on the current stream -> (mel_post [B, 80, Tout], [Tout_i]).  Blocks the host once,
     for the decoder's output lengths."""
     dev = next(tacotron.parameters()).device
     x, lens = pad_ppgs(ppgs, device=dev)
     if timer is not None:
         timer.mark("ppg_upload")
-    _, mel_post, _, _ = tacotron.inference(x, lengths=lens if len(lens) > 1 else None, dropout_masks=dropout_masks,
-                                           seed=seed, utterance_seeds=utterance_seeds, step_limits=step_limits,
-                                           while_decoding=while_decoding, frame_consumer=consumer if len(lens) == 1 else None,
-                                           **({"timer": timer} if timer is not None else {}))
+    out = tacotron.inference(x, lengths=lens if len(lens) > 1 else None, dropout_masks=dropout_masks,
+                             seed=seed, utterance_seeds=utterance_seeds, step_limits=step_limits,
+                             while_decoding=while_decoding, frame_consumer=consumer if len(lens) == 1 else None,
+                             decoder_workgroups=decoder_workgroups, **({"timer": timer} if timer is not None else {}))
+    mel_post, tout = out[1], [int(v) for v in out.out_lengths]
     if consumer is not None and consumer.active:      # (the vocoder reads the stream's own mel buffer: no copy on the latency path)
-        return mel_post, [int(v) for v in tacotron.last_output_lengths]
-    return mel_post.contiguous(), [int(v) for v in tacotron.last_output_lengths]
+        return mel_post, tout
+    return mel_post.contiguous(), tout
 
 
 def _vocode(mel_post, tout, waveglow, denoiser, sigma, strength, seed, z, utterance_seeds, timer=None, consumer=None):
@@ -482,8 +485,8 @@ def synthesize_stream(jobs, tacotron, waveglow, denoiser=None, sigma=0.6, streng
     synthesize() on the same job: the stages, their inputs and their random streams are the same, only their placement in
     time differs (tests/test_gpu_e2e.py).  overlap=False runs the same jobs back to back on the caller's stream.
 
-    acoustic_workgroups: while overlapped, the decoder is held to this many CUs (Tacotron2.decoder_workgroups, unless the model
-    already carries a bound of its own).  A decoder workgroup owns its CU's LDS, so the vocoder loses every CU the decoder
+    acoustic_workgroups: while overlapped, each acoustic call holds its decoder to this many CUs (unless the model carries a bound
+    of its own, Tacotron2.decoder_workgroups).  A decoder workgroup owns its CU's LDS, so the vocoder loses every CU the decoder
     sits on; on the whole chip (240 workgroups for 16 utterances) the two stages merely take turns (146.7 -> 140.2 ms per
     batch), on 32 CUs the decoder takes 60 instead of 18 ms -- still hidden -- and the vocoder keeps 7/8 of the chip
     (128.3 ms; profiles/r03_experiments.txt).  The slice width that goes with the bound cuts the decoder's LSTM sums
@@ -497,13 +500,9 @@ def synthesize_stream(jobs, tacotron, waveglow, denoiser=None, sigma=0.6, streng
     def acoustic(job):
         with torch.no_grad(), torch.cuda.stream(side):
             # (the inputs are host arrays: nothing on the caller's stream to wait for -- in particular not the previous vocoder)
-            bound = tacotron.decoder_workgroups
-            if overlap and not bound and acoustic_workgroups:
-                tacotron.decoder_workgroups = int(acoustic_workgroups)
-            try:
-                mel_post, tout = _acoustic(job["ppgs"], tacotron, job.get("seed"), None, job.get("utterance_seeds"), job.get("step_limits"))
-            finally:
-                tacotron.decoder_workgroups = bound
+            bound = tacotron.decoder_workgroups or (int(acoustic_workgroups or 0) if overlap else 0)
+            mel_post, tout = _acoustic(job["ppgs"], tacotron, job.get("seed"), None, job.get("utterance_seeds"), job.get("step_limits"),
+                                       decoder_workgroups=bound)
             done = torch.cuda.Event()
             done.record(side)
         mel_post.record_stream(main)

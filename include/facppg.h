@@ -437,27 +437,10 @@ void facppg_taco_destroy(facppg_taco* h);
 size_t facppg_taco_workspace_bytes(const facppg_taco* h, int B, int Tin);
 size_t facppg_taco_decode_workspace_bytes(const facppg_taco* h, int B, int max_steps);
 size_t facppg_taco_postnet_workspace_bytes(const facppg_taco* h, int B, int T);
-/* Bounds the workgroups (= CUs: a decoder workgroup holds a CU's whole LDS) later facppg_taco_decode calls on this handle may
- * occupy; 0 = no bound beyond the device's.  No reference counterpart (the reference decodes one utterance at a time on
- * the whole device, model.py:489-535): it exists for callers that run the latency-bound decoder of the NEXT batch on a second
- * stream under the MFMA-bound vocoder of the current one (facppg.pipeline.synthesize_stream) and want it to take few CUs
- * away from the vocoder.  A tighter bound selects wider weight slices per workgroup, which cuts the LSTM sums differently:
- * results agree with the unbounded launch to rounding (1e-6 relative on the mel), not bit for bit. */
-int facppg_taco_set_decoder_workgroups(facppg_taco* h, int max_workgroups);
-/* Which decoder kernel the most recent facppg_taco_decode launched (tests assert the shape they mean to cover, as
- * facppg_wg_last_launch_shape does for the vocoder): *mode = 0 one workgroup per utterance (k_decoder), 1 cooperative
- * slices (k_decoder_coop), 2 split (k_decoder_split: one attention workgroup per utterance + register-resident dense-layer
- * workers); *workgroups = workgroups of that launch.  The reference has one code path (model.py:489-535). */
-int facppg_taco_last_decoder_launch(const facppg_taco* h, int* mode, int* workgroups);
 
-/* ---- the decoder's frames while it is still producing them (B = 1, split decoder).  The reference's decoder appends a frame per
- * step to a Python list (model.py:516-531) and the postnet runs on the finished spectrogram (model.py:604-605); here a
- * consumer on another stream may start on the frames as they appear.
- * facppg_taco_set_frame_stream: words_dev = [frames * n_feat] 8-byte words, ZEROED by the caller before every decode, or NULL
- *   to switch publishing off.  The next facppg_taco_decode with B = 1 whose launch is the split decoder and whose max_steps <=
- *   frames then stores every mel value of frame t ALSO as the word {value, t + 1} at words[t * n_feat + row] with an
- *   agent-scope store the moment it exists (the plain mel_dev stores are only guaranteed visible once the launch has ended).
- *   facppg_taco_last_decode_streamed tells whether the most recent decode did.
+/* ---- the decoder's frames while it is still producing them (B = 1, split decoder; facppg_taco_decode_opts.frame_words_dev).
+ * The reference's decoder appends a frame per step to a Python list (model.py:516-531) and the postnet runs on the finished
+ * spectrogram (model.py:604-605); here a consumer on another stream may start on the frames as they appear.
  * facppg_taco_collect_frames: waits (bounded in wall-clock time, FACPPG_POLL_LIMIT) for frames [frame_a, frame_b) and writes
  *   them channel-major into mel_dev [n_feat][ld].  If the decoder stops short of frame_b (out_length_dev, the decode call's
  *   output, becomes > 0 and <= a wanted frame) the block is VOID: *void_flag_dev = 1 and nothing more is waited for; a block
@@ -469,13 +452,11 @@ int facppg_taco_last_decoder_launch(const facppg_taco* h, int* mode, int* workgr
  *   every layer runs up to final_T with the convolutions' zero padding behind it.  Every output column is the sum, in the
  *   order, of facppg_taco_postnet's: same bits.  The workspace (facppg_taco_postnet_stream_workspace_bytes(h, max_frames))
  *   carries the layers' columns from call to call.  *skip_dev != 0 (device, may be NULL): the call's launches do nothing. */
-int facppg_taco_set_frame_stream(facppg_taco* h, void* words_dev, int frames);
-int facppg_taco_last_decode_streamed(const facppg_taco* h, int* streamed);
 int facppg_taco_collect_frames(const facppg_taco* h, const void* words_dev, const int32_t* out_length_dev, int frame_a,
                                int frame_b, float* mel_dev, int ld, int32_t* void_flag_dev, const int32_t* prev_flag_dev,
                                void* stream);
 size_t facppg_taco_postnet_stream_workspace_bytes(const facppg_taco* h, int max_frames);
-int facppg_taco_postnet_range(facppg_taco* h, const float* mel_dev, int ld, int f_prev, int f_new, int final_T,
+int facppg_taco_postnet_range(const facppg_taco* h, const float* mel_dev, int ld, int f_prev, int f_new, int final_T,
                               float* mel_post_dev, int ld_post, void* workspace_dev, size_t workspace_bytes,
                               int max_frames, const int32_t* skip_dev, void* stream);
 
@@ -486,7 +467,7 @@ int facppg_taco_postnet_range(facppg_taco* h, const float* mel_dev, int ld, int 
  * (the prenet's two always-on p=0.5 dropouts, model.py:132-135).
  * Outputs: memory_dev [B][Tin][E] and processed-memory pm_dev [B][attention_dim][Tin] (an opaque
  * intermediate handed to facppg_taco_decode; positions contiguous). */
-int facppg_taco_encode(facppg_taco* h, const float* ppg_dev, const int32_t* lengths_dev,
+int facppg_taco_encode(const facppg_taco* h, const float* ppg_dev, const int32_t* lengths_dev,
                        const uint8_t* masks_dev, uint64_t seed, int B, int Tin, float* memory_dev,
                        float* pm_dev, void* workspace_dev, size_t workspace_bytes, void* stream);
 /* Replaces Decoder.inference (model.py:489-535) including the attention window mask
@@ -500,13 +481,35 @@ int facppg_taco_encode(facppg_taco* h, const float* ppg_dev, const int32_t* leng
  * workgroup each plus register-resident dense-layer workers shared by 1-3 of them, up to 120 as 2-38 cooperating workgroups
  * (larger batches in chunks of 120), one workgroup per utterance as the fallback; the first two use hipLaunchCooperativeKernel (the workgroups
  * of an utterance must be co-resident) and every shape returns the same values to fp32 round-off.
- * FACPPG_DECODER_MODE=split|coop|single forces one (FACPPG_EUNSUPPORTED if B does not allow it). */
-int facppg_taco_decode(facppg_taco* h, const float* memory_dev, const float* pm_dev,
+ * FACPPG_DECODER_MODE=split|coop|single forces one (FACPPG_EUNSUPPORTED if B does not allow it).
+ * opts NULL, or the call's own options and launch report (the handle holds no per-call state):
+ *   max_workgroups bounds the workgroups (= CUs: a decoder workgroup holds a CU's whole LDS) the launch may occupy; 0 = no bound
+ *     beyond the device's.  No reference counterpart (the reference decodes one utterance at a time on the whole device): it
+ *     exists for callers that run the latency-bound decoder of the NEXT batch on a second stream under the MFMA-bound vocoder
+ *     of the current one (facppg.pipeline.synthesize_stream) and want it to take few CUs away from the vocoder.  A tighter
+ *     bound selects wider weight slices per workgroup, which cuts the LSTM sums differently: results agree with the unbounded
+ *     launch to rounding (1e-6 relative on the mel), not bit for bit.
+ *   frame_words_dev NULL, or [frame_words_frames * n_feat] 8-byte words ZEROED by the caller: if B = 1, the launch is the split
+ *     decoder and max_steps <= frame_words_frames, every mel value of frame t is ALSO stored as the word {value, t + 1} at
+ *     words[t * n_feat + row] with an agent-scope store the moment it exists (the plain mel_dev stores are only guaranteed
+ *     visible once the launch has ended); otherwise nothing is published.
+ *   Filled in by the call: mode = 0 one workgroup per utterance (k_decoder), 1 cooperative slices (k_decoder_coop), 2 split
+ *     (k_decoder_split); workgroups = workgroups of that launch (of the last one when a large batch runs in chunks);
+ *     streamed = 1 if the frames were published. */
+typedef struct facppg_taco_decode_opts {
+  int32_t max_workgroups;       /* in: 0 = no bound */
+  void* frame_words_dev;        /* in: NULL = publish nothing */
+  int32_t frame_words_frames;   /* in */
+  int32_t mode;                 /* out */
+  int32_t workgroups;           /* out */
+  int32_t streamed;             /* out */
+} facppg_taco_decode_opts;
+int facppg_taco_decode(const facppg_taco* h, const float* memory_dev, const float* pm_dev,
                        const int32_t* lengths_dev, const int32_t* step_limits_dev,
                        const uint8_t* masks_dev, uint64_t seed, int B,
                        int Tin, int max_steps, float* mel_dev, float* gate_dev, float* align_dev,
                        int32_t* out_lengths_dev, void* workspace_dev, size_t workspace_bytes,
-                       void* stream);
+                       facppg_taco_decode_opts* opts, void* stream);
 /* The always-on p=0.5 dropout draws of both prenets (Prenet.forward, model.py:132-135) as PER-UTTERANCE
  * streams keyed by seeds_dev[b] (uint64 [B]): enc_masks_dev uint8 [2][B][symbols_embedding_dim][Tin] and
  * dec_masks_dev uint8 [max_steps][2][B][prenet_dim] in the layouts facppg_taco_encode / _decode accept
@@ -523,7 +526,7 @@ int facppg_attention_window_mask(const int32_t* lengths_dev, int B, int Tmax, in
                                  int time_step, uint8_t* mask_dev, void* stream);
 /* Replaces Postnet.forward + the residual add (model.py:178-184, 604-605):
  * mel_dev [B][n_feat][ld] (first T columns used) -> mel_post_dev, same layout. */
-int facppg_taco_postnet(facppg_taco* h, const float* mel_dev, const int32_t* out_lengths_dev,
+int facppg_taco_postnet(const facppg_taco* h, const float* mel_dev, const int32_t* out_lengths_dev,
                         int B, int T, int ld, float* mel_post_dev, void* workspace_dev,
                         size_t workspace_bytes, void* stream);
 

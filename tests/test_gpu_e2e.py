@@ -180,7 +180,17 @@ def test_config3_batch16_ragged_end_to_end(checkpoints, monkeypatch):
     # ... and with the decoder held to 32 CUs (the default while overlapped: 2 workgroups per utterance instead of 15) they are
     # those of synthesize() under the same bound, bit for bit, and those of the unbounded decoder to rounding
     monkeypatch.delenv("FACPPG_DECODER_COOP_U")
+    from facppg import lib as flib
+    L = flib.load()
+    encode, model_bound = L.facppg_taco_encode, []
+
+    def encode_spy(*a):                    # inside the acoustic call's window
+        model_bound.append(taco.decoder_workgroups)
+        return encode(*a)
+    monkeypatch.setattr(L, "facppg_taco_encode", encode_spy)
     bounded = list(pipeline.synthesize_stream(jobs[1:3], taco, wg, den, sigma=0.6, strength=0.005, return_device=False))
+    monkeypatch.setattr(L, "facppg_taco_encode", encode)
+    assert model_bound == [0, 0]           # the bound travels with each call: the shared model's default is never touched
     assert taco.decoder_workgroups == 0
     taco.decoder_workgroups = 32
     ref32, t32 = pipeline.synthesize(ppgs, taco, wg, den, sigma=0.6, strength=0.005, utterance_seeds=seeds, step_limits=lens)

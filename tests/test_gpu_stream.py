@@ -51,6 +51,7 @@ def run(taco, wg, den, ppg, em, dm, zs, stream, monkeypatch):
         out = inference(*a, **kw)
         seen["mel_post"] = out[1].detach().clone()
         seen["streamed"] = kw.get("frame_consumer") is not None and kw["frame_consumer"].active
+        seen["published"] = out.launch.streamed
         return out
     taco.inference = spy
     try:
@@ -80,6 +81,7 @@ def test_streamed_utterance_equals_the_unstreamed_path_bit_for_bit(vocoder, Tin,
     # is finished by the one-shot postnet and the ordinary vocoder
     cap = min(steps, -(-(Tin + ConditioningStream.SLACK) // 32) * 32)
     assert not seen_ref["streamed"] and seen["streamed"] == (min(steps, Tin) >= 64 and t_ref <= cap)
+    assert not seen_ref["published"] and seen["published"] == (min(steps, Tin) >= 64)
     assert taco.last_decoder_launch()[0] == "split"
     assert t_out == t_ref and (gate_bias > -1 or t_ref == steps)
     cs = wg.__dict__["_facppg_cond_stream"]
@@ -122,6 +124,51 @@ def test_blocks_that_time_out_are_redone_behind_the_decoder(vocoder, monkeypatch
     print("blocks", cs.cuts, "void", cs.void_blocks, "seeded frames", cs.seeded)
     assert seen["streamed"] and cs.void_blocks > 0 and cs.seeded < 160
     assert t_out == t_ref and np.array_equal(out, ref)
+
+
+def test_a_decode_inside_a_streamed_call_publishes_nothing_into_it(vocoder, monkeypatch):
+    """The frame words and the launch report travel with each facppg_taco_decode call, not on the shared handle.  A second,
+    unstreamed B = 1 call on the same model inside a streamed call's window -- frame words zeroed, decoder not launched yet: what a
+    second thread on the same models may do -- leaves those words alone, and each utterance equals its own serial, unstreamed
+    result bit for bit.  The nested call runs from the streamed call's encode, where the window is open."""
+    cfg, wg, den = vocoder
+    Tin = steps = 200
+    hp, taco = acoustic(steps, -10.0)
+    ppg = synth.synthetic_ppg(Tin, 5816, seed=8, alpha=0.002)
+    em = masks_from_seed(81, (2, 1, Tin, hp.symbols_embedding_dim))
+    dm = masks_from_seed(82, (steps, 2, 1, hp.prenet_dim))
+    zs = synth.synthetic_z(1, steps * HOP // 8, cfg, seed=83)
+    x2 = torch.from_numpy(synth.synthetic_ppg(Tin, 5816, seed=9, alpha=0.002).T.copy()).unsqueeze(0).cuda()
+    em2 = masks_from_seed(84, (2, 1, Tin, hp.symbols_embedding_dim))
+    dm2 = masks_from_seed(85, (steps, 2, 1, hp.prenet_dim))
+    inference = taco.inference
+
+    def second_utterance():
+        with contextlib.redirect_stdout(io.StringIO()):
+            out = inference(x2, dropout_masks=(em2, dm2))
+        return [o.cpu().numpy() for o in out], out.launch
+    serial, _ = second_utterance()
+    ref, t_ref, _ = run(taco, wg, den, ppg, em, dm, zs, False, monkeypatch)
+    from facppg import lib as flib
+    L = flib.load()
+    encode = L.facppg_taco_encode
+    nested = {}
+
+    def encode_then_second_utterance(*a):
+        rc = encode(*a)
+        if not nested:                                   # (the nested call's own encode is the real one)
+            nested["running"] = True
+            words = wg.__dict__["_facppg_cond_stream"].words
+            nested["outputs"], nested["launch"] = second_utterance()
+            nested["words_untouched"] = not bool((words != 0).any())
+        return rc
+    monkeypatch.setattr(L, "facppg_taco_encode", encode_then_second_utterance)
+    out, t_out, seen = run(taco, wg, den, ppg, em, dm, zs, True, monkeypatch)
+    assert seen["streamed"] and "launch" in nested
+    assert nested["words_untouched"]                     # the nested decode published nothing into the streamed call's words
+    assert nested["launch"].mode == "split" and not nested["launch"].streamed
+    assert t_out == t_ref and np.array_equal(out, ref)
+    assert all(np.array_equal(a, b) for a, b in zip(nested["outputs"], serial))
 
 
 def test_stream_footprint_follows_the_utterance_not_the_step_limit(vocoder, monkeypatch):
