@@ -2174,6 +2174,11 @@ void wg_launch_noise(float* z, size_t n, uint64_t seed, hipStream_t s) {
 using namespace facppg;
 
 
+// the fp32 entry points refuse a handle made by facppg_wg_create_f16 (facppg_wg16.hip)
+#define WG_REQUIRE_FP32(h, fn)                                                                                    \
+  FACPPG_REQUIRE(!(h) || !(h)->w16, FACPPG_EINVAL,                                                               \
+                 fn ": the handle holds fp16 images (facppg_wg_create_f16); use facppg_wg_infer_f16, or make it with facppg_wg_create")
+
 extern "C" int facppg_version(void) { return FACPPG_VERSION; }
 extern "C" const char* facppg_last_error(void) { return g_err; }
 
@@ -2452,6 +2457,7 @@ extern "C" void facppg_wg_destroy(facppg_wg* h) {
   if (!h) return;
   for (hipEvent_t e : h->ev) hipEventDestroy(e);
   wgp_destroy(h);
+  if (h->w16) wg16_destroy(h);
   hipFree(h->arena);
   delete h;
 }
@@ -2512,6 +2518,7 @@ PmLayout pm_layout(const facppg_wg_config& c, int B, int T) {
 
 extern "C" size_t facppg_wg_workspace_bytes(const facppg_wg* h, int B, int T) {
   if (!h || B <= 0 || T <= 0) return 0;
+  if (h->w16) return wg16_workspace_bytes(h, B, T);
   const size_t a = ws_layout(h->cfg, B, T).total, b = pm_layout(h->cfg, B, T).total, c = wgp_workspace_bytes(h, B, T);
   return std::max(a, std::max(b, c));
 }
@@ -2530,6 +2537,7 @@ extern "C" int facppg_debug_wn8_prof(unsigned long long* out12, int reset) {
 // enable: 0 off, 1 the launches of the most recent infer, n > 1 accumulate over the next n infers (the events of n
 // infers are created HERE, so that none is created inside a timed region)
 extern "C" int facppg_wg_set_profiling(facppg_wg* h, int enable) {
+  WG_REQUIRE_FP32(h, "facppg_wg_set_profiling");
   FACPPG_REQUIRE(h && enable >= 0, FACPPG_EINVAL, "handle is NULL or enable < 0");
   h->profiling = enable;
   h->ev_used = 0;
@@ -2546,6 +2554,7 @@ extern "C" int facppg_wg_set_profiling(facppg_wg* h, int enable) {
 }
 
 extern "C" int facppg_wg_last_layer_ms(facppg_wg* h, float* avg_ms, int* n_launches) {
+  WG_REQUIRE_FP32(h, "facppg_wg_last_layer_ms");
   FACPPG_REQUIRE(h && avg_ms && n_launches, FACPPG_EINVAL, "NULL argument");
   double tot = 0;
   for (int i = 0; i + 1 < h->ev_used; i += 2) {
@@ -2796,6 +2805,7 @@ static int wg_infer_pm(facppg_wg* h, const float* mel_dev, const int32_t* T_vali
 extern "C" int facppg_wg_infer(facppg_wg* h, const float* mel_dev, const int32_t* T_valid_dev, const float* z_dev,
                                uint64_t seed, float sigma, int B, int T, float* audio_dev, void* ws_, size_t ws_bytes,
                                void* stream_) {
+  WG_REQUIRE_FP32(h, "facppg_wg_infer");
   FACPPG_REQUIRE(h && mel_dev && audio_dev && ws_, FACPPG_EINVAL, "NULL argument");
   FACPPG_REQUIRE(B > 0 && T > 0, FACPPG_EINVAL, "B and T must be positive (got %d, %d)", B, T);
   const facppg_wg_config& c = h->cfg;
@@ -2922,6 +2932,7 @@ extern "C" int facppg_wg_infer(facppg_wg* h, const float* mel_dev, const int32_t
 }
 
 extern "C" int facppg_wg_seed_layout(const facppg_wg* h, int T, int* Tqp, int* margin, size_t* seed_bytes) {
+  WG_REQUIRE_FP32(h, "facppg_wg_seed_layout");
   FACPPG_REQUIRE(h && T > 0 && Tqp && margin && seed_bytes, FACPPG_EINVAL, "NULL argument or T <= 0");
   const PmLayout w = pm_layout(h->cfg, 1, T);
   *Tqp = w.Tqp; *margin = HQ;
@@ -2932,6 +2943,7 @@ extern "C" int facppg_wg_seed_layout(const facppg_wg* h, int T, int* Tqp, int* m
 extern "C" int facppg_wg_cond_seed(facppg_wg* h, const float* melp_dev, int T, int frame0, int nframes, int block_tiles,
                                    int layers_per_workgroup, int flow0, int nflows, float* seeds_dev, size_t seed_bytes,
                                    const int32_t* skip_dev, int max_workgroups, int32_t* counter_dev, void* stream_) {
+  WG_REQUIRE_FP32(h, "facppg_wg_cond_seed");
   FACPPG_REQUIRE(h && melp_dev && seeds_dev, FACPPG_EINVAL, "NULL argument");
   const facppg_wg_config& c = h->cfg;
   const PmLayout w = pm_layout(c, 1, T);
@@ -2995,6 +3007,7 @@ extern "C" int facppg_wg_cond_seed(facppg_wg* h, const float* melp_dev, int T, i
 }
 
 extern "C" int facppg_wg_mel_pad(const facppg_wg* h, const float* mel_dev, int T, int ld, float* melp_dev, void* stream_) {
+  WG_REQUIRE_FP32(h, "facppg_wg_mel_pad");
   FACPPG_REQUIRE(h && mel_dev && melp_dev && T > 0 && ld >= T, FACPPG_EINVAL, "NULL argument or bad T / ld");
   const PmLayout w = pm_layout(h->cfg, 1, T);
   FACPPG_HIP_CHECK(hipMemsetAsync(melp_dev, 0, (size_t)NMEL * w.Tqp * 4, (hipStream_t)stream_));
@@ -3006,6 +3019,7 @@ extern "C" int facppg_wg_mel_pad(const facppg_wg* h, const float* mel_dev, int T
 extern "C" int facppg_wg_infer_seeded(facppg_wg* h, const float* melp_dev, int T_layout, int T, const float* seeds_dev, int seeded_frames,
                                       const float* z_dev, uint64_t seed, float sigma, float* audio_dev, void* ws_, size_t ws_bytes,
                                       void* const* flow_events, void* stream_) {
+  WG_REQUIRE_FP32(h, "facppg_wg_infer_seeded");
   FACPPG_REQUIRE(h && melp_dev && seeds_dev && audio_dev && ws_, FACPPG_EINVAL, "NULL argument");
   FACPPG_REQUIRE(T > 0 && T_layout >= T, FACPPG_EINVAL, "need 0 < T <= T_layout (got %d, %d)", T, T_layout);
   const size_t need = facppg_wg_workspace_bytes(h, 1, T_layout);
@@ -3034,6 +3048,7 @@ static void launch_fwd_end(bool early_next, bool lastflow, dim3 grid, hipStream_
 }
 
 extern "C" size_t facppg_wg_log_s_count(const facppg_wg* h, int B, int N) {
+  if (h && h->w16) return 0;   // (an fp16 handle has no training direction)
   if (!h || B <= 0 || N <= 0) return 0;
   size_t n = 0;
   for (int k = 0; k < h->cfg.n_flows; ++k) n += (size_t)B * h->n_half[k] * (N / 8);
@@ -3042,6 +3057,7 @@ extern "C" size_t facppg_wg_log_s_count(const facppg_wg* h, int B, int N) {
 
 extern "C" int facppg_wg_forward(facppg_wg* h, const float* mel_dev, const float* audio_dev, int B, int F, int N, float* z_dev,
                                  float* log_s_dev, void* ws_, size_t ws_bytes, void* stream_) {
+  WG_REQUIRE_FP32(h, "facppg_wg_forward");
   FACPPG_REQUIRE(h && mel_dev && audio_dev && z_dev && log_s_dev && ws_, FACPPG_EINVAL, "NULL argument");
   const facppg_wg_config& c = h->cfg;
   FACPPG_REQUIRE(B > 0 && F > 0 && N > 0 && N % 8 == 0, FACPPG_EINVAL, "need B, F > 0 and N a positive multiple of n_group");

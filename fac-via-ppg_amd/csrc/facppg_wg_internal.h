@@ -35,6 +35,7 @@ __device__ __forceinline__ float gate_tanh_sigmoid(float a, float b) {
 }
 
 struct WgpState;   // facppg_wgp.hip: images, tables and launch state of the persistent small-launch path (null: not built)
+struct Wg16State;  // facppg_wg16.hip: the fp16 images of a handle made by facppg_wg_create_f16 (null: an fp32 handle)
 
 }  // namespace facppg
 
@@ -70,6 +71,7 @@ struct facppg_wg {
   int n_cu;
   facppg::WgpState* wgp;   // persistent small-launch path (facppg_wgp.hip), or null
   int last_tile, last_waves, last_tiles;   // shape of the WN layer launches of the most recent infer (facppg_wg_last_launch_shape)
+  facppg::Wg16State* w16;  // fp16 handle (facppg_wg_create_f16): its images live in `arena`, no fp32 image is kept
 };
 
 namespace facppg {
@@ -95,5 +97,8 @@ int wgp_infer(facppg_wg* h, const float* mel_dev, const float* z_dev, uint64_t s
               char* ws, hipStream_t s);
 // facppg_wg.hip: z[0..n) ~ N(0, 1), Philox4x32-10 keyed by `seed` (the noise of facppg_wg_infer when none is injected)
 void wg_launch_noise(float* z, size_t n, uint64_t seed, hipStream_t s);
+// facppg_wg16.hip: the fp16 handle's workspace and host-side state
+size_t wg16_workspace_bytes(const facppg_wg* h, int B, int T);
+void wg16_destroy(facppg_wg* h);
 
 }  // namespace facppg

@@ -97,6 +97,8 @@ def _declare(lib):
         "facppg_wg_destroy": (None, [vp]),
         "facppg_wg_workspace_bytes": (sz, [vp, c.c_int, c.c_int]),
         "facppg_wg_infer": (c.c_int, [vp, vp, vp, vp, u64, f32, c.c_int, c.c_int, vp, vp, sz, vp]),
+        "facppg_wg_create_f16": (c.c_int, [c.POINTER(WgConfig), vp, sz, c.c_int, vp, c.POINTER(vp)]),
+        "facppg_wg_infer_f16": (c.c_int, [vp, vp, vp, vp, u64, f32, c.c_int, c.c_int, vp, vp, sz, vp]),
         "facppg_wg_log_s_count": (sz, [vp, c.c_int, c.c_int]),
         "facppg_wg_forward": (c.c_int, [vp, vp, vp, c.c_int, c.c_int, c.c_int, vp, vp, vp, sz, vp]),
         "facppg_wn_train_workspace_bytes": (sz, [c.c_int, c.c_int, c.c_int]),

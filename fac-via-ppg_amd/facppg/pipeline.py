@@ -90,6 +90,8 @@ class ConditioningStream(object):
             return False
         if os.environ.get("FACPPG_WG_EDGE_FOLD", "1") == "0" or getattr(tacotron, "decoder_workgroups", 0):
             return False
+        if getattr(getattr(waveglow, "upsample", None), "weight", torch.empty(0)).dtype != torch.float32:
+            return False    # the seeds are fp32 accumulators: a half vocoder runs unstreamed
         return waveglow.WN[0].n_layers == 8 and waveglow.n_group == 8
 
     SLACK = 64   # frames past the PPG's length the buffers are laid out for (an utterance that runs on past them is finished unstreamed)
@@ -410,12 +412,17 @@ def _vocode(mel_post, tout, waveglow, denoiser, sigma, strength, seed, z, uttera
     hop = waveglow.upsample.stride[0]
     multi = len(tout) > 1
     wg_seeds = None if utterance_seeds is None else [int(v) + 1 for v in utterance_seeds]
+    half = waveglow.upsample.weight.dtype != torch.float32   # a .half() vocoder: half mel in, its half audio widened to fp32
+    if half:
+        mel_post = mel_post.to(waveglow.upsample.weight.dtype)
     if consumer is not None and consumer.active:
         if wg_seeds is not None:
             z = waveglow.draw_noise(wg_seeds, tout[0], mel_post.device)
         audio = consumer.vocode(sigma, z=z, seed=seed)
     else:
         audio = waveglow.infer(mel_post, sigma=sigma, z=z, lengths=tout if multi else None, seed=seed, utterance_seeds=wg_seeds)
+        if half:
+            audio = audio.float()
     if timer is not None:
         timer.mark("waveglow")
     if denoiser is not None:

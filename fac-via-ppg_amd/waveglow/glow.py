@@ -949,16 +949,29 @@ class WaveGlow(torch.nn.Module):
         self._release()
         L = _lib.load()
         cfg = self._config()
+        create = L.facppg_wg_create_f16 if self._precision() == torch.float16 else L.facppg_wg_create
         blob = self._flat_weights().to(device).contiguous()
         if blob.numel() != L.facppg_wg_weight_count(cfg):
             raise _lib.FacppgError("weight blob has %d values, library expects %d (unsupported config: %s)" % (
                 blob.numel(), L.facppg_wg_weight_count(cfg), L.facppg_last_error().decode()))
         out = _lib.ctypes.c_void_p()
         with torch.cuda.device(device):
-            _lib.check(L.facppg_wg_create(cfg, _lib.ptr(blob), blob.numel(), device.index,
-                                          _lib.current_stream(device), _lib.ctypes.byref(out)))
+            _lib.check(create(cfg, _lib.ptr(blob), blob.numel(), device.index,
+                              _lib.current_stream(device), _lib.ctypes.byref(out)))
         self.__dict__["_facppg_handle"] = (out, device, _lib.WeightIdentity(self))
         return out
+
+    def _precision(self):
+        """The inference precision of the module: the dtype of its WN and upsample parameters -- all fp32 (facppg_wg_create)
+        or all fp16 (facppg_wg_create_f16, the reference's .half() branch).  convinv may be fp32 (the reference's recipe:
+        inference.py keeps it in float) or fp16; W_inverse is formed in fp32 either way.  Anything else is refused."""
+        dts = {p.dtype for p in self.upsample.parameters()} | {p.dtype for wn in self.WN for p in wn.parameters()}
+        inv = {p.dtype for p in self.convinv.parameters()}
+        if len(dts) == 1 and dts <= {torch.float32, torch.float16} and inv <= {torch.float32, torch.float16}:
+            return next(iter(dts))
+        raise _lib.FacppgError("WaveGlow: inference runs with the WN and upsample parameters all fp32 or all fp16 (convinv fp32 "
+                               "or fp16); got WN/upsample %s, convinv %s" % (
+                                   sorted(str(d) for d in dts), sorted(str(d) for d in inv)))
 
     def _apply(self, fn, *a, **k):                       # .cuda()/.to()/.float(): weights moved
         self._release()
@@ -1290,14 +1303,15 @@ class WaveGlow(torch.nn.Module):
         return self._handle(dev)
 
     def infer(self, spect, sigma=1.0, z=None, lengths=None, seed=None, utterance_seeds=None, groups=None):
-        """mel [B, n_mel, T] (GPU, fp32) -> audio [B, T*hop]   (glow.py:252-293).
+        """mel [B, n_mel, T] (GPU, fp32) -> audio [B, T*hop]   (glow.py:252-293); a .half() module takes a half mel and returns
+        half audio (the reference's HalfTensor branch, see _infer_half).
         groups: None = decide from the launch shape (ragged batches whose layer launches would idle through >= 3 % of their
         time in the last round run as two concurrent half-batches, see _infer_two_groups), 1 = one launch sequence, 2 = force
         the two half-batches (needs host-side lengths).  With `seed` alone the noise of a uniform batch is a function of (seed, batch
         layout); a ragged batch with host-side lengths draws per-utterance streams derived from (seed, b), identical in both modes."""
         _lib.require_cuda(spect, "WaveGlow.infer: spect")
-        if spect.dtype != torch.float32:
-            raise _lib.FacppgError("WaveGlow.infer: fp32 only (the reference's fp16 branch is not built)")
+        if spect.dtype != torch.float32 or self.upsample.weight.dtype != torch.float32:
+            return self._infer_half(spect, sigma, z, lengths, seed, utterance_seeds, groups)
         dev = spect.device
         h = self._checked_handle(dev)   # (ONE validity check of the packed weights per call -- it walks ~1000 tensors -- or none:
         spect = spect.contiguous()      #  prepare(); consumed HERE so that no path -- two half-batches included -- leaves the token behind)
@@ -1343,6 +1357,60 @@ class WaveGlow(torch.nn.Module):
         audio = torch.zeros(B, T * hop, dtype=torch.float32, device=dev) if lt is not None else \
             torch.empty(B, T * hop, dtype=torch.float32, device=dev)
         self._infer_launch(spect, lt, zt, seed, sigma, audio, self._infer_workspace(B, T, dev, 0, h), h)
+        return audio
+
+    def _infer_half(self, spect, sigma, z, lengths, seed, utterance_seeds, groups):
+        """infer() of a .half() module (glow.py:261-290, the HalfTensor branch): half mel [B, n_mel, T] -> half audio
+        [B, T*hop] on the fp16 MFMA kernels (facppg_wg_infer_f16).  Same z / seed / lengths / utterance_seeds semantics as
+        the fp32 path; one launch sequence (groups 1)."""
+        if self._precision() != torch.float16:
+            raise _lib.FacppgError("WaveGlow.infer: fp32 only for this module (its WN / upsample parameters are fp32; "
+                                   "got a %s mel) -- .half() the module for half inference" % spect.dtype)
+        if spect.dtype != torch.float16:
+            raise _lib.FacppgError("WaveGlow.infer: the module is fp16 (.half()), the mel must be fp16 too (got %s)" % spect.dtype)
+        if groups not in (None, 1):
+            raise _lib.FacppgError("WaveGlow.infer: groups=%r: the fp16 path runs one launch sequence (groups=1)" % (groups,))
+        dev = spect.device
+        h = self._checked_handle(dev)
+        spect = spect.contiguous()
+        B, _, T = spect.shape
+        hop = self.upsample.stride[0]
+        n = B * self.n_group * (T * hop // self.n_group)
+        host_lengths = lengths is not None and not torch.is_tensor(lengths)
+        if host_lengths and (len(lengths) != B or max(int(v) for v in lengths) > T or min(int(v) for v in lengths) < 1):
+            raise _lib.FacppgError("lengths must be B values in [1, T]")
+        zt = None
+        if utterance_seeds is not None:
+            if z is not None or len(utterance_seeds) != B:
+                raise _lib.FacppgError("utterance_seeds: B integers, and not together with z")
+        elif z is not None:
+            if isinstance(z, (list, tuple)):
+                z = torch.cat([t.to(dev).reshape(-1) for t in z])
+            zt = z.to(device=dev, dtype=torch.float16).contiguous()   # injected z is rounded to half, as the reference's draw is
+            if zt.numel() != n:
+                raise _lib.FacppgError("z has %d values, expected B*n_group*L = %d" % (zt.numel(), n))
+        if seed is None:
+            seed = int(torch.empty((), dtype=torch.int64).random_().item())
+        if utterance_seeds is None and zt is None and host_lengths and B >= 2:
+            # the fp32 path's per-utterance streams for `seed` on a ragged batch, so both precisions draw the same noise
+            utterance_seeds = [(int(seed) * 0x9E3779B97F4A7C15 + (b + 1) * 0xBF58476D1CE4E5B9) & 0x7FFFFFFFFFFFFFFF for b in range(B)]
+        if utterance_seeds is not None:
+            zt = self.draw_noise(utterance_seeds, T, dev).half()
+        lt = None
+        if lengths is not None:
+            if host_lengths:
+                lt = _lib.upload([int(v) for v in lengths], torch.int32, dev)
+            else:
+                lt = lengths.to(device=dev, dtype=torch.int32).contiguous()
+                if lt.numel() != B or int(lt.max()) > T or int(lt.min()) < 1:
+                    raise _lib.FacppgError("lengths must be B values in [1, T]")
+        audio = torch.zeros(B, T * hop, dtype=torch.float16, device=dev) if lt is not None else \
+            torch.empty(B, T * hop, dtype=torch.float16, device=dev)
+        ws = self._infer_workspace(B, T, dev, 0, h)
+        with torch.cuda.device(dev):
+            _lib.check(_lib.load().facppg_wg_infer_f16(h, _lib.ptr(spect), _lib.ptr(lt), _lib.ptr(zt), seed & 0xFFFFFFFFFFFFFFFF,
+                                                       float(sigma), B, T, _lib.ptr(audio), _lib.ptr(ws), ws.numel(),
+                                                       _lib.current_stream(dev)))
         return audio
 
     @staticmethod

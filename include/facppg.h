@@ -112,6 +112,23 @@ int facppg_wg_infer(facppg_wg* h, const float* mel_dev, const int32_t* T_valid_d
 int facppg_wg_draw_noise(const facppg_wg* h, const uint64_t* seeds_dev, int B, int T, float* z_dev,
                          void* stream);
 
+/* Half-precision WaveGlow.infer: the reference's HalfTensor branch (glow.py:261-290), reached through
+ * inference.py:38-48 --is_fp16 (waveglow.half(), convinv kept in fp32, mel.half()).
+ * facppg_wg_create_f16 takes the SAME fp32 blob as facppg_wg_create (the half module's values widened), folds it
+ * in fp32 and keeps only fp16 weight images (glow.py:179-206 / common/utils.py:177-181 as for facppg_wg_create).
+ * facppg_wg_infer_f16 has the semantics of facppg_wg_infer (T_valid, flat injected-z layout, seed) with
+ *   mel_dev [B][n_mel][T], z_dev (NULL or the flat layout) and audio_dev [B][T*hop] in IEEE fp16;
+ * noise drawn from `seed` is facppg_wg_infer's Philox draw rounded to fp16.  Accumulation, the gate, the skip sum
+ * and the flow-edge arithmetic (affine inverse, W_inverse, early z) run in fp32.
+ * facppg_wg_workspace_bytes, facppg_wg_last_launch_shape, facppg_wg_draw_noise (fp32 values, any handle) and
+ * facppg_wg_destroy accept either kind of handle; the other fp32 entry points return FACPPG_EINVAL for an fp16
+ * handle and facppg_wg_infer_f16 does for an fp32 one (facppg_last_error names the mismatch). */
+int facppg_wg_create_f16(const facppg_wg_config* cfg, const float* weights_dev, size_t n_floats,
+                         int device, void* stream, facppg_wg** out);
+int facppg_wg_infer_f16(facppg_wg* h, const uint16_t* mel_dev, const int32_t* T_valid_dev,
+                        const uint16_t* z_dev, uint64_t seed, float sigma, int B, int T,
+                        uint16_t* audio_dev, void* workspace_dev, size_t workspace_bytes, void* stream);
+
 /* Replaces: WaveGlow.forward((spect, audio)) (glow.py:208-250), the training direction
  * audio -> z: upsample + crop to the audio length, 8-sample regroup, per flow the forward 1x1
  * mixing conv, WN, and a1 = exp(log_s)*a1 + b, with early outputs split off every n_early_every
