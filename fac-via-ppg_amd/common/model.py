@@ -4,8 +4,9 @@ The module tree (names, parameter shapes, state-dict keys: SURVEY.md Appendix B)
 reference's so ``load_state_dict(torch.load(ckpt)['state_dict'])`` works unchanged
 (generate_synthesis.py:82).  The modules hold parameters only; ``Tacotron2.inference`` packs
 them once into a ``facppg_taco`` handle and runs the encoder GEMMs, the BiLSTM kernel, the
-persistent decoder kernel and the postnet GEMMs of csrc/facppg_taco.hip through the C ABI.
-There is no CPU path.
+persistent decoder kernel and the postnet GEMMs of csrc/facppg_taco.hip through the C ABI;
+``Tacotron2.forward`` is the teacher-forced pass (eval mode) on the padded-batch encoder, the
+teacher-forced recurrent kernel and the same postnet.  There is no CPU path, and no backward pass.
 
 Extensions over the reference signature (defaults reproduce it):
   ``inference(inputs, lengths=None, dropout_masks=None, seed=None)``
@@ -25,6 +26,7 @@ import torch
 from torch import nn
 
 from common.layers import ConvNorm, LinearNorm
+from common.utils import get_mask_from_lengths, to_gpu
 from facppg import lib as _lib
 
 # One decoder launch as facppg_taco_decode reports it: mode 'single', 'coop' or 'split', its workgroups, and whether it published
@@ -249,11 +251,109 @@ class Tacotron2(nn.Module):
             raise _lib.FacppgError("fp16_run is not built (the reference's README.md:53 says FP16 does not work either)")
         return inputs
 
+    def parse_batch(self, batch):
+        """A collated batch (common.data_utils.ppg_acoustics_collate: ppg, input lengths, acoustic targets, gate targets, output
+        lengths) -> (forward's inputs, the loss's targets), on the GPU: the features as float, the lengths as long
+        (the reference's model.py:548-560).  forward's inputs carry the longest PPG length as a host integer in slot 3."""
+        if len(batch) != 5:
+            raise ValueError("parse_batch: a batch is (ppg, input_lengths, acoustic, gate, output_lengths), got %d items" % len(batch))
+        ppg, in_lens, acoustic, gate, out_lens = (to_gpu(t).float() if k in (0, 2, 3) else to_gpu(t).long()
+                                                  for k, t in enumerate(batch))
+        return (ppg, in_lens, acoustic, int(in_lens.max()), out_lens), (acoustic, gate)
+
     def parse_output(self, outputs, output_lengths=None):
+        """model.py:566-578: beyond each utterance's output length mel and mel_post become 0 and the gate energies 1e3 (when
+        ``mask_padding``); the alignments stay as they are.  ``inference`` calls it without lengths."""
+        if self.mask_padding and output_lengths is not None:
+            pad = ~get_mask_from_lengths(output_lengths)                 # [B, T_out], True = padding
+            outputs[0].masked_fill_(pad.unsqueeze(1), 0.0)
+            outputs[1].masked_fill_(pad.unsqueeze(1), 0.0)
+            outputs[2].masked_fill_(pad, 1e3)
         return outputs
 
-    def forward(self, inputs):
-        raise NotImplementedError("teacher-forced training of the PPG->mel model is out of scope (SURVEY.md section 2)")
+    def forward(self, inputs, dropout_masks=None, seed=None, utterance_seeds=None):
+        """The teacher-forced pass (model.py:580-595) in eval mode, on the HIP kernels of csrc/facppg_taco.hip.
+        inputs = (ppg_padded [B, n_symbols, Tin], input_lengths [B] descending, acoustic_padded [B, n_feat, T_out], max_len,
+        output_lengths [B]) as ``parse_batch`` returns them -> [mel, mel_post, gate [B, T_out], alignments [B, T_out, Tin]].
+        It reproduces the reference's PADDED-BATCH computation (facppg_taco_encode_padded, facppg_taco_postnet without lengths):
+        the encoder's conv bank and the postnet run over the zero-padded batch, so an utterance's result depends on how far
+        its batch is padded -- what the checkpoints were trained with and what makes a validation loss comparable.
+        dropout_masks  (enc [2, B, Tin, E], dec [2, T_out + 1, B, prenet_dim]) keep-masks in the reference's draw order (it draws
+                       T_out + 1 decoder frames and uses the first T_out); None -> drawn on the device from ``seed``
+        utterance_seeds  B integers, as in ``inference``: utterance b's dropout draws depend on utterance_seeds[b] alone
+        B = 1 works (the reference's own forward fails there on a squeeze(), model.py:481).  The backward pass is not built:
+        in training mode the call raises; the three extra training-mode dropouts of the reference do not exist here."""
+        if self.training:
+            raise _lib.FacppgError("Tacotron2.forward: the backward pass is not built -- the teacher-forced pass runs in eval mode "
+                                   "only (call model.eval(); training the PPG->mel model is out of scope)")
+        ppg, input_lengths, targets, _max_len, output_lengths = self.parse_input(inputs)
+        _lib.require_cuda(ppg, "Tacotron2.forward: inputs")
+        _lib.require_cuda(targets, "Tacotron2.forward: targets")
+        L = _lib.load()
+        dev = ppg.device
+        hp = self._hp
+        x = ppg.float().contiguous()
+        tgt = targets.to(dev).float().contiguous()
+        B, S, Tin = x.shape
+        E, P, NF, AD = hp["encoder_embedding_dim"], hp["prenet_dim"], hp["n_acoustic_feat_dims"], hp["attention_dim"]
+        if S != hp["n_symbols"]:
+            raise _lib.FacppgError("inputs have %d symbols, model was built for %d" % (S, hp["n_symbols"]))
+        if tgt.dim() != 3 or tgt.shape[0] != B or tgt.shape[1] != NF or tgt.shape[2] < 1:
+            raise _lib.FacppgError("targets must be [B, %d, T_out], got %s" % (NF, tuple(tgt.shape)))
+        T = tgt.shape[2]
+        lens_host = torch.as_tensor(input_lengths).detach().to("cpu", torch.int32).contiguous()
+        out_lens = torch.as_tensor(output_lengths).to(dev).long()
+        if lens_host.numel() != B or out_lens.numel() != B:
+            raise _lib.FacppgError("input_lengths and output_lengths must hold B values")
+        if int(lens_host.max()) != Tin:
+            raise _lib.FacppgError("the longest utterance has %d frames, the padded batch %d (model.py:232-233 pads to the longest)"
+                                   % (int(lens_host.max()), Tin))
+        if int(out_lens.max()) != T:
+            raise _lib.FacppgError("the longest target has %d frames, the padded targets %d" % (int(out_lens.max()), T))
+        lt = lens_host.to(dev)
+        h = self._handle(dev)
+        if seed is None:
+            seed = int(torch.empty((), dtype=torch.int64).random_().item())
+        seed &= 0xFFFFFFFFFFFFFFFF
+        enc_m = dec_m = None
+        st = _lib.current_stream(dev)
+        if dropout_masks is not None:
+            if utterance_seeds is not None:
+                raise _lib.FacppgError("utterance_seeds: B integers, and not together with dropout_masks")
+            em, dm = dropout_masks
+            enc_m = torch.as_tensor(em).to(dev).to(torch.uint8).reshape(2, B, Tin, E).permute(0, 1, 3, 2).contiguous()
+            dm = torch.as_tensor(dm).to(dev).to(torch.uint8)
+            if tuple(dm.shape) != (2, T + 1, B, P):
+                raise _lib.FacppgError("decoder masks must be [2, T_out + 1, B, prenet_dim]")
+            dec_m = dm[:, :T].permute(0, 2, 3, 1).contiguous()               # [2, B, P, T_out]
+        elif utterance_seeds is not None:
+            if len(utterance_seeds) != B:
+                raise _lib.FacppgError("utterance_seeds: B integers, and not together with dropout_masks")
+            enc_m, _ = self.draw_dropout_masks(utterance_seeds, Tin, dev, 1)
+            sd = torch.tensor([int(v) & 0x7FFFFFFFFFFFFFFF for v in utterance_seeds], dtype=torch.int64, device=dev)
+            dec_m = torch.empty(2, B, P, T, dtype=torch.uint8, device=dev)
+            with torch.cuda.device(dev):
+                _lib.check(L.facppg_taco_draw_dropout_forced(h, _lib.ptr(sd), B, T, _lib.ptr(dec_m), st))
+        ws = torch.empty(max(L.facppg_taco_workspace_bytes(h, B, Tin), L.facppg_taco_decode_forced_workspace_bytes(h, B, T),
+                             L.facppg_taco_postnet_workspace_bytes(h, B, T)), dtype=torch.uint8, device=dev)
+        memory = torch.empty(B, Tin, E, dtype=torch.float32, device=dev)
+        pm = torch.empty(B, AD, Tin, dtype=torch.float32, device=dev)
+        mel = torch.empty(B, NF, T, dtype=torch.float32, device=dev)
+        mel_post = torch.empty_like(mel)
+        gate = torch.empty(B, T, dtype=torch.float32, device=dev)
+        align = torch.empty(B, T, Tin, dtype=torch.float32, device=dev)
+        opts = _lib.TacoDecodeOpts(max_workgroups=int(self.decoder_workgroups))
+        with torch.cuda.device(dev):
+            _lib.check(L.facppg_taco_encode_padded(h, _lib.ptr(x), _lib.ptr(lt), _lib.ctypes.c_void_p(lens_host.data_ptr()),
+                                                   _lib.ptr(enc_m), seed, B, Tin, _lib.ptr(memory), _lib.ptr(pm), _lib.ptr(ws),
+                                                   ws.numel(), st))
+            _lib.check(L.facppg_taco_decode_forced(h, _lib.ptr(memory), _lib.ptr(pm), _lib.ptr(lt), _lib.ptr(tgt), _lib.ptr(dec_m),
+                                                   seed, B, Tin, T, _lib.ptr(mel), _lib.ptr(gate), _lib.ptr(align), _lib.ptr(ws),
+                                                   ws.numel(), _lib.ctypes.byref(opts), st))
+            _lib.check(L.facppg_taco_postnet(h, _lib.ptr(mel), None, B, T, T, _lib.ptr(mel_post), _lib.ptr(ws), ws.numel(), st))
+        # (for single-threaded callers: tests, tools)
+        self.last_memory, self._last_launch = memory, DecoderLaunch("coop", opts.workgroups, False)
+        return self.parse_output([mel, mel_post, gate, align], out_lens)
 
     def draw_dropout_masks(self, utterance_seeds, Tin, device=None, steps=None):
         """Per-utterance dropout keep-masks (facppg_taco_draw_dropout) in the DEVICE layouts the kernels read:

@@ -1,4 +1,5 @@
-// Tacotron2-style PPG -> mel inference on gfx950: encoder, autoregressive decoder, postnet.
+// Tacotron2-style PPG -> mel inference on gfx950: encoder, autoregressive decoder, postnet; and the teacher-forced
+// forward pass (Encoder.forward :215-235, Decoder.forward :444-487, Tacotron2.forward :580-595) in eval mode.
 //
 // Replaces src/common/model.py of the reference: Prenet (:124-135), Encoder.inference (:237-249),
 // LocationLayer/Attention (:44-121), Decoder.inference/decode (:489-535, :387-442), Postnet
@@ -14,6 +15,7 @@
 // reference's mask keeps (<= 2W+1 of Tin).  Each has a throughput shape and latency shapes:
 //   k_bilstm / k_bilstm_coop                       encoder BiLSTM recurrence (input projections were one GEMM)
 //   k_decoder / k_decoder_coop / k_decoder_split   the autoregressive decoder loop
+//   k_decoder_forced                               the teacher-forced decoder loop (Tacotron2.forward: targets known, no stop rule)
 // The latency shapes spread one utterance over many co-resident workgroups (cooperative launch) that
 // exchange hidden state through 8-byte {value, tag} words; _split and _bilstm_coop keep their weight
 // slices in registers for the whole sequence.
@@ -54,6 +56,10 @@ struct facppg_taco {
   // postnet
   float4* post[8];
   float *post_b[8], *post_scale[8], *post_shift[8];
+  // teacher-forced decoder (facppg_taco_decode_forced): the layers that leave the frame loop, as GEMM operands
+  float4 *tf_dp0, *tf_dp1;         // decoder prenet layers [P][NF], [P][P]
+  float4* tf_attx;                 // attention LSTM W_ih[:, :P]  [4A][P]
+  float4* tf_proj;                 // linear_projection rows 0..NF-1 + gate_layer row NF  [NF+1][D+E]
 };
 
 namespace {
@@ -1468,6 +1474,180 @@ __global__ __launch_bounds__(NTC) void k_decoder_split(DecArgs p) {
 }
 
 // ------------------------------------------------------------------------------------------
+// k_decoder_forced: the teacher-forced decoder loop (Decoder.forward, model.py:444-487; one step = Decoder.decode,
+// model.py:387-442, in eval mode).  With the targets known, the prenet of every frame and the prenet part of the
+// attention LSTM's input product were GEMMs in front of the launch (xa[b][t][4A] = W_ih[:, :P] prenet(frame t) + b_ih + b_hh)
+// and the projection + gate of every frame is a GEMM behind it; the loop keeps
+//     attention LSTMCell -> location-sensitive attention -> decoder LSTMCell
+// and stores [decoder_hidden | context] per frame (hc[b][D + E][T], the GEMM's operand) and the alignments.
+// The attention LSTM of frame t+1 needs ctx(t) and ah(t) only -- not dh(t): the decoder LSTM is OFF the dependent chain.
+// So an utterance has two kinds of workgroups in the one launch:
+//   chain (NA of them, U units of the attention LSTM each, slices as k_decoder_coop's): attention-LSTM slice -> AH words ->
+//     [location features and the query-free part of the energies, which need frame t-1's weights only, while the
+//     words are in flight] -> gather AH -> attention, redundantly in every chain workgroup (the first publishes CTX words
+//     and writes the alignments).  One exchange per frame.
+//   decoder-LSTM (ND of them, UD units each): gather AH(t), CTX(t), DH(t-1) -> decoder-LSTM slice -> DH words; they also
+//     write hc.  They trail the chain by about a frame and never hold it up: the chain waits for nothing of theirs.
+// Every exchange word is {value, frame + 1}, indexed BY FRAME ([T][A + E + D] per utterance, zeroed by the caller): a word is
+// written once, so no reader can be overtaken, however far the decoder-LSTM workgroups fall behind.
+// Exactly T steps for every utterance: no gate, no stop (shorter utterances go on decoding their zero targets).
+// ------------------------------------------------------------------------------------------
+template <int NT>
+__device__ __forceinline__ void forced_att_slice(const float* __restrict__ Wslice, const float* __restrict__ xrow, int K, int U,
+                                                 int A, int unit0, const float* in, float* part, float* cstate,
+                                                 unsigned long long* xchg_out, unsigned tag, int tid) {
+  const int SC = 4 * U, KS = pick_ks<NT>(SC, K);
+  float xv[2];   // this frame's hoisted input product of the thread's gate rows (4U <= 640 rows): requested ahead of the matvec
+#pragma unroll
+  for (int j = 0; j < 2; ++j) {
+    const int c = tid + j * NT, u = unit0 + c % U;
+    xv[j] = (c < SC && u < A) ? xrow[(c / U) * A + u] : 0.0f;
+  }
+  matvec_part<(NT <= 512 ? 16 : 4)>(Wslice, K, SC, KS, in, part, tid);
+  __syncthreads();
+#pragma unroll
+  for (int j = 0; j < 2; ++j) {
+    const int c = tid + j * NT;
+    if (c < SC) part[4 * NT + c] = part_sum(part, SC, KS, c) + xv[j];
+  }
+  __syncthreads();
+  if (tid < U && unit0 + tid < A) {
+    const float* gs = part + 4 * NT;
+    const float h = lstm_point(gs[tid], gs[U + tid], gs[2 * U + tid], gs[3 * U + tid], &cstate[tid]);
+    __hip_atomic_store(xchg_out + unit0 + tid, ((unsigned long long)tag << 32) | __float_as_uint(h), __ATOMIC_RELAXED,
+                       __HIP_MEMORY_SCOPE_AGENT);
+  }
+}
+
+// REGW (up to 2 utterances): the chain workgroups are split_nwk = A / 4 of 4 units each and keep their attention-LSTM slice --
+// 16 gate rows x (E + A) / 32 columns per thread, k_decoder_split's worker layout (att_w4, stat_load / stat_mv16) -- IN REGISTERS
+// for the whole utterance: the chain's matvec streams nothing.
+constexpr int SKR_FA = 32;   // columns per thread: E + A <= 1024
+template <bool REGW>
+__global__ __launch_bounds__(NTC) void k_decoder_forced(DecArgs p, const float* __restrict__ xa /*[B][T][4A]*/,
+                                                        float* __restrict__ hc /*[B][D + E][T]*/,
+                                                        unsigned long long* __restrict__ xw /*[B][T][A + E + D]*/, int NA, int UD) {
+  extern __shared__ float sm[];
+  __shared__ float c_state[160];   // <= 160 units per workgroup
+  const int blk = blockIdx.x, b = p.b0 + blockIdx.y, tid = threadIdx.x;
+  const int T = p.max_steps;
+  DecLds L;
+  dec_carve(p, sm, L);
+  const size_t fw = (size_t)(p.A + p.E + p.D);               // words per frame: [AH | CTX | DH]
+  unsigned long long* xb = xw + (size_t)b * T * fw;
+  float* hcb = hc + (size_t)b * L.KP * T;
+  if (tid < 160) c_state[tid] = 0.0f;
+  if (blk >= NA) {   // ------------------------------------------------ decoder-LSTM workgroup
+    const int wg = blk - NA, ND = gridDim.x - NA, unit0 = wg * UD;
+    const float* dec_slice = p.dec_coop + (size_t)wg * L.KD * 4 * UD;
+    for (int i = tid; i < L.KD; i += NTC) L.in_dec[i] = 0.0f;
+    __syncthreads();
+    float* dh = L.in_dec + p.A + p.E;
+    for (int t = 0; t < T; ++t) {
+      unsigned long long* xt = xb + (size_t)t * fw;
+      if (t > 0) {
+        coop_gather<NTC>(xt - fw + p.A + p.E, (unsigned)t, p.D, dh, dh, tid);
+        for (int k = wg + ND * tid; k < p.D; k += ND * NTC) hcb[(size_t)k * T + t - 1] = dh[k];
+      }
+      coop_gather<NTC>(xt, (unsigned)(t + 1), p.A + p.E, L.in_dec, L.in_dec, tid);   // [ah | ctx] of this frame
+      for (int k = wg + ND * tid; k < p.E; k += ND * NTC) hcb[(size_t)(p.D + k) * T + t] = L.in_dec[p.A + k];
+      coop_lstm_slice<NTC>(dec_slice, p.dec_b, L.KD, UD, p.D, unit0, L.in_dec, L.part, c_state, xt + p.A + p.E, (unsigned)(t + 1), tid);
+    }
+    coop_gather<NTC>(xb + (size_t)(T - 1) * fw + p.A + p.E, (unsigned)T, p.D, dh, dh, tid);
+    for (int k = wg + ND * tid; k < p.D; k += ND * NTC) hcb[(size_t)k * T + T - 1] = dh[k];
+    return;
+  }
+  // ------------------------------------------------------------------ chain workgroup
+  const int wg = blk;
+  const bool leader = wg == 0;
+  const int len = p.lengths ? p.lengths[b] : p.Tin;
+  dec_init<NTC>(p, L, sm, tid);
+  __syncthreads();
+  const float* mem = p.memory + (size_t)b * p.Tin * p.E;
+  const float* pm = p.pm + (size_t)b * p.Tin * p.AD;
+  float* ah = L.in_att + p.P + p.E;
+  // attn_energy_pre's results, behind everything dec_carve laid out
+  float4* stash = reinterpret_cast<float4*>(sm + round_up((int)dec_lds_floats(p.P, p.E, p.A, p.D, p.NF, p.AD, p.NFIL, p.KSZ, p.Tin), 4));
+  const int SC = 4 * p.U, unit0 = wg * p.U;
+  // the slices are [K][4U] k-major over [prenet | ctx | ah]: the prenet rows were taken by the GEMM
+  const float* att_slice = p.att_coop + ((size_t)wg * L.KA + p.P) * SC;
+  const float* xab = xa + (size_t)b * T * L.G;
+  float w_att[REGW ? SKR_FA : 1];
+  if constexpr (REGW) stat_load(w_att, p.att_w4 + ((size_t)wg * L.KA + p.P) * SSC, SSC, 0, SSC, p.E + p.A, tid);
+  // attention LSTMCell of frame tf (this workgroup's units) -> AH words of that frame
+  auto att_step = [&](int tf) __attribute__((always_inline)) {
+    unsigned long long* out = xb + (size_t)tf * fw;
+    const float* xrow = xab + (size_t)tf * L.G;
+    if constexpr (REGW) {
+      const int u = wg * SU + tid;
+      float x4[4] = {0.0f, 0.0f, 0.0f, 0.0f};
+      if (tid < SU && u < p.A) {
+#pragma unroll
+        for (int g = 0; g < 4; ++g) x4[g] = xrow[g * p.A + u];
+      }
+      stat_mv16(w_att, p.E + p.A, L.in_att + p.P, L.part, tid);
+      if (tid < SU && u < p.A) {
+        const float* gs = L.part + 256;
+        xpub(out + u, lstm_point(gs[tid] + x4[0], gs[SU + tid] + x4[1], gs[2 * SU + tid] + x4[2], gs[3 * SU + tid] + x4[3], &c_state[tid]),
+             (unsigned)(tf + 1));
+      }
+    } else {
+      forced_att_slice<NTC>(att_slice, xrow, p.E + p.A, p.U, p.A, unit0, L.in_att + p.P, L.part, c_state, out, (unsigned)(tf + 1), tid);
+    }
+    __syncthreads();
+  };
+  att_step(0);
+  long long tk = clock64();
+#define PROF(slot)                                                        \
+  if (p.prof && leader && b == 0 && tid == 0) {                           \
+    const long long now = clock64();                                      \
+    p.prof[slot] += now - tk;                                             \
+    tk = now;                                                             \
+  }
+  for (int t = 0; t < T; ++t) {
+    unsigned long long* xt = xb + (size_t)t * fw;
+    int lo, hi;
+    attn_window_range(p.window, t, len, &lo, &hi);
+    attn_features<NTC>(p, L, lo, min(64, hi - lo + 1), tid);   // needs only frame t-1's weights
+    __syncthreads();
+    attn_energy_pre<NTC>(p, L, pm, lo, min(64, hi - lo + 1), tid, stash);   // ... and so does this part of the energies
+    PROF(0)
+    coop_gather<NTC>(xt, (unsigned)(t + 1), p.A, ah, L.in_dec, tid);
+    PROF(1)
+    dec_attention<NTC, 0, true>(p, L, mem, pm, len, t, b, tid, leader, true, NoQueryRegs().w, stash);
+    if (leader)
+      for (int i = tid; i < p.E; i += NTC) xpub(xt + p.A + i, L.in_proj[p.D + i], (unsigned)(t + 1));
+    PROF(2)
+    if (t + 1 < T) att_step(t + 1);
+    PROF(3)
+  }
+#undef PROF
+}
+
+// [go frame; targets[..., :T - 1]] (model.py:459-461), channel-major: x[b][c][t] = t ? targets[b][c][t - 1] : 0
+__global__ void k_forced_inputs(const float* __restrict__ tgt, float* __restrict__ x, size_t rows, int T) {
+  const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= rows * T) return;
+  const int t = (int)(i % T);
+  x[i] = t ? tgt[i - 1] : 0.0f;
+}
+// the projection GEMM's [B][NF + 1][T] -> mel [B][NF][T], gate [B][T]
+__global__ void k_forced_outputs(const float* __restrict__ mg, float* __restrict__ mel, float* __restrict__ gate, int B, int NF, int T) {
+  const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= (size_t)B * (NF + 1) * T) return;
+  const int t = (int)(i % T), r = (int)(i / T % (NF + 1)), b = (int)(i / T / (NF + 1));
+  if (r < NF) mel[((size_t)b * NF + r) * T + t] = mg[i];
+  else gate[(size_t)b * T + t] = mg[i];
+}
+// dec masks of the teacher-forced pass [2][B][P][T]: the very bits facppg_taco_draw_dropout gives frame t of utterance b
+__global__ void k_random_mask_forced_utt(uint8_t* __restrict__ out, const uint64_t* __restrict__ seeds, int B, int P, int T) {
+  const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= (size_t)2 * B * P * T) return;
+  const int t = (int)(i % T), u = (int)(i / T % P), b = (int)(i / T / P % B), j = (int)(i / T / P / B);
+  out[i] = mask_bit(seeds[b] ^ 0xD1B54A32D192ED03ull, ((uint64_t)t << 32) | (uint32_t)(j * P + u));
+}
+
+// ------------------------------------------------------------------------------------------
 struct TWs {
   size_t a0, a1, xproj, mem_cm, mask, xchg, splitk, splitk_bytes, total;
 };
@@ -1562,7 +1742,7 @@ extern "C" int facppg_taco_create(const facppg_taco_config* cfg, const float* ws
     // the neighbouring stages' kernels on other streams find a CU.  0 => the one-workgroup kernels run instead.
     int per_cu = 1;
     const struct { const void* fn; size_t lds; } coop_kernels[] = {
-        {(const void*)k_decoder_coop, 150 * 1024}, {(const void*)k_decoder_split<1>, 150 * 1024},
+        {(const void*)k_decoder_coop, 150 * 1024}, {(const void*)k_decoder_forced<false>, 150 * 1024}, {(const void*)k_decoder_forced<true>, 150 * 1024}, {(const void*)k_decoder_split<1>, 150 * 1024},
         {(const void*)k_decoder_split<2>, 150 * 1024}, {(const void*)k_decoder_split<3>, 150 * 1024},
         {(const void*)k_bilstm_coop<32, 96>, 0}, {(const void*)k_bilstm_coop<64, 152>, 0}};
     for (const auto& k : coop_kernels) {
@@ -1604,7 +1784,8 @@ extern "C" int facppg_taco_create(const facppg_taco_config* cfg, const float* ws
   size_t off = 0;
   auto take = [&](size_t bytes) { size_t o = off; off += (bytes + 255) / 256 * 256; return o; };
   struct { size_t pre0, pre1, conv[8], conv_b[8], conv_sc[8], conv_sh[8], wih, whh[2], lstm_b, mem_w, dp0, dp1, att, att_b, dec, dec_b, q,
-           proj, proj_b, lc, ld, v, attc[5], decc[5], att4, dec4, w1p, b1p, post[8], post_b[8], post_sc[8], post_sh[8]; } o;
+           proj, proj_b, lc, ld, v, attc[5], decc[5], att4, dec4, w1p, b1p, post[8], post_b[8], post_sc[8], post_sh[8],
+           tf_dp0, tf_dp1, tf_attx, tf_proj; } o;
   o.pre0 = take(packed_a_float4s(S, c.n_symbols) * 16);
   o.pre1 = take(packed_a_float4s(S, S) * 16);
   for (int j = 0; j < c.encoder_n_convolutions; ++j) {
@@ -1634,6 +1815,8 @@ extern "C" int facppg_taco_create(const facppg_taco_config* cfg, const float* ws
     o.post[j] = take(packed_a_float4s(co, ci * PK) * 16);
     o.post_b[j] = take(co * 4); o.post_sc[j] = take(co * 4); o.post_sh[j] = take(co * 4);
   }
+  o.tf_dp0 = take(packed_a_float4s(P, NF) * 16); o.tf_dp1 = take(packed_a_float4s(P, P) * 16);
+  o.tf_attx = take(packed_a_float4s(G, P) * 16); o.tf_proj = take(packed_a_float4s(NF + 1, D + E) * 16);
   if (hipMalloc((void**)&h->arena, off) != hipSuccess) {
     h->arena = nullptr;
     set_error("hipMalloc(%zu) failed", off);
@@ -1685,8 +1868,12 @@ extern "C" int facppg_taco_create(const facppg_taco_config* cfg, const float* ws
   h->dp0_t = F(o.dp0); h->dp1_t = F(o.dp1); h->att_t = F(o.att); h->att_b = F(o.att_b); h->dec_t = F(o.dec); h->dec_b = F(o.dec_b);
   h->q_t = F(o.q); h->proj_t = F(o.proj); h->proj_b = F(o.proj_b); h->loc_conv = F(o.lc); h->loc_dense = F(o.ld); h->v = F(o.v);
   h->mem_w = F4(o.mem_w);
+  h->tf_dp0 = F4(o.tf_dp0); h->tf_dp1 = F4(o.tf_dp1); h->tf_attx = F4(o.tf_attx); h->tf_proj = F4(o.tf_proj);
+  if (!rc) rc = pack_a(src, P, NF, 1, h->tf_dp0, s);
   tr(src, h->dp0_t, P, NF, Pp, 0); src += (size_t)P * NF;
+  if (!rc) rc = pack_a(src, P, P, 1, h->tf_dp1, s);
   tr(src, h->dp1_t, P, P, Pp, 0); src += (size_t)P * P;
+  if (!rc) rc = pack_a_strided(src, G, P, 1, P + E, 1, 0, 0, h->tf_attx, s);   // the prenet columns of W_ih [4A][P + E]
   tr(src, h->att_t, G, P + E, G, 0); src += (size_t)G * (P + E);
   tr(src, h->att_t, G, A, G, P + E); src += (size_t)G * A;
   k_add2<<<(G + 255) / 256, 256, 0, s>>>(src, src + G, h->att_b, G); src += 2 * (size_t)G;
@@ -1725,6 +1912,8 @@ extern "C" int facppg_taco_create(const facppg_taco_config* cfg, const float* ws
     h->w1p_t = F(o.w1p); h->b1p = F(o.b1p);
     const int n = (D + E + 1) * Pp;
     k_fold_prenet<<<(n + 255) / 256, 256, 0, s>>>(h->proj_t, h->proj_b, h->dp0_t, h->w1p_t, h->b1p, D + E, NF, NFp, Pp);
+    // projection + gate as one [NF + 1][D + E] GEMM operand, read back from the k-major image built above
+    if (!rc) rc = pack_a_strided(h->proj_t, NF + 1, D + E, 1, 1, NFp, 0, 0, h->tf_proj, s);
   }
   for (int j = 0; j < c.postnet_n_convolutions; ++j) {
     const int ci = j == 0 ? NF : PE, co = j == c.postnet_n_convolutions - 1 ? NF : PE;
@@ -1753,10 +1942,12 @@ extern "C" size_t facppg_taco_workspace_bytes(const facppg_taco* h, int B, int T
   return tws_layout(h->c, B, Tin).total;
 }
 
-// Encoder.inference (model.py:237-249) + Attention.memory_layer (model.py:334).
-extern "C" int facppg_taco_encode(const facppg_taco* h, const float* ppg_dev, const int32_t* lengths_dev, const uint8_t* masks_dev,
-                                  uint64_t seed, int B, int Tin, float* memory_dev, float* pm_dev, void* ws_, size_t ws_bytes,
-                                  void* stream_) {
+// Encoder.inference (model.py:237-249) + Attention.memory_layer (model.py:334); padded_batch: Encoder.forward (model.py:215-235),
+// whose prenet and conv bank run over all Tin columns of every utterance (the caller's zero padding turns non-zero behind
+// the first biased layer and reaches the valid frames through the k-wide convolutions) and only the BiLSTM follows the lengths.
+static int taco_encode_impl(const facppg_taco* h, const float* ppg_dev, const int32_t* lengths_dev, const uint8_t* masks_dev,
+                            uint64_t seed, int B, int Tin, float* memory_dev, float* pm_dev, void* ws_, size_t ws_bytes,
+                            void* stream_, bool padded_batch) {
   FACPPG_REQUIRE(h && ppg_dev && memory_dev && pm_dev && ws_, FACPPG_EINVAL, "NULL argument");
   FACPPG_REQUIRE(B > 0 && Tin > 0 && B <= 65535, FACPPG_EINVAL, "bad B/Tin");
   const facppg_taco_config& c = h->c;
@@ -1777,7 +1968,7 @@ extern "C" int facppg_taco_encode(const facppg_taco* h, const float* ppg_dev, co
     masks = m;
   }
   GemmArgs g;
-  g.B = B; g.N = Tin; g.n_valid = lengths_dev;
+  g.B = B; g.N = Tin; g.n_valid = padded_batch ? nullptr : lengths_dev;
   g.splitk_ws = (float*)(ws + w.splitk); g.splitk_ws_bytes = w.splitk_bytes;
   // prenet: 2 x (Linear no bias, ReLU, dropout p=.5 always on)  model.py:124-135
   g.A = h->pre0; g.M = S; g.Cin = c.n_symbols; g.X = ppg_dev; g.x_bs = (long)c.n_symbols * Tin; g.ldx = Tin; g.act = ACT_RELU;
@@ -1831,6 +2022,33 @@ extern "C" int facppg_taco_encode(const facppg_taco* h, const float* ppg_dev, co
   if (int rc = gemm_launch(m, s)) return rc;
   FACPPG_HIP_CHECK(hipGetLastError());
   return FACPPG_OK;
+}
+
+extern "C" int facppg_taco_encode(const facppg_taco* h, const float* ppg_dev, const int32_t* lengths_dev, const uint8_t* masks_dev,
+                                  uint64_t seed, int B, int Tin, float* memory_dev, float* pm_dev, void* ws_, size_t ws_bytes,
+                                  void* stream_) {
+  return taco_encode_impl(h, ppg_dev, lengths_dev, masks_dev, seed, B, Tin, memory_dev, pm_dev, ws_, ws_bytes, stream_, false);
+}
+
+// Encoder.forward (model.py:215-235) + Attention.memory_layer (model.py:334) over a zero-padded batch.
+extern "C" int facppg_taco_encode_padded(const facppg_taco* h, const float* ppg_dev, const int32_t* lengths_dev,
+                                         const int32_t* lengths_host, const uint8_t* masks_dev, uint64_t seed, int B, int Tin,
+                                         float* memory_dev, float* pm_dev, void* ws_, size_t ws_bytes, void* stream_) {
+  FACPPG_REQUIRE(h && memory_dev && pm_dev, FACPPG_EINVAL, "NULL argument");
+  FACPPG_REQUIRE(B > 0 && Tin > 0, FACPPG_EINVAL, "bad B/Tin");
+  FACPPG_REQUIRE((lengths_dev == nullptr) == (lengths_host == nullptr), FACPPG_EINVAL, "lengths_dev and lengths_host go together");
+  for (int b = 0; lengths_host && b < B; ++b) {
+    FACPPG_REQUIRE(lengths_host[b] >= 1 && lengths_host[b] <= Tin, FACPPG_EINVAL, "lengths[%d] = %d is outside [1, Tin = %d]", b,
+                   lengths_host[b], Tin);
+    FACPPG_REQUIRE(b == 0 || lengths_host[b] <= lengths_host[b - 1], FACPPG_EINVAL,
+                   "lengths must be sorted in descending order (pack_padded_sequence, model.py:226): lengths[%d] = %d > lengths[%d] = %d",
+                   b, lengths_host[b], b - 1, lengths_host[b - 1]);
+  }
+  hipStream_t s = (hipStream_t)stream_;
+  // the BiLSTM and the memory layer write valid frames only: everything behind them is zero (pad_packed_sequence)
+  FACPPG_HIP_CHECK(hipMemsetAsync(memory_dev, 0, (size_t)B * Tin * h->c.encoder_embedding_dim * 4, s));
+  FACPPG_HIP_CHECK(hipMemsetAsync(pm_dev, 0, (size_t)B * Tin * h->c.attention_dim * 4, s));
+  return taco_encode_impl(h, ppg_dev, lengths_dev, masks_dev, seed, B, Tin, memory_dev, pm_dev, ws_, ws_bytes, stream_, true);
 }
 
 namespace {
@@ -2016,6 +2234,158 @@ extern "C" int facppg_taco_decode(const facppg_taco* h, const float* memory_dev,
   }
   FACPPG_HIP_CHECK(hipGetLastError());
   if (opts) { opts->mode = launch_mode; opts->workgroups = launch_wgs; opts->streamed = a.melx != nullptr; }
+  return FACPPG_OK;
+}
+
+namespace {
+struct ForcedWs { size_t x0, p1, p2, xa, hc, mg, mask, xchg, prof, splitk, splitk_bytes, total; };
+ForcedWs forced_ws(const facppg_taco_config& c, int B, int T) {
+  ForcedWs w;
+  size_t off = 0;
+  auto take = [&](size_t bytes) { size_t o = off; off += (bytes + 255) / 256 * 256; return o; };
+  const size_t BT = (size_t)B * T;
+  w.x0 = take(BT * c.n_acoustic_feat_dims * 4);
+  w.p1 = take(BT * c.prenet_dim * 4);
+  w.p2 = take(BT * c.prenet_dim * 4);
+  w.xa = take(BT * 4 * c.attention_rnn_dim * 4);
+  w.hc = take(BT * (c.decoder_rnn_dim + c.encoder_embedding_dim) * 4);
+  w.mg = take(BT * (c.n_acoustic_feat_dims + 1) * 4);
+  w.mask = take(2 * BT * c.prenet_dim);
+  w.xchg = take(BT * (c.attention_rnn_dim + c.encoder_embedding_dim + c.decoder_rnn_dim) * 8);   // {value, frame + 1} words, by frame
+  w.prof = take(32 * 8);
+  w.splitk_bytes = 16 * BT * (c.n_acoustic_feat_dims + 1) * 4;   // the projection's split-K partial sums
+  w.splitk = take(w.splitk_bytes);
+  w.total = off;
+  return w;
+}
+}  // namespace
+
+extern "C" size_t facppg_taco_decode_forced_workspace_bytes(const facppg_taco* h, int B, int T_out) {
+  if (!h || B <= 0 || T_out <= 0) return 0;
+  return forced_ws(h->c, B, T_out).total;
+}
+
+extern "C" int facppg_taco_draw_dropout_forced(const facppg_taco* h, const uint64_t* seeds_dev, int B, int T_out,
+                                               uint8_t* dec_masks_dev, void* stream_) {
+  FACPPG_REQUIRE(h && seeds_dev && dec_masks_dev, FACPPG_EINVAL, "NULL argument");
+  FACPPG_REQUIRE(B > 0 && T_out > 0, FACPPG_EINVAL, "bad B/T_out");
+  const size_t n = (size_t)2 * B * h->c.prenet_dim * T_out;
+  k_random_mask_forced_utt<<<(unsigned)((n + 255) / 256), 256, 0, (hipStream_t)stream_>>>(dec_masks_dev, seeds_dev, B, h->c.prenet_dim, T_out);
+  FACPPG_HIP_CHECK(hipGetLastError());
+  return FACPPG_OK;
+}
+
+// Decoder.forward (model.py:444-487), eval mode.
+extern "C" int facppg_taco_decode_forced(const facppg_taco* h, const float* memory_dev, const float* pm_dev, const int32_t* lengths_dev,
+                                         const float* targets_dev, const uint8_t* masks_dev, uint64_t seed, int B, int Tin, int T_out,
+                                         float* mel_dev, float* gate_dev, float* align_dev, void* ws_, size_t ws_bytes,
+                                         facppg_taco_decode_opts* opts, void* stream_) {
+  FACPPG_REQUIRE(h && memory_dev && pm_dev && targets_dev && mel_dev && gate_dev && ws_, FACPPG_EINVAL, "NULL argument");
+  FACPPG_REQUIRE(B > 0 && Tin > 0 && T_out > 0 && B <= 65535, FACPPG_EINVAL, "bad B/Tin/T_out");
+  FACPPG_REQUIRE(!opts || opts->max_workgroups >= 0, FACPPG_EINVAL, "negative max_workgroups");
+  FACPPG_REQUIRE(Tin <= 8192, FACPPG_EUNSUPPORTED, "Tin > 8192 does not fit the decoder's LDS state");
+  const facppg_taco_config& c = h->c;
+  hipStream_t s = (hipStream_t)stream_;
+  const ForcedWs w = forced_ws(c, B, T_out);
+  FACPPG_REQUIRE(ws_bytes >= w.total, FACPPG_EWORKSPACE, "teacher-forced decode workspace has %zu bytes, need %zu", ws_bytes, w.total);
+  char* ws = (char*)ws_;
+  const int P = c.prenet_dim, E = c.encoder_embedding_dim, A = c.attention_rnn_dim, D = c.decoder_rnn_dim, NF = c.n_acoustic_feat_dims;
+  const int T = T_out, G = 4 * A, KP = D + E;
+  float *x0 = (float*)(ws + w.x0), *p1 = (float*)(ws + w.p1), *p2 = (float*)(ws + w.p2), *xa = (float*)(ws + w.xa);
+  float *hc = (float*)(ws + w.hc), *mg = (float*)(ws + w.mg);
+  const uint8_t* masks = masks_dev;
+  const size_t nmask = (size_t)2 * B * P * T;
+  if (!masks) {
+    k_random_mask<<<(unsigned)((nmask + 255) / 256), 256, 0, s>>>((uint8_t*)(ws + w.mask), nmask, seed ^ 0xD1B54A32D192ED03ull);
+    masks = (const uint8_t*)(ws + w.mask);
+  }
+  // prenet over [go frame; targets[..., :T - 1]] (model.py:459-462) and the attention LSTM's input product of its output
+  {
+    const size_t n = (size_t)B * NF * T;
+    k_forced_inputs<<<(unsigned)((n + 255) / 256), 256, 0, s>>>(targets_dev, x0, (size_t)B * NF, T);
+  }
+  GemmArgs g;
+  g.B = B; g.N = T; g.A = h->tf_dp0; g.M = P; g.Cin = NF; g.X = x0; g.x_bs = (long)NF * T; g.ldx = T; g.act = ACT_RELU;
+  g.mask = masks; g.mask_bs = (long)P * T; g.ldmask = T; g.C = p1; g.c_bs = (long)P * T; g.ldc = T;
+  if (int rc = gemm_launch(g, s)) return rc;
+  g.A = h->tf_dp1; g.Cin = P; g.X = p1; g.x_bs = (long)P * T; g.mask = masks + (size_t)B * P * T; g.C = p2;
+  if (int rc = gemm_launch(g, s)) return rc;
+  GemmArgs x;
+  x.B = B; x.N = T; x.A = h->tf_attx; x.M = G; x.Cin = P; x.X = p2; x.x_bs = (long)P * T; x.ldx = T; x.bias = h->att_b;
+  x.C = xa; x.c_bs = (long)T * G; x.ldc = G; x.c_transposed = 1;
+  if (int rc = gemm_launch(x, s)) return rc;
+  // the recurrence: one launch per chunk of co-resident utterances (one launch whenever B * workgroups-per-utterance fit)
+  DecArgs a = {};
+  a.dec_b = h->dec_b; a.q_t = h->q_t; a.loc_conv = h->loc_conv; a.loc_dense = h->loc_dense; a.v = h->v;
+  a.memory = memory_dev; a.pm = pm_dev; a.lengths = lengths_dev; a.align = align_dev;
+  a.B = B; a.Tin = Tin; a.E = E; a.P = P; a.A = A; a.D = D; a.AD = c.attention_dim; a.NF = NF;
+  a.NFIL = c.attention_location_n_filters; a.KSZ = c.attention_location_kernel_size; a.window = c.attention_window_size;
+  a.max_steps = T; a.gate_thr = c.gate_threshold;
+  // chain workgroups: the decoder's LDS state + attn_energy_pre's stash ([8][NTC] float4)
+  const size_t smem = (round_up((int)dec_lds_floats(a.P, a.E, a.A, a.D, a.NF, a.AD, a.NFIL, a.KSZ, Tin), 4) + (size_t)8 * NTC * 4) * 4;
+  FACPPG_REQUIRE(smem <= 160 * 1024 - 1024, FACPPG_EUNSUPPORTED, "decoder state (%zu bytes) exceeds LDS", smem);
+  const int max_wgs = opts ? opts->max_workgroups : 0;
+  const int wg_limit = max_wgs > 0 && max_wgs < h->coop_limit ? max_wgs : h->coop_limit;
+  FACPPG_REQUIRE(wg_limit >= 2 * h->coop_nwg[4], FACPPG_EUNSUPPORTED, "the teacher-forced decoder needs %d co-resident workgroups, %d allowed",
+                 2 * h->coop_nwg[4], wg_limit);
+  // Slice widths: the narrowest chain slices (the dependent chain) whose workgroups, with decoder-LSTM workgroups of the same
+  // or the next width (they have a frame's slack), stay co-resident for nb utterances; FACPPG_DECODER_COOP_U (tests / tuning)
+  // forces one width for both roles.
+  const char* force_u = getenv("FACPPG_DECODER_COOP_U");
+  auto pick = [&](int nb, int* vc, int* vd) {
+    for (int c2 = 0; c2 < 5; ++c2) {
+      if (force_u && atoi(force_u) != h->coop_U[c2]) continue;
+      for (int d2 = c2; d2 <= (force_u ? c2 : std::min(c2 + 1, 4)); ++d2)
+        if ((long)nb * (h->coop_nwg[c2] + h->coop_nwg[d2]) <= wg_limit) { *vc = c2; *vd = d2; return true; }
+    }
+    return false;
+  };
+  // up to 2 utterances: register-resident attention-LSTM slices of 4 units (k_decoder_forced<true>) next to the narrowest decoder slices
+  const bool regw = !force_u && !getenv("FACPPG_FORCED_NO_REGW") && (long)B * (h->split_nwk + h->coop_nwg[0]) <= wg_limit &&
+                    E + A <= SKP * SKR_FA && A <= h->split_nwk * SU;
+  int vc = 4, vd = 4, chunk = B;
+  if (regw) { vc = vd = 0; }
+  else if (!pick(B, &vc, &vd)) {   // beyond that the widest slices run the batch in chunks of co-resident utterances
+    FACPPG_REQUIRE(!force_u, FACPPG_EUNSUPPORTED, "FACPPG_DECODER_COOP_U=%s does not fit B = %d", force_u, B);
+    vc = vd = 4; chunk = wg_limit / (2 * h->coop_nwg[4]);
+  }
+  unsigned long long* xw = (unsigned long long*)(ws + w.xchg);
+  FACPPG_HIP_CHECK(hipMemsetAsync(xw, 0, w.prof + 32 * 8 - w.xchg, s));   // the exchange words and the phase counters behind them
+  a.prof = getenv("FACPPG_DECODER_PROF") ? (long long*)(ws + w.prof) : nullptr;
+  const void* fn = regw ? (const void*)k_decoder_forced<true> : (const void*)k_decoder_forced<false>;
+  FACPPG_HIP_CHECK(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem));
+  a.att_w4 = h->att_w4;
+  int launch_wgs = 0;
+  for (int b0 = 0; b0 < B; b0 += chunk) {
+    const int nb = B - b0 < chunk ? B - b0 : chunk;
+    int cv = vc, dv = vd;   // the last chunk may be small enough for narrower slices
+    if (nb < chunk && !force_u && !regw) pick(nb, &cv, &dv);
+    a.b0 = b0; a.att_coop = h->att_coop[cv]; a.dec_coop = h->dec_coop[dv]; a.U = h->coop_U[cv];
+    const float* xa_c = xa;
+    int NA = regw ? h->split_nwk : h->coop_nwg[cv], UD = h->coop_U[dv];
+    void* args[] = {(void*)&a, (void*)&xa_c, (void*)&hc, (void*)&xw, (void*)&NA, (void*)&UD};
+    FACPPG_HIP_CHECK(launch_coop(fn, dim3(NA + h->coop_nwg[dv], nb), dim3(NTC), args, smem, s));
+    launch_wgs = (NA + h->coop_nwg[dv]) * nb;
+  }
+  if (a.prof) {
+    long long pr[16];
+    FACPPG_HIP_CHECK(hipMemcpyAsync(pr, a.prof, sizeof(pr), hipMemcpyDeviceToHost, s));
+    FACPPG_HIP_CHECK(hipStreamSynchronize(s));
+    fprintf(stderr, "[facppg teacher-forced decoder prof (chain workgroup 0), shader cycles] features+energy_pre %lld gather_ah %lld attention %lld att_slice %lld | att: query %lld feat %lld energy %lld softmax %lld update %lld context %lld\n",
+            pr[0], pr[1], pr[2], pr[3], pr[8], pr[9], pr[10], pr[11], pr[12], pr[13]);
+  }
+  // linear_projection + gate_layer of every frame (model.py:436-441) on [decoder_hidden | context]
+  GemmArgs q;
+  q.splitk_ws = (float*)(ws + w.splitk); q.splitk_ws_bytes = w.splitk_bytes;
+  q.B = B; q.N = T; q.A = h->tf_proj; q.M = NF + 1; q.Cin = KP; q.X = hc; q.x_bs = (long)KP * T; q.ldx = T; q.bias = h->proj_b;
+  q.C = mg; q.c_bs = (long)(NF + 1) * T; q.ldc = T;
+  if (int rc = gemm_launch(q, s)) return rc;
+  {
+    const size_t n = (size_t)B * (NF + 1) * T;
+    k_forced_outputs<<<(unsigned)((n + 255) / 256), 256, 0, s>>>(mg, mel_dev, gate_dev, B, NF, T);
+  }
+  FACPPG_HIP_CHECK(hipGetLastError());
+  if (opts) { opts->mode = 1; opts->workgroups = launch_wgs; opts->streamed = 0; }
   return FACPPG_OK;
 }
 

@@ -163,6 +163,11 @@ def _declare(lib):
         "facppg_taco_decode": (c.c_int, [vp, vp, vp, vp, vp, vp, u64, c.c_int, c.c_int, c.c_int, vp, vp, vp, vp, vp, sz,
                                          c.POINTER(TacoDecodeOpts), vp]),
         "facppg_taco_draw_dropout": (c.c_int, [vp, vp, c.c_int, c.c_int, c.c_int, vp, vp, vp]),
+        "facppg_taco_encode_padded": (c.c_int, [vp, vp, vp, vp, vp, u64, c.c_int, c.c_int, vp, vp, vp, sz, vp]),
+        "facppg_taco_decode_forced_workspace_bytes": (sz, [vp, c.c_int, c.c_int]),
+        "facppg_taco_decode_forced": (c.c_int, [vp, vp, vp, vp, vp, vp, u64, c.c_int, c.c_int, c.c_int, vp, vp, vp, vp, sz,
+                                                c.POINTER(TacoDecodeOpts), vp]),
+        "facppg_taco_draw_dropout_forced": (c.c_int, [vp, vp, c.c_int, c.c_int, vp, vp]),
         "facppg_wg_draw_noise": (c.c_int, [vp, vp, c.c_int, c.c_int, vp, vp]),
         "facppg_taco_postnet": (c.c_int, [vp, vp, vp, c.c_int, c.c_int, c.c_int, vp, vp, sz, vp]),
         "facppg_mfcc_create": (c.c_int, [c.c_int, c.c_int, c.c_int, vp, vp, c.c_int, vp, c.c_int, c.c_int, vp, c.POINTER(vp)]),

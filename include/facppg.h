@@ -527,6 +527,49 @@ int facppg_taco_decode(const facppg_taco* h, const float* memory_dev, const floa
                        int Tin, int max_steps, float* mel_dev, float* gate_dev, float* align_dev,
                        int32_t* out_lengths_dev, void* workspace_dev, size_t workspace_bytes,
                        facppg_taco_decode_opts* opts, void* stream);
+/* ---- the teacher-forced pass (Tacotron2.forward, model.py:580-595, eval mode): encode_padded -> decode_forced ->
+ * facppg_taco_postnet(out_lengths_dev = NULL); the parse_output masking (model.py:566-578) is the caller's.
+ *
+ * facppg_taco_encode_padded replaces Encoder.forward (model.py:215-235) + the memory_layer projection (model.py:334).  It is
+ *   a PADDED-BATCH computation, not B independent runs: the prenet and the conv bank run over all Tin columns of every
+ *   utterance (ppg_dev zero-padded by the caller), so the padded frames, non-zero behind the first bias / BatchNorm shift, reach
+ *   the last valid frames of the shorter utterances through the convolutions; only the BiLSTM (pack_padded_sequence) and the
+ *   memory layer follow the lengths.  memory_dev and pm_dev are zero beyond each length (written by the call).  lengths_dev /
+ *   lengths_host: the same [B] values on the device and on the host (both NULL: every utterance has Tin frames); they must be
+ *   in [1, Tin] and descending, as pack_padded_sequence demands -- anything else is FACPPG_EINVAL.  Masks, seed, workspace
+ *   (facppg_taco_workspace_bytes) and output layouts as facppg_taco_encode.
+ * facppg_taco_decode_forced replaces Decoder.forward (model.py:444-487): targets_dev [B][n_feat][T_out] (zero-padded), masks_dev
+ *   NULL (drawn from `seed`) or uint8 [2][B][prenet_dim][T_out] -- layer, utterance, channel, INPUT frame (frame 0 is the go
+ *   frame; the reference draws T_out + 1 frames and uses the first T_out).  The prenet of all frames, the attention LSTM's input
+ *   product of its output, and the projection + gate of all frames are GEMMs around ONE cooperative launch for the recurrence
+ *   (attention LSTMCell -> location-sensitive attention with the window mask of utils.py:46-78 -> decoder LSTMCell), exactly
+ *   T_out steps for every utterance: no stop rule, shorter utterances go on decoding their zero targets.  Outputs, unmasked:
+ *   mel_dev [B][n_feat][T_out], gate_dev [B][T_out], align_dev NULL or [B][T_out][Tin] (fully written).  opts NULL, or
+ *   max_workgroups as in facppg_taco_decode; the call reports mode = 1 and the workgroups of its (last) launch.  Batches whose
+ *   workgroups do not fit the device together run in chunks of co-resident utterances.  Unlike facppg_taco_decode there is no
+ *   one-workgroup shape: the call needs a cooperative launch of at least 4 co-resident workgroups (2 chain + 2 decoder-LSTM;
+ *   FACPPG_EUNSUPPORTED if the device or max_workgroups allows fewer).  A chain workgroup holds the decoder's LDS state plus a
+ *   64 KiB stash of query-free energies, which bounds Tin lower than inference does: 2157 frames at the reference's
+ *   layer widths (inference: 7618); beyond it FACPPG_EUNSUPPORTED.  Up to 2 utterances run with register-resident
+ *   attention-LSTM slices (75 chain workgroups per utterance); FACPPG_FORCED_NO_REGW (environment, read per call, any value)
+ *   keeps the streamed slices, and FACPPG_DECODER_COOP_U forces one slice width for both roles -- tests and A/B runs, the
+ *   results agree to fp32 round-off.  Workspace: facppg_taco_decode_forced_workspace_bytes(h, B, T_out), about 27 KB per
+ *   utterance and frame at the reference's widths (9.6 KB of it the frame-indexed exchange words, which the call zeroes):
+ *   32 MB at B = 6, T_out = 200, 430 MB at B = 16, T_out = 1000.
+ * facppg_taco_draw_dropout_forced: the decoder-prenet masks [2][B][prenet_dim][T_out] keyed by seeds_dev[b] -- for every
+ *   (layer, channel, frame) the very bit facppg_taco_draw_dropout gives that utterance. */
+int facppg_taco_encode_padded(const facppg_taco* h, const float* ppg_dev, const int32_t* lengths_dev,
+                              const int32_t* lengths_host, const uint8_t* masks_dev, uint64_t seed, int B,
+                              int Tin, float* memory_dev, float* pm_dev, void* workspace_dev,
+                              size_t workspace_bytes, void* stream);
+size_t facppg_taco_decode_forced_workspace_bytes(const facppg_taco* h, int B, int T_out);
+int facppg_taco_decode_forced(const facppg_taco* h, const float* memory_dev, const float* pm_dev,
+                              const int32_t* lengths_dev, const float* targets_dev,
+                              const uint8_t* masks_dev, uint64_t seed, int B, int Tin, int T_out,
+                              float* mel_dev, float* gate_dev, float* align_dev, void* workspace_dev,
+                              size_t workspace_bytes, facppg_taco_decode_opts* opts, void* stream);
+int facppg_taco_draw_dropout_forced(const facppg_taco* h, const uint64_t* seeds_dev, int B, int T_out,
+                                    uint8_t* dec_masks_dev, void* stream);
 /* The always-on p=0.5 dropout draws of both prenets (Prenet.forward, model.py:132-135) as PER-UTTERANCE
  * streams keyed by seeds_dev[b] (uint64 [B]): enc_masks_dev uint8 [2][B][symbols_embedding_dim][Tin] and
  * dec_masks_dev uint8 [max_steps][2][B][prenet_dim] in the layouts facppg_taco_encode / _decode accept
@@ -542,7 +585,9 @@ int facppg_taco_draw_dropout(const facppg_taco* h, const uint64_t* seeds_dev, in
 int facppg_attention_window_mask(const int32_t* lengths_dev, int B, int Tmax, int window,
                                  int time_step, uint8_t* mask_dev, void* stream);
 /* Replaces Postnet.forward + the residual add (model.py:178-184, 604-605):
- * mel_dev [B][n_feat][ld] (first T columns used) -> mel_post_dev, same layout. */
+ * mel_dev [B][n_feat][ld] (first T columns used) -> mel_post_dev, same layout.  out_lengths_dev [B]: utterance b is
+ * convolved as its own out_lengths[b]-column run (columns beyond stay untouched); NULL: the padded-batch form of
+ * Tacotron2.forward (model.py:591-592) -- all T columns of every utterance, whatever follows its last frame included. */
 int facppg_taco_postnet(const facppg_taco* h, const float* mel_dev, const int32_t* out_lengths_dev,
                         int B, int T, int ld, float* mel_post_dev, void* workspace_dev,
                         size_t workspace_bytes, void* stream);
