@@ -6,7 +6,9 @@ reference's so ``load_state_dict(torch.load(ckpt)['state_dict'])`` works unchang
 them once into a ``facppg_taco`` handle and runs the encoder GEMMs, the BiLSTM kernel, the
 persistent decoder kernel and the postnet GEMMs of csrc/facppg_taco.hip through the C ABI;
 ``Tacotron2.forward`` is the teacher-forced pass (eval mode) on the padded-batch encoder, the
-teacher-forced recurrent kernel and the same postnet.  There is no CPU path, and no backward pass.
+teacher-forced recurrent kernel and the same postnet; ``forward(..., differentiable=True)`` attaches that pass to the autograd
+graph, its backward pass being common/taco_grad.py on the recurrent kernels of csrc/facppg_taco_bwd.hip.  There is no CPU
+path, and training-mode semantics (batch-statistics BatchNorm, the training-mode dropouts) are not built.
 
 Extensions over the reference signature (defaults reproduce it):
   ``inference(inputs, lengths=None, dropout_masks=None, seed=None)``
@@ -271,7 +273,7 @@ class Tacotron2(nn.Module):
             outputs[2].masked_fill_(pad, 1e3)
         return outputs
 
-    def forward(self, inputs, dropout_masks=None, seed=None, utterance_seeds=None):
+    def forward(self, inputs, dropout_masks=None, seed=None, utterance_seeds=None, differentiable=False):
         """The teacher-forced pass (model.py:580-595) in eval mode, on the HIP kernels of csrc/facppg_taco.hip.
         inputs = (ppg_padded [B, n_symbols, Tin], input_lengths [B] descending, acoustic_padded [B, n_feat, T_out], max_len,
         output_lengths [B]) as ``parse_batch`` returns them -> [mel, mel_post, gate [B, T_out], alignments [B, T_out, Tin]].
@@ -281,11 +283,23 @@ class Tacotron2(nn.Module):
         dropout_masks  (enc [2, B, Tin, E], dec [2, T_out + 1, B, prenet_dim]) keep-masks in the reference's draw order (it draws
                        T_out + 1 decoder frames and uses the first T_out); None -> drawn on the device from ``seed``
         utterance_seeds  B integers, as in ``inference``: utterance b's dropout draws depend on utterance_seeds[b] alone
-        B = 1 works (the reference's own forward fails there on a squeeze(), model.py:481).  The backward pass is not built:
-        in training mode the call raises; the three extra training-mode dropouts of the reference do not exist here."""
+        differentiable   per call, not model state.  False: the outputs are detached and nothing is kept, whatever the grad mode.
+                       True (eval mode, gradients enabled, at least one parameter requiring a gradient -- anything else
+                       raises): the same values, bit for bit, attached to the autograd graph; ``backward()`` leaves the
+                       gradients of this eval-mode function -- running-statistics BatchNorm, the prenet dropouts under the
+                       masks of this call, padded-batch semantics -- in all 61 parameter tensors.  ``alignments`` is not
+                       differentiable, and no gradient is produced for the PPG or the targets.
+        B = 1 works (the reference's own forward fails there on a squeeze(), model.py:481).  Training mode raises: the backward
+        pass is not built for ITS semantics (batch-statistics BatchNorm, the 0.5 / 0.1 training-mode dropouts)."""
         if self.training:
-            raise _lib.FacppgError("Tacotron2.forward: the backward pass is not built -- the teacher-forced pass runs in eval mode "
-                                   "only (call model.eval(); training the PPG->mel model is out of scope)")
+            raise _lib.FacppgError("Tacotron2.forward in training mode: the backward pass is not built for training-mode semantics "
+                                   "(batch-statistics BatchNorm, the training-mode dropouts) -- call model.eval(); "
+                                   "forward(..., differentiable=True) gives the gradients of the eval-mode pass")
+        if differentiable:
+            if not torch.is_grad_enabled():
+                raise _lib.FacppgError("Tacotron2.forward(differentiable=True) under torch.no_grad(): nothing could be attached to a graph")
+            if not any(p.requires_grad for p in self.parameters()):
+                raise _lib.FacppgError("Tacotron2.forward(differentiable=True): no parameter requires a gradient")
         ppg, input_lengths, targets, _max_len, output_lengths = self.parse_input(inputs)
         _lib.require_cuda(ppg, "Tacotron2.forward: inputs")
         _lib.require_cuda(targets, "Tacotron2.forward: targets")
@@ -347,13 +361,38 @@ class Tacotron2(nn.Module):
             _lib.check(L.facppg_taco_encode_padded(h, _lib.ptr(x), _lib.ptr(lt), _lib.ctypes.c_void_p(lens_host.data_ptr()),
                                                    _lib.ptr(enc_m), seed, B, Tin, _lib.ptr(memory), _lib.ptr(pm), _lib.ptr(ws),
                                                    ws.numel(), st))
+            if differentiable and enc_m is None:      # the masks the encoder drew from the seed, before its workspace is reused
+                enc_m = torch.empty(2, B, hp["symbols_embedding_dim"], Tin, dtype=torch.uint8, device=dev)
+                _lib.check(L.facppg_taco_encode_state(h, _lib.ptr(ws), ws.numel(), B, Tin, _lib.ptr(enc_m), st))
             _lib.check(L.facppg_taco_decode_forced(h, _lib.ptr(memory), _lib.ptr(pm), _lib.ptr(lt), _lib.ptr(tgt), _lib.ptr(dec_m),
                                                    seed, B, Tin, T, _lib.ptr(mel), _lib.ptr(gate), _lib.ptr(align), _lib.ptr(ws),
                                                    ws.numel(), _lib.ctypes.byref(opts), st))
+            if differentiable:                        # the LSTMCells' hidden states of every frame, out of the exchange words
+                ah = torch.empty(B, T, hp["attention_rnn_dim"], dtype=torch.float32, device=dev)
+                dh = torch.empty(B, T, hp["decoder_rnn_dim"], dtype=torch.float32, device=dev)
+                drawn = torch.empty(2, B, P, T, dtype=torch.uint8, device=dev) if dec_m is None else None
+                _lib.check(L.facppg_taco_decode_forced_state(h, _lib.ptr(ws), ws.numel(), B, T, _lib.ptr(ah), _lib.ptr(dh),
+                                                             _lib.ptr(drawn), st))
+                dec_m = drawn if dec_m is None else dec_m
             _lib.check(L.facppg_taco_postnet(h, _lib.ptr(mel), None, B, T, T, _lib.ptr(mel_post), _lib.ptr(ws), ws.numel(), st))
         # (for single-threaded callers: tests, tools)
         self.last_memory, self._last_launch = memory, DecoderLaunch("coop", opts.workgroups, False)
-        return self.parse_output([mel, mel_post, gate, align], out_lens)
+        if not differentiable:
+            return self.parse_output([mel, mel_post, gate, align], out_lens)
+        from common import taco_grad
+        s = taco_grad.ForcedState()
+        s.ppg, s.lengths, s.lengths_dev, s.targets, s.enc_masks, s.dec_masks = x, lens_host, lt, tgt, enc_m, dec_m
+        s.memory, s.mel, s.align, s.ah, s.dh = memory, mel, align, ah, dh
+        masking = self.mask_padding and out_lens is not None
+        s.pad = ~get_mask_from_lengths(out_lens) if masking else None
+        s.identity = self.__dict__["_facppg_handle"][2]
+        s.outputs, s.launches = (mel.clone(), mel_post, gate, align.clone()), None
+        outs = list(taco_grad.ForcedGraph.apply(self, s, *self.parameters()))
+        s.outputs = None
+        if masking:                                   # parse_output's masking as graph operations: the same values
+            outs = [outs[0].masked_fill(s.pad.unsqueeze(1), 0.0), outs[1].masked_fill(s.pad.unsqueeze(1), 0.0),
+                    outs[2].masked_fill(s.pad, 1e3), outs[3]]
+        return outs
 
     def draw_dropout_masks(self, utterance_seeds, Tin, device=None, steps=None):
         """Per-utterance dropout keep-masks (facppg_taco_draw_dropout) in the DEVICE layouts the kernels read:

@@ -2389,6 +2389,48 @@ extern "C" int facppg_taco_decode_forced(const facppg_taco* h, const float* memo
   return FACPPG_OK;
 }
 
+// The per-frame state facppg_taco_decode_forced left in its workspace, as the backward pass reads it: the exchange words'
+// values [B][T][AH | CTX | DH] -> ah [B][T][A], dh [B][T][D]; and the prenet masks the call drew, if it drew them.
+__global__ void k_forced_state(const unsigned long long* __restrict__ xw, float* __restrict__ ah, float* __restrict__ dh, size_t BT,
+                               int A, int E, int D) {
+  const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= BT * (A + D)) return;
+  const size_t r = i / (A + D);
+  const int k = (int)(i % (A + D));
+  const float v = __uint_as_float((unsigned)xw[r * (A + E + D) + (k < A ? k : k + E)]);
+  if (k < A) ah[r * A + k] = v;
+  else dh[r * D + k - A] = v;
+}
+
+extern "C" int facppg_taco_decode_forced_state(const facppg_taco* h, const void* ws_, size_t ws_bytes, int B, int T_out, float* ah_dev,
+                                               float* dh_dev, uint8_t* masks_dev, void* stream_) {
+  FACPPG_REQUIRE(h && ws_ && ah_dev && dh_dev, FACPPG_EINVAL, "NULL argument");
+  FACPPG_REQUIRE(B > 0 && T_out > 0, FACPPG_EINVAL, "bad B/T_out");
+  const facppg_taco_config& c = h->c;
+  const ForcedWs w = forced_ws(c, B, T_out);
+  FACPPG_REQUIRE(ws_bytes >= w.total, FACPPG_EWORKSPACE, "teacher-forced decode workspace has %zu bytes, need %zu", ws_bytes, w.total);
+  hipStream_t s = (hipStream_t)stream_;
+  const char* ws = (const char*)ws_;
+  const size_t BT = (size_t)B * T_out, n = BT * (c.attention_rnn_dim + c.decoder_rnn_dim);
+  k_forced_state<<<(unsigned)((n + 255) / 256), 256, 0, s>>>((const unsigned long long*)(ws + w.xchg), ah_dev, dh_dev, BT,
+                                                             c.attention_rnn_dim, c.encoder_embedding_dim, c.decoder_rnn_dim);
+  FACPPG_HIP_CHECK(hipGetLastError());
+  if (masks_dev) FACPPG_HIP_CHECK(hipMemcpyAsync(masks_dev, ws + w.mask, 2 * BT * c.prenet_dim, hipMemcpyDeviceToDevice, s));
+  return FACPPG_OK;
+}
+
+// The encoder-prenet masks facppg_taco_encode_padded drew from its seed (masks_dev = NULL), out of its workspace.
+extern "C" int facppg_taco_encode_state(const facppg_taco* h, const void* ws_, size_t ws_bytes, int B, int Tin, uint8_t* masks_dev,
+                                        void* stream_) {
+  FACPPG_REQUIRE(h && ws_ && masks_dev, FACPPG_EINVAL, "NULL argument");
+  FACPPG_REQUIRE(B > 0 && Tin > 0, FACPPG_EINVAL, "bad B/Tin");
+  const TWs w = tws_layout(h->c, B, Tin);
+  FACPPG_REQUIRE(ws_bytes >= w.total, FACPPG_EWORKSPACE, "encoder workspace has %zu bytes, need %zu", ws_bytes, w.total);
+  FACPPG_HIP_CHECK(hipMemcpyAsync(masks_dev, (const char*)ws_ + w.mask, (size_t)2 * B * h->c.symbols_embedding_dim * Tin,
+                                  hipMemcpyDeviceToDevice, (hipStream_t)stream_));
+  return FACPPG_OK;
+}
+
 // Postnet + residual (model.py:178-184, 604-605): mel_post = mel + postnet(mel).
 extern "C" int facppg_taco_postnet(const facppg_taco* h, const float* mel_dev, const int32_t* out_lengths_dev, int B, int T, int ld,
                                    float* mel_post_dev, void* ws_, size_t ws_bytes, void* stream_) {

@@ -44,6 +44,13 @@ class TacoDecodeOpts(ctypes.Structure):
                 ("mode", ctypes.c_int32), ("workgroups", ctypes.c_int32), ("streamed", ctypes.c_int32)]
 
 
+class TacoAttentionBackwardArgs(ctypes.Structure):
+    """facppg_taco_attention_backward_args (include/facppg.h): twelve inputs, four outputs, all device pointers."""
+    _fields_ = [(n, ctypes.c_void_p) for n in (
+        "w_cat", "w_query", "v", "w_loc_dense", "w_loc_conv", "memory", "align", "tanh_s", "act_a", "c_a", "base_ctx", "base_ah",
+        "dgates_a", "dctx", "ds", "de")]
+
+
 class WnWeights(ctypes.Structure):
     """facppg_wn_weights (include/facppg.h)."""
     _fields_ = [("start_w", ctypes.c_void_p), ("start_b", ctypes.c_void_p),
@@ -168,6 +175,14 @@ def _declare(lib):
         "facppg_taco_decode_forced": (c.c_int, [vp, vp, vp, vp, vp, vp, u64, c.c_int, c.c_int, c.c_int, vp, vp, vp, vp, sz,
                                                 c.POINTER(TacoDecodeOpts), vp]),
         "facppg_taco_draw_dropout_forced": (c.c_int, [vp, vp, c.c_int, c.c_int, vp, vp]),
+        "facppg_taco_decode_forced_state": (c.c_int, [vp, vp, sz, c.c_int, c.c_int, vp, vp, vp, vp]),
+        "facppg_taco_encode_state": (c.c_int, [vp, vp, sz, c.c_int, c.c_int, vp, vp]),
+        "facppg_lstm_cell_scan": (c.c_int, [vp, vp, vp, c.c_int, c.c_int, c.c_int, vp]),
+        "facppg_lstm_backward_workspace_bytes": (sz, [c.c_int, c.c_int]),
+        "facppg_lstm_backward": (c.c_int, [vp, vp, vp, vp, vp, c.c_int, c.c_int, c.c_int, vp, vp, sz, vp]),
+        "facppg_taco_attention_backward_workspace_bytes": (sz, [c.POINTER(TacoConfig), c.c_int, c.c_int]),
+        "facppg_taco_attention_backward": (c.c_int, [c.POINTER(TacoConfig), c.POINTER(TacoAttentionBackwardArgs), c.c_int, c.c_int,
+                                                     c.c_int, vp, sz, vp]),
         "facppg_wg_draw_noise": (c.c_int, [vp, vp, c.c_int, c.c_int, vp, vp]),
         "facppg_taco_postnet": (c.c_int, [vp, vp, vp, c.c_int, c.c_int, c.c_int, vp, vp, sz, vp]),
         "facppg_mfcc_create": (c.c_int, [c.c_int, c.c_int, c.c_int, vp, vp, c.c_int, vp, c.c_int, c.c_int, vp, c.POINTER(vp)]),

@@ -1,8 +1,12 @@
-"""The parts of the reference's src/script/train_ppg2mel.py that need no backward pass: ``load_model`` (:113-119,
-imported by generate_synthesis.py:20), ``warm_start_model`` (:122-127) and ``validate`` (:152-177), which scores a
-checkpoint on held-out data through the teacher-forced ``Tacotron2.forward`` and ``Tacotron2Loss``.  ``train`` itself is
-not built: the kernels have no backward pass."""
+"""The reference's src/script/train_ppg2mel.py on the HIP kernels: ``load_model`` (:113-119, imported by
+generate_synthesis.py:20), ``warm_start_model`` (:122-127), ``load_checkpoint`` / ``save_checkpoint`` (:130-150),
+``validate`` (:152-177), which scores a checkpoint on held-out data through the teacher-forced ``Tacotron2.forward`` and
+``Tacotron2Loss``, and ``finetune``: the body of the training loop (:199-276) for one GPU with EVAL-MODE semantics, on the
+backward pass of ``Tacotron2.forward(..., differentiable=True)``.  ``train`` itself is not built: training-mode BatchNorm and
+the training-mode dropouts have no kernels."""
+import math
 import os
+import time
 
 import torch
 from torch.utils.data import DataLoader
@@ -26,6 +30,117 @@ def warm_start_model(checkpoint_path, model):
     weights = torch.load(checkpoint_path, map_location="cpu", weights_only=False)["state_dict"]
     model.load_state_dict(weights)                     # (drops the packed-weight handle: Tacotron2.load_state_dict)
     return model
+
+
+def load_checkpoint(checkpoint_path, model, optimizer):
+    """train_ppg2mel.py:130-140: -> (model, optimizer, learning_rate, iteration) from a file of ``save_checkpoint``."""
+    if not os.path.isfile(checkpoint_path):
+        raise FileNotFoundError("load_checkpoint: no checkpoint at %r" % (checkpoint_path,))
+    print("Loading checkpoint '{}'".format(checkpoint_path))
+    checkpoint_dict = torch.load(checkpoint_path, map_location="cpu", weights_only=False)
+    model.load_state_dict(checkpoint_dict["state_dict"])          # (drops the packed-weight handle)
+    optimizer.load_state_dict(checkpoint_dict["optimizer"])
+    learning_rate, iteration = checkpoint_dict["learning_rate"], checkpoint_dict["iteration"]
+    print("Loaded checkpoint '{}' from iteration {}".format(checkpoint_path, iteration))
+    return model, optimizer, learning_rate, iteration
+
+
+def save_checkpoint(model, optimizer, learning_rate, iteration, filepath):
+    """train_ppg2mel.py:143-149, the reference's file layout: iteration, state_dict, optimizer, learning_rate."""
+    print("Saving model and optimizer state at iteration {} to {}".format(iteration, filepath))
+    torch.save({"iteration": iteration, "state_dict": model.state_dict(), "optimizer": optimizer.state_dict(),
+                "learning_rate": learning_rate}, filepath)
+
+
+def finetune(model, hparams, trainset, collate_fn, steps, output_directory=None, valset=None, checkpoint_path=None,
+             warm_start=False, step_seeds=None, step_masks=None, optimizer=None, logger=None, log=print):
+    """Fit ``model`` to ``trainset`` for ``steps`` optimiser steps: the body of the reference's training loop
+    (train_ppg2mel.py:199-276) on one GPU -- Adam (``waveglow.optim.Adam``, one HIP launch per step) with
+    ``hparams.learning_rate`` / ``weight_decay``, zero_grad -> parse_batch -> forward -> Tacotron2Loss -> backward ->
+    clip_grad_norm_(``hparams.grad_clip_thresh``) -> step, and ``validate`` + a checkpoint ``checkpoint_<iteration>`` in
+    ``output_directory`` every ``hparams.iters_per_checkpoint`` iterations (when an output directory is given; ``validate``
+    when a ``valset`` is given).
+
+    THE MODEL STAYS IN EVAL MODE.  The gradient is that of the function ``Tacotron2.forward`` computes in eval mode, the one
+    ``validate`` reports the loss of: BatchNorm normalises with its RUNNING statistics, which are not updated (frozen
+    normalisation statistics; the BatchNorm weights and biases are trained), and the reference's training-mode dropouts -- 0.5
+    behind the encoder convolutions and the postnet layers, 0.1 on the LSTMCell states -- are OFF; the prenets' always-on
+    dropouts are on, as everywhere.  The reason is that training-mode semantics have no kernels: ``train()`` stays unbuilt.
+
+    trainset     any map-style data set of (ppg [L_in, n_symbols], acoustic [L_out, n_feat]) pairs; batches of
+                 ``hparams.batch_size`` are taken IN ORDER (no shuffling: a run is reproducible) through ``collate_fn``
+                 (``common.data_utils.ppg_acoustics_collate``), epoch after epoch
+    step_seeds   None, or a callable step -> seed of that step's dropout draws (``Tacotron2.forward(seed=...)``)
+    step_masks   None, or a callable step -> (enc masks, dec masks) as ``Tacotron2.forward(dropout_masks=...)`` takes them
+    checkpoint_path / warm_start   initialise from a checkpoint's weights (warm start) or resume it: weights, optimiser state,
+                 iteration (and its learning rate when ``hparams.use_saved_learning_rate``)
+    optimizer    None (built here) or the optimiser to use and resume into
+    Returns a dict: losses and grad_norms (pre-clip) per step, iteration (the next one), optimizer, learning_rate."""
+    from common.loss_function import Tacotron2Loss
+    from waveglow.optim import Adam
+    if hparams.fp16_run:
+        raise NotImplementedError("finetune: fp16_run is not built (README.md:53 of the reference: FP16 does not work)")
+    if any(not p.is_cuda for p in model.parameters()):
+        raise ValueError("finetune: the model must be on the GPU (there is no CPU path): load_model(hparams)")
+    if step_seeds is not None and step_masks is not None:
+        raise ValueError("finetune: step_seeds or step_masks, not both")
+    learning_rate = hparams.learning_rate
+    if optimizer is None:
+        optimizer = Adam(model.parameters(), lr=learning_rate, weight_decay=hparams.weight_decay)
+    criterion = Tacotron2Loss(hparams.mel_weight, hparams.gate_weight)
+    iteration = 0
+    if checkpoint_path:
+        if warm_start:
+            model = warm_start_model(checkpoint_path, model)
+        else:
+            model, optimizer, saved_lr, iteration = load_checkpoint(checkpoint_path, model, optimizer)
+            if hparams.use_saved_learning_rate:
+                learning_rate = saved_lr
+            iteration += 1                                        # next iteration is iteration + 1
+    if output_directory:
+        os.makedirs(output_directory, exist_ok=True)
+    batches = DataLoader(trainset, batch_size=hparams.batch_size, shuffle=False, collate_fn=collate_fn, num_workers=0)
+    if len(batches) == 0:
+        raise ValueError("finetune: the training set yields no batch")
+    model.eval()
+    losses, norms, done = [], [], 0
+    while done < steps:
+        for batch in batches:
+            if done == steps:
+                break
+            start = time.perf_counter()
+            for group in optimizer.param_groups:
+                group["lr"] = learning_rate
+            model.zero_grad()
+            x, y = model.parse_batch(batch)
+            kw = {}
+            if step_seeds is not None:
+                kw["seed"] = int(step_seeds(done))
+            if step_masks is not None:
+                kw["dropout_masks"] = step_masks(done)
+            loss = criterion(model(x, differentiable=True, **kw), y)
+            reduced_loss = loss.item()
+            loss.backward()
+            grad_norm = float(torch.nn.utils.clip_grad_norm_(model.parameters(), hparams.grad_clip_thresh))
+            optimizer.step()
+            # waveglow.optim.Adam's launch writes the parameters through raw pointers: no tensor version moves, so the packed-weight
+            # handle (facppg.lib.WeightIdentity) cannot see the step.  Drop it; the next forward packs the new weights.
+            model.invalidate_packed_weights()
+            losses.append(reduced_loss)
+            norms.append(grad_norm)
+            if not math.isnan(reduced_loss) and log is not None:
+                duration = time.perf_counter() - start
+                log("Train loss {} {:.6f} Grad Norm {:.6f} {:.2f}s/it".format(iteration, reduced_loss, grad_norm, duration))
+                if logger is not None:
+                    logger.log_training(reduced_loss, grad_norm, learning_rate, duration, iteration)
+            if output_directory and iteration % hparams.iters_per_checkpoint == 0:
+                if valset is not None:
+                    validate(model, criterion, valset, iteration, hparams.batch_size, 1, collate_fn, logger, False, 0)
+                    model.eval()                                  # (validate leaves train() mode, as the reference does)
+                save_checkpoint(model, optimizer, learning_rate, iteration, os.path.join(output_directory, "checkpoint_{}".format(iteration)))
+            iteration += 1
+            done += 1
+    return {"losses": losses, "grad_norms": norms, "iteration": iteration, "optimizer": optimizer, "learning_rate": learning_rate}
 
 
 def validate(model, criterion, valset, iteration, batch_size, n_gpus, collate_fn, logger, distributed_run, rank):
@@ -64,5 +179,6 @@ def validate(model, criterion, valset, iteration, batch_size, n_gpus, collate_fn
 
 
 def train(*args, **kwargs):
-    raise NotImplementedError("training the PPG->mel model is not built: the HIP kernels have no backward pass.  "
-                              "validate() scores a checkpoint through the teacher-forced forward pass")
+    raise NotImplementedError("train() is not built: training-mode semantics (batch-statistics BatchNorm, the training-mode "
+                              "dropouts) have no kernels.  finetune() fits a checkpoint with eval-mode semantics; validate() "
+                              "scores one through the teacher-forced forward pass")

@@ -570,6 +570,59 @@ int facppg_taco_decode_forced(const facppg_taco* h, const float* memory_dev, con
                               size_t workspace_bytes, facppg_taco_decode_opts* opts, void* stream);
 int facppg_taco_draw_dropout_forced(const facppg_taco* h, const uint64_t* seeds_dev, int B, int T_out,
                                     uint8_t* dec_masks_dev, void* stream);
+/* ---- the backward pass of the teacher-forced pass, eval mode (csrc/facppg_taco_bwd.hip): the recurrences.  The dense
+ * products around them (weight gradients, prenets, projection, postnet, encoder convolutions) are the caller's
+ * (common/taco_grad.py).  All tensors fp32, contiguous; LSTM gate order i, f, g, o as torch stores it.
+ *
+ * facppg_taco_decode_forced_state / facppg_taco_encode_state read what the forward calls left in THEIR workspace (pass the
+ *   very workspace, before anything else writes to it): ah_dev [B][T_out][attention_rnn_dim] and dh_dev
+ *   [B][T_out][decoder_rnn_dim], the hidden states of the two LSTMCells of every frame (model.py:401, 427), and the prenet
+ *   masks the call drew from its seed (masks_dev NULL: not wanted; only meaningful if the forward call got masks_dev = NULL).
+ *   Saving them costs (attention_rnn_dim + decoder_rnn_dim) * 4 = 2.4 KB per utterance and frame at the reference's widths,
+ *   next to the forward's 26.8 KB.
+ * facppg_lstm_cell_scan: gates_dev [N][T][4H] holds the gate pre-activations of every frame (a GEMM on the saved hidden
+ *   states) and receives the activations; c_dev [N][T][H] the cell states (zero initial state, nn.LSTMCell / nn.LSTM).
+ *   lengths_dev NULL or [N]: frames at or beyond an utterance's length are zero (pack_padded_sequence, model.py:226).
+ * facppg_lstm_backward: the backward chain of one LSTM, t = T-1 .. 0: dh(t) = dh_seed[n][t] + W_hh^T dgates(t+1), the
+ *   cell's pointwise backward, dgates_dev [N][T][4H] (pre-activation gradients; zero beyond the length).  w_hh_dev [4H][H].
+ *   Used for decoder_rnn (model.py:427-428; its chain needs nothing of the attention's) and for each direction of the
+ *   encoder's BiLSTM (model.py:229-230; the reverse direction on time-reversed utterances).  4H <= 8192.
+ *   Workspace: facppg_lstm_backward_workspace_bytes(N, H).
+ * facppg_taco_attention_backward: the attention chain of Decoder.decode (model.py:400-424, Attention.forward 100-121,
+ *   get_alignment_energies 78-98, LocationLayer 56-60), t = T_out-1 .. 0; see the argument struct.  Masked positions
+ *   carry weight 0 and get gradient 0, whatever the window rule was.  Workspace:
+ *   facppg_taco_attention_backward_workspace_bytes(config, B, Tin) (0 for a NULL config).
+ * One launch per frame and kernel in stream order, no atomics: two runs give the same bits. */
+typedef struct {
+  const float* w_cat;       /* [4A][E + A]: attention_rnn.weight_ih[:, prenet_dim:] | attention_rnn.weight_hh */
+  const float* w_query;     /* [AD][A] query_layer */
+  const float* v;           /* [AD] */
+  const float* w_loc_dense; /* [AD][NFIL] */
+  const float* w_loc_conv;  /* [NFIL][2][KSZ] */
+  const float* memory;      /* [B][Tin][E] */
+  const float* align;       /* [B][T_out][Tin] attention weights of the forward pass */
+  const float* tanh_s;      /* [B][T_out][Tin][AD] tanh(processed_query + processed_attention_weights + processed_memory) */
+  const float* act_a;       /* [B][T_out][4A], c_a [B][T_out][A]: facppg_lstm_cell_scan of the attention LSTM */
+  const float* c_a;
+  const float* base_ctx;    /* [B][T_out][E]: d loss / d ctx(t) through the projection and the decoder LSTM's input */
+  const float* base_ah;     /* [B][T_out][A]: d loss / d ah(t) through the decoder LSTM's input */
+  float* dgates_a;          /* out [B][T_out][4A] */
+  float* dctx;              /* out [B][T_out][E] total adjoint of the attention context */
+  float* ds;                /* out [B][T_out][Tin][AD] adjoint of tanh's argument */
+  float* de;                /* out [B][T_out][Tin] adjoint of the energies */
+} facppg_taco_attention_backward_args;
+int facppg_taco_decode_forced_state(const facppg_taco* h, const void* workspace_dev, size_t workspace_bytes, int B,
+                                    int T_out, float* ah_dev, float* dh_dev, uint8_t* masks_dev, void* stream);
+int facppg_taco_encode_state(const facppg_taco* h, const void* workspace_dev, size_t workspace_bytes, int B, int Tin,
+                             uint8_t* masks_dev, void* stream);
+int facppg_lstm_cell_scan(float* gates_dev, float* c_dev, const int32_t* lengths_dev, int N, int T, int H, void* stream);
+size_t facppg_lstm_backward_workspace_bytes(int N, int H);
+int facppg_lstm_backward(const float* w_hh_dev, const float* act_dev, const float* c_dev, const float* dh_seed_dev,
+                         const int32_t* lengths_dev, int N, int T, int H, float* dgates_dev, void* workspace_dev,
+                         size_t workspace_bytes, void* stream);
+size_t facppg_taco_attention_backward_workspace_bytes(const facppg_taco_config* config, int B, int Tin);
+int facppg_taco_attention_backward(const facppg_taco_config* config, const facppg_taco_attention_backward_args* args,
+                                   int B, int Tin, int T_out, void* workspace_dev, size_t workspace_bytes, void* stream);
 /* The always-on p=0.5 dropout draws of both prenets (Prenet.forward, model.py:132-135) as PER-UTTERANCE
  * streams keyed by seeds_dev[b] (uint64 [B]): enc_masks_dev uint8 [2][B][symbols_embedding_dim][Tin] and
  * dec_masks_dev uint8 [max_steps][2][B][prenet_dim] in the layouts facppg_taco_encode / _decode accept
