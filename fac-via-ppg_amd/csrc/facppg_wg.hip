@@ -354,6 +354,17 @@ struct WnArgs {
   // k_cond_seed (this layer's slice of its buffer), and the K loop is the convolution chunks alone
   const float4* seed;  // [P][seed_nt][8 waves][2 row blocks][4][64 lanes]
   int seed_nt;         // 32-frame tiles per phase in that buffer
+  // fused flow edge (LAST tiles of one short utterance, wn_edge_tile): the tile runs k_flow_end's folded branch for its own
+  // columns.  fe_mode = 0: off (the edge is a launch of its own), else 2 * n_half + (1 if the flow prepends early noise)
+  int fe_mode, fe_swap, fe_swap_next, fe_L, fe_La;
+  float fe_sigma;
+  const float* fe_aud_in;    // [8][La]
+  float* fe_aud_out;         // [8][La]
+  const float* fe_z_early;   // [2][L] or null
+  const float* fe_winv;      // [2H][2H]
+  const float* fe_start_w;   // next flow: [256][Hn]
+  const float* fe_start_b;   // [256]
+  float* fe_xa_out;          // [8][Lp]
 };
 
 typedef float f4u __attribute__((ext_vector_type(4), aligned(4)));   // 16-byte access at 4-byte alignment
@@ -863,19 +874,28 @@ __global__ __launch_bounds__(256, 2) void k_wn_layer(WnArgs p) {
   }
 }
 
-// FACPPG_WN8_PROF: phase stamps of k_wn_layer8 (workgroup 0, thread 0; clock64 ticks summed over launches), read back with
-// facppg_debug_wn8_prof -- where a narrow launch spends its time outside the K loop (tools/prof_wn8.py)
+// FACPPG_WN8_PROF: phase stamps of the 8-wave layer tiles (wn_layer8_tile and wn_layer16_tile; thread 0 of one workgroup per
+// launch and tile kind; ticks of the constant 100 MHz clock summed over launches), by tile kind and by the layer's place in
+// its flow, read back with facppg_debug_wn_prof -- where a small launch spends its time outside the K loop
+// (tools/prof_wn8.py).  A profiling build only: the stamps drain the memory queue at the end of the prologue and of the
+// epilogue, so that the operand (seed) round trip and the stores' issue are counted where they belong.
 #ifdef FACPPG_WN8_PROF
-__device__ unsigned long long g_wn8_prof[12];   // 0-5 phases, 6 launches
-#define WN8_STAMP_DECL long long wn8_t = clock64()
+// [tile kind: 0 = 32-frame tile (workgroup 0), 1 = 16-frame tile (the first one of phase 0)][first, middle, last layer]
+// [0-5: prologue, K loop, gate, second GEMM, end rows, epilogue; 6: fused flow edge; 7: launches]
+__device__ unsigned long long g_wn_prof[2][3][8];
+#define WN8_STAMP_DECL(TK, ON, KIND)                                  \
+  long long wn8_t = wall_clock64();                                   \
+  const bool wn8_on = (ON) && threadIdx.x == 0;                       \
+  unsigned long long* const wn8_slot = g_wn_prof[TK][KIND]
 #define WN8_STAMP(i)                                                                           \
   do {                                                                                         \
-    const long long now__ = clock64();                                                         \
-    if (blockIdx.x == 0 && threadIdx.x == 0) { atomicAdd(&g_wn8_prof[i], (unsigned long long)(now__ - wn8_t)); if ((i) == 5) atomicAdd(&g_wn8_prof[6], 1ull); } \
+    if ((i) == 0 || (i) == 5) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");                 \
+    const long long now__ = wall_clock64();                                                    \
+    if (wn8_on) { atomicAdd(&wn8_slot[i], (unsigned long long)(now__ - wn8_t)); if ((i) == 5) atomicAdd(&wn8_slot[7], 1ull); } \
     wn8_t = now__;                                                                             \
   } while (0)
 #else
-#define WN8_STAMP_DECL
+#define WN8_STAMP_DECL(TK, ON, KIND)
 #define WN8_STAMP(i)
 #endif
 
@@ -909,11 +929,109 @@ __device__ __forceinline__ void store_f4(float* g, const float4 v) {
 }
 __device__ __forceinline__ void store_f1(float* g, const float v) { *(__attribute__((address_space(1))) float*)g = v; }
 
+// ------------------------------------------------------------------------------------------
+// wn_edge_tile: the flow edge of one LAST tile's own columns (one short utterance: B = 1), in place of a k_flow_end<QS>
+// launch that is a latency chain alone on the chip.  The tile's final end rows are in LDS (fin[8][TW], written by the
+// threads that added them into `skip`); one thread per column runs k_flow_end's folded branch on them -- the same
+// operations in the same order, hence the same bits -- and leaves the next flow's conditioning channels in LDS, from
+// where all eight waves form the start conv (32 channels each, the fmaf chain of start_conv) as 16-byte row segments.
+// The start-conv rows go to p.h_out, NOT to the buffer the layer reads (where the separate launch puts them, after the
+// whole layer has ended): neighbouring tiles still read these columns of h_in through their dilated taps.
+// ------------------------------------------------------------------------------------------
+template <int H, bool EARLY, int TW>
+__device__ __forceinline__ void wn_edge_column(const WnArgs& p, const int ph, const int x, const int col, float* __restrict__ smem) {
+  constexpr int CC = 2 * H, CN = EARLY ? CC + 2 : CC, HN = CN / 2;
+  const int pos = x * p.P + ph;
+  float a[CC], y[CN], o[CC];
+#pragma unroll
+  for (int j = 0; j < CC; ++j) a[j] = gld(p.fe_aud_in + (size_t)j * p.fe_La + pos);
+  if constexpr (EARLY) {
+#pragma unroll
+    for (int j = 0; j < 2; ++j) y[j] = p.fe_sigma * gld(p.fe_z_early + (size_t)j * p.fe_L + pos);
+  }
+#pragma unroll
+  for (int j = 0; j < CC; ++j) o[j] = smem[j * TW + col];
+#pragma unroll
+  for (int j = 0; j < H; ++j) {   // the transformed half: the second one, or (legacy layout, odd flows) the first
+    const float t = ((p.fe_swap ? a[j] : a[H + j]) - o[j]) / expf(o[H + j]);
+    if (p.fe_swap) a[j] = t;
+    else a[H + j] = t;
+  }
+#pragma unroll
+  for (int i = 0; i < CC; ++i) {
+    float v = 0.0f;
+#pragma unroll
+    for (int j = 0; j < CC; ++j) v = fmaf(p.fe_winv[i * CC + j], a[j], v);
+    y[(EARLY ? 2 : 0) + i] = v;
+  }
+#pragma unroll
+  for (int j = 0; j < CN; ++j) store_f1(p.fe_aud_out + (size_t)j * p.fe_La + pos, y[j]);
+  float* xd = p.fe_xa_out + ph * p.Tqp + HQ + x;
+#pragma unroll
+  for (int j = 0; j < 8; ++j) {
+    const float a0 = j < HN ? (p.fe_swap_next ? y[HN + (j < HN ? j : 0)] : y[j < HN ? j : 0]) : j == HN ? 1.0f : 0.0f;
+    store_f1(xd + (size_t)j * p.Lp, a0);
+    if (j < HN) smem[(8 + j) * TW + col] = a0;
+  }
+}
+
+// q0: the tile's first frame, ncol: its live columns.  Every thread of the tile calls this (two barriers inside).
+template <int TW>
+__device__ __forceinline__ void wn_edge_tile(const WnArgs& p, const int ph, const int q0, const int ncol, float* __restrict__ smem) {
+  const int tid = threadIdx.x, lane = tid & 63, w8 = tid >> 6;
+  const int hn = (p.fe_mode >> 1) + (p.fe_mode & 1);   // conditioning channels of the NEXT flow
+  constexpr int F4 = TW / 4, RP = 64 / F4, NPASS = 32 / RP;
+  const int srow = lane / F4, col4 = (lane % F4) * 4;
+  // this thread's start-conv operands, requested ahead of the column chain
+  float sb[NPASS], sw[NPASS][4];
+#pragma unroll
+  for (int i = 0; i < NPASS; ++i) {
+    const int ch = 32 * w8 + i * RP + srow;
+    sb[i] = gld(p.fe_start_b + ch);
+#pragma unroll
+    for (int j = 0; j < 4; ++j) sw[i][j] = j < hn ? gld(p.fe_start_w + ch * hn + j) : 0.0f;
+  }
+  __syncthreads();   // fin is complete
+  if (tid < ncol) {
+    const int x = q0 + tid;
+    switch (p.fe_mode) {
+      case 2: wn_edge_column<1, false, TW>(p, ph, x, tid, smem); break;
+      case 3: wn_edge_column<1, true, TW>(p, ph, x, tid, smem); break;
+      case 4: wn_edge_column<2, false, TW>(p, ph, x, tid, smem); break;
+      case 5: wn_edge_column<2, true, TW>(p, ph, x, tid, smem); break;
+      case 6: wn_edge_column<3, false, TW>(p, ph, x, tid, smem); break;
+      case 7: wn_edge_column<3, true, TW>(p, ph, x, tid, smem); break;
+      default: wn_edge_column<4, false, TW>(p, ph, x, tid, smem); break;
+    }
+  }
+  __syncthreads();   // the conditioning channels a0[hn][TW] are in LDS behind fin
+  const int nv = ncol - col4;
+  if (nv <= 0) return;
+  float* hd = p.h_out + ph * p.Tqp + HQ + q0 + col4;
+#pragma unroll
+  for (int i = 0; i < NPASS; ++i) {
+    const int ch = 32 * w8 + i * RP + srow;
+    float v[4] = {sb[i], sb[i], sb[i], sb[i]};
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      if (j < hn) {
+        const float4 a0 = *reinterpret_cast<const float4*>(smem + (8 + j) * TW + col4);
+        v[0] = fmaf(sw[i][j], a0.x, v[0]); v[1] = fmaf(sw[i][j], a0.y, v[1]);
+        v[2] = fmaf(sw[i][j], a0.z, v[2]); v[3] = fmaf(sw[i][j], a0.w, v[3]);
+      }
+    }
+    float* g = hd + (size_t)ch * p.Lp;
+    if (nv >= 4) store_f4(g, make_float4(v[0], v[1], v[2], v[3]));
+    else
+      for (int k = 0; k < nv; ++k) store_f1(g + k, v[k]);
+  }
+}
+
 template <bool LAST, int NCB, bool EF, bool SEED = false>
 __device__ __forceinline__ void wn_layer8_tile(const WnArgs& p, const int lin, float* __restrict__ smem) {
   static_assert(!SEED || NCB == 1, "seeded tiles: 32 frames");
   constexpr int TNt = 32 * NCB;
-  WN8_STAMP_DECL;
+  WN8_STAMP_DECL(0, blockIdx.x == 0, p.first ? 0 : LAST ? 2 : 1);
   const int tid = threadIdx.x, lane = tid & 63, w8 = tid >> 6, wq = w8 >> 1, sub = w8 & 1;
   const int li = lane & 31, kh = lane >> 5;
   const int chb = wq * 64 + sub * 32;   // first channel of this wave's block
@@ -1167,15 +1285,29 @@ __device__ __forceinline__ void wn_layer8_tile(const WnArgs& p, const int lin, f
       float* g = p.skip + ((size_t)b * 8 + row) * p.Lr + sk_off;
       const float bias = p.endb[row];
       const float vv[4] = {v4.x, v4.y, v4.z, v4.w};
+      float fs[4] = {0.0f, 0.0f, 0.0f, 0.0f};
       if (nvalid >= 4) {
         float4 x = make_float4(bias, bias, bias, bias);
         if (!p.first) x = *reinterpret_cast<const float4*>(g);
-        store_f4(g, make_float4(x.x + vv[0], x.y + vv[1], x.z + vv[2], x.w + vv[3]));
+        fs[0] = x.x + vv[0]; fs[1] = x.y + vv[1]; fs[2] = x.z + vv[2]; fs[3] = x.w + vv[3];
+        store_f4(g, make_float4(fs[0], fs[1], fs[2], fs[3]));
       } else {
-        for (int k = 0; k < nvalid; ++k) store_f1(g + k, (p.first ? bias : g[k]) + vv[k]);
+#pragma unroll
+        for (int k = 0; k < 3; ++k)
+          if (k < nvalid) { fs[k] = (p.first ? bias : g[k]) + vv[k]; store_f1(g + k, fs[k]); }
+      }
+      if constexpr (LAST && ESPLIT) {   // fused flow edge: the final rows go on to the column threads (the gate image is dead)
+        if (p.fe_mode) *reinterpret_cast<float4*>(smem + row * TNt + scol4) = make_float4(fs[0], fs[1], fs[2], fs[3]);
       }
     }
   }
+  if constexpr (LAST && ESPLIT) {
+    if (p.fe_mode) {   // (B = 1: the tile's first frame follows from its index alone)
+      const int q0 = (p.flat_cols > 0 ? tile : tile % p.ntq) * TNt;
+      wn_edge_tile<TNt>(p, ph, q0, min(TNt, (p.t_valid ? p.t_valid[0] : p.T) - q0), smem);
+    }
+  }
+  WN8_STAMP(6);   // fused flow edge (with the add into skip)
   float* slab = smem + w8 * (32 * TNt);
 #pragma unroll
   for (int half = 0; half < NRB2; ++half) {
@@ -1416,12 +1548,14 @@ constexpr int TN16 = 16;
 
 // one 16-frame tile: phase ph, frames q0 .. q0 + 15 of utterance b
 template <bool LAST, bool EF>
-__device__ __forceinline__ void wn_layer16_tile(const WnArgs& p, const int ph, const int b, const int q0, float* __restrict__ smem) {
+__device__ __forceinline__ void wn_layer16_tile(const WnArgs& p, const int ph, const int b, const int q0, float* __restrict__ smem,
+                                                const bool stamp = false) {   // stamp: FACPPG_WN8_PROF builds, this workgroup reports
   const int tid = threadIdx.x, lane = tid & 63, w8 = tid >> 6;
   const int pl = lane & 15, kq = lane >> 4;
   const int chb = w8 * 32;
   const int nvalid = (p.t_valid ? p.t_valid[b] : p.T) - q0;
   if (nvalid <= 0) return;
+  WN8_STAMP_DECL(1, stamp, p.first ? 0 : LAST ? 2 : 1);
   const int in_off = ph * p.Tqp + HQ + q0, sk_off = ph * p.Tr + q0;
   int tapo[3];
 #pragma unroll
@@ -1479,6 +1613,7 @@ __device__ __forceinline__ void wn_layer16_tile(const WnArgs& p, const int ph, c
   }
   stage_write(0);
   __syncthreads();
+  WN8_STAMP(0);   // prologue
   for (int c = 0; c < nch; ++c) {
     stage_load(c + 1 < nch ? c + 1 : c);
     const float* lb = smem + (c & 1) * (KCH * TN16) + (kq * TN16 + pl) * 4;
@@ -1499,6 +1634,7 @@ __device__ __forceinline__ void wn_layer16_tile(const WnArgs& p, const int ph, c
     stage_write((c + 1) & 1);
     __syncthreads();
   }
+  WN8_STAMP(1);   // K loop
   // gate -> LDS [256][16]
 #pragma unroll
   for (int rbl = 0; rbl < 2; ++rbl)
@@ -1506,6 +1642,7 @@ __device__ __forceinline__ void wn_layer16_tile(const WnArgs& p, const int ph, c
     for (int r = 0; r < 4; ++r)   // channel chb + 16 rbl + 4 kq + r into the same [group][kq][column][s] image
       smem[(((2 * w8 + rbl) * 4 + 2 * (r & 1) + (kq & 1)) * TN16 + pl) * 4 + 2 * (kq >> 1) + ((r >> 1) & 1)] = gate_tanh_sigmoid(acc[rbl][r], acc[rbl + 2][r]);
   __syncthreads();
+  WN8_STAMP(2);   // gate
   // res_skip 1x1 conv: blocks rbl 0,1 = res rows chb.., rbl 2,3 = skip rows 256+chb.. (LAST: rbl 0,1 = skip rows chb..)
   constexpr int NB2 = EF ? (LAST ? 0 : 2) : LAST ? 2 : 4;   // EF: res rows only (image laid out like a LAST layer's 256 rows)
   constexpr bool ROWS256 = LAST || EF;
@@ -1549,6 +1686,7 @@ __device__ __forceinline__ void wn_layer16_tile(const WnArgs& p, const int ph, c
       }
     }
   }
+  WN8_STAMP(3);   // second GEMM
   if constexpr (EF) {
     // end rows (see k_wn_layer<EF>): wave w8 forms K slice w8 of the single 16-column block; the slices meet in LDS
     // and are summed in slice order below -- the same sums, in the same order, as the wider tiles
@@ -1568,6 +1706,7 @@ __device__ __forceinline__ void wn_layer16_tile(const WnArgs& p, const int ph, c
   }
   // epilogue through a private [32][16] LDS slab per wave, 16-byte row segments to HBM
   __syncthreads();
+  WN8_STAMP(4);   // end rows
   if constexpr (EF) {
     if (tid < 32) {
       const int row = tid >> 2, c4 = (tid & 3) * 4, nv = nvalid - c4;
@@ -1582,16 +1721,27 @@ __device__ __forceinline__ void wn_layer16_tile(const WnArgs& p, const int ph, c
         float* g = p.skip + ((size_t)b * 8 + row) * p.Lr + sk_off + c4;
         const float bias = p.endb[row];
         const float vv[4] = {t.x, t.y, t.z, t.w};
+        float fs[4] = {0.0f, 0.0f, 0.0f, 0.0f};
         if (nv >= 4) {
           float4 x = make_float4(bias, bias, bias, bias);
           if (!p.first) x = *reinterpret_cast<const float4*>(g);
-          *reinterpret_cast<float4*>(g) = make_float4(x.x + vv[0], x.y + vv[1], x.z + vv[2], x.w + vv[3]);
+          fs[0] = x.x + vv[0]; fs[1] = x.y + vv[1]; fs[2] = x.z + vv[2]; fs[3] = x.w + vv[3];
+          store_f4(g, make_float4(fs[0], fs[1], fs[2], fs[3]));
         } else {
-          for (int k = 0; k < nv; ++k) g[k] = (p.first ? bias : g[k]) + vv[k];
+#pragma unroll
+          for (int k = 0; k < 3; ++k)
+            if (k < nv) { fs[k] = (p.first ? bias : g[k]) + vv[k]; g[k] = fs[k]; }
+        }
+        if constexpr (LAST) {   // fused flow edge: the final rows go on to the column threads (the gate image is dead)
+          if (p.fe_mode) *reinterpret_cast<float4*>(smem + row * TN16 + c4) = make_float4(fs[0], fs[1], fs[2], fs[3]);
         }
       }
     }
+    if constexpr (LAST) {
+      if (p.fe_mode) wn_edge_tile<TN16>(p, ph, q0, min(TN16, nvalid), smem);
+    }
   }
+  WN8_STAMP(6);   // fused flow edge (with the add into skip)
   float* slab = smem + w8 * (32 * TN16);
   const int erow = lane >> 2, ecol = (lane & 3) * 4;   // 16 rows x 4 float4 per pass, two passes
 #pragma unroll
@@ -1619,13 +1769,14 @@ __device__ __forceinline__ void wn_layer16_tile(const WnArgs& p, const int ph, c
           else x = *reinterpret_cast<const float4*>(rbase + o);
           v.x += x.x; v.y += x.y; v.z += x.z; v.w += x.w;
         }
-        *reinterpret_cast<float4*>(gbase + o) = v;
+        store_f4(gbase + o, v);
       } else {
         const float vv[4] = {v.x, v.y, v.z, v.w};
         for (int k = 0; k < nv; ++k) gbase[o + k] = vv[k] + (add ? rbase[o + k] : 0.0f);
       }
     }
   }
+  WN8_STAMP(5);   // epilogue
 }
 
 template <bool LAST, bool EF = false>
@@ -1638,7 +1789,7 @@ __global__ __launch_bounds__(512, 4) void k_wn_layer16(WnArgs p) {
     else { ph = lin / p.nt; tile = lin % p.nt; }
     if (ph >= p.P) return;
   }
-  wn_layer16_tile<LAST, EF>(p, ph, tile / p.ntq, (tile % p.ntq) * TN16, smem);
+  wn_layer16_tile<LAST, EF>(p, ph, tile / p.ntq, (tile % p.ntq) * TN16, smem, ph == 0 && tile == 0);
 }
 
 // ------------------------------------------------------------------------------------------
@@ -1658,7 +1809,7 @@ __global__ __launch_bounds__(512, 4) void k_wn_layer_mixed(WnArgs p32, WnArgs p1
   else { ph = lin / nt; tile = lin % nt; }
   if (ph >= p32.P) return;
   if (tile < n32) wn_layer8_tile<LAST, 1, true, true>(p32, lin, smem);
-  else wn_layer16_tile<LAST, true>(p16, ph, 0, 32 * n32 + (tile - n32) * TN16, smem);
+  else wn_layer16_tile<LAST, true>(p16, ph, 0, 32 * n32 + (tile - n32) * TN16, smem, ph == 0 && tile == n32);
 }
 
 // ------------------------------------------------------------------------------------------
@@ -2524,11 +2675,12 @@ extern "C" size_t facppg_wg_workspace_bytes(const facppg_wg* h, int B, int T) {
 }
 
 #ifdef FACPPG_WN8_PROF
-extern "C" int facppg_debug_wn8_prof(unsigned long long* out12, int reset) {
-  FACPPG_HIP_CHECK(hipMemcpyFromSymbol(out12, HIP_SYMBOL(g_wn8_prof), 12 * sizeof(unsigned long long)));
+extern "C" int facppg_debug_wn_prof(unsigned long long* out48, int reset) {
+  FACPPG_HIP_CHECK(hipMemcpyFromSymbol(out48, HIP_SYMBOL(g_wn_prof), 48 * sizeof(unsigned long long)));
   if (reset) {
-    unsigned long long z[12] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
-    FACPPG_HIP_CHECK(hipMemcpyToSymbol(HIP_SYMBOL(g_wn8_prof), z, sizeof(z)));
+    unsigned long long z[48];
+    memset(z, 0, sizeof(z));
+    FACPPG_HIP_CHECK(hipMemcpyToSymbol(HIP_SYMBOL(g_wn_prof), z, sizeof(z)));
   }
   return FACPPG_OK;
 }
@@ -2726,11 +2878,35 @@ static int wg_infer_pm(facppg_wg* h, const float* mel_dev, const int32_t* T_vali
   h->last_tile = tn; h->last_tiles = (int)lgrid;
   h->last_waves = (wide128 || tile16 || (narrow && w8mode != 0) || (!narrow && w8mode == 2)) ? 8 : 4;
   h->ev_layers = c.wn_layers;
+  // One short utterance on 16-frame or 8-wave 32-frame tiles (where the edge launch would take k_flow_end's QS shape): the
+  // LAST layer's tiles run the inner flow edges themselves (wn_edge_tile).  FACPPG_WG_EDGE_FUSE=0: the separate launches.
+  const char* fuse_env = getenv("FACPPG_WG_EDGE_FUSE");   // (read per call: the tests flip it)
+  const bool fuse = fold && fqs && B == 1 && (tile16 || (narrow && w8mode != 0)) && (!fuse_env || atoi(fuse_env) != 0);
   for (int k = nf - 1; k >= 0; --k) {
     // (streamed utterance: the seeds of this flow come from a pass that may still be running on another stream)
     if (flow_events && flow_events[k]) FACPPG_HIP_CHECK(hipStreamWaitEvent(s, (hipEvent_t)flow_events[k], 0));
+    e.aud_in = aud[ai]; e.aud_out = aud[ai ^ 1];
+    e.end_w = h->end_w[k]; e.end_b = h->end_b[k]; e.winv = h->winv[k];
+    e.final_flow = (k == 0);
+    e.swap = c.alternate_halves && (k & 1);
+    e.swap_next = c.alternate_halves && k > 0 && ((k - 1) & 1);
+    e.z_early = nullptr;
+    if (h->early[k]) { e.z_early = z + z_off; z_off += (size_t)B * c.n_early_size * w.L; }
+    if (k > 0) { e.start_w = h->start_w[k - 1]; e.start_b = h->start_b[k - 1]; }
+    const int cn = 2 * h->n_half[k] + (h->early[k] ? 2 : 0);
+    if (k > 0) FACPPG_REQUIRE(cn == 2 * h->n_half[k - 1], FACPPG_EUNSUPPORTED, "flow %d channel mismatch", k);
+    else FACPPG_REQUIRE(cn == 8, FACPPG_EUNSUPPORTED, "final flow must yield n_group channels");
+    FACPPG_REQUIRE(h->n_half[k] >= 1 && h->n_half[k] <= 4, FACPPG_EUNSUPPORTED, "n_half %d", h->n_half[k]);
+    const bool fuse_k = fuse && k > 0;   // the final flow's edge (interleaved audio) stays a launch
     for (int i = 0; i < c.wn_layers; ++i) {
       a.h_in = hbuf[hi]; a.h_out = hbuf[hi ^ 1];
+      a.fe_mode = 0;
+      if (fuse_k && i == c.wn_layers - 1) {
+        a.fe_mode = 2 * h->n_half[k] + (h->early[k] ? 1 : 0);
+        a.fe_swap = e.swap; a.fe_swap_next = e.swap_next; a.fe_L = w.L; a.fe_La = w.La; a.fe_sigma = sigma;
+        a.fe_aud_in = e.aud_in; a.fe_aud_out = e.aud_out; a.fe_z_early = e.z_early; a.fe_winv = e.winv;
+        a.fe_start_w = e.start_w; a.fe_start_b = e.start_b; a.fe_xa_out = xa;
+      }
       a.w1 = h->w1pm[k][i]; a.wc = h->wcpm[k][i]; a.b1 = h->b1pm[k][i]; a.w2 = h->w2[k][i]; a.b2 = h->b2[k][i];
       if (tile16) { a.w1 = h->w1_16[k][i]; a.wc = h->wc_16[k][i]; a.w2 = h->w2_16[k][i]; }
       a.dil = 1 << i; a.first = (i == 0);
@@ -2778,17 +2954,12 @@ static int wg_infer_pm(facppg_wg* h, const float* mel_dev, const int32_t* T_vali
       if (!last) hi ^= 1;
       if (h->profiling && last) FACPPG_HIP_CHECK(hipEventRecord(h->ev[h->ev_used++], s));
     }
-    e.aud_in = aud[ai]; e.aud_out = aud[ai ^ 1]; e.h_out = hbuf[hi];
-    e.end_w = h->end_w[k]; e.end_b = h->end_b[k]; e.winv = h->winv[k];
-    e.final_flow = (k == 0);
-    e.swap = c.alternate_halves && (k & 1);
-    e.swap_next = c.alternate_halves && k > 0 && ((k - 1) & 1);
-    e.z_early = nullptr;
-    if (h->early[k]) { e.z_early = z + z_off; z_off += (size_t)B * c.n_early_size * w.L; }
-    if (k > 0) { e.start_w = h->start_w[k - 1]; e.start_b = h->start_b[k - 1]; }
-    const int cn = 2 * h->n_half[k] + (h->early[k] ? 2 : 0);
-    if (k > 0) FACPPG_REQUIRE(cn == 2 * h->n_half[k - 1], FACPPG_EUNSUPPORTED, "flow %d channel mismatch", k);
-    else FACPPG_REQUIRE(cn == 8, FACPPG_EUNSUPPORTED, "final flow must yield n_group channels");
+    if (fuse_k) {
+      // the last layer's tiles ran the edge and left the next flow's start-conv rows in the buffer they did not read
+      hi ^= 1; ai ^= 1;
+      continue;
+    }
+    e.h_out = hbuf[hi];
     switch (h->n_half[k]) {
       case 1: launch_flow_end<1>(h->early[k], fqs, fgrid, s, e); break;
       case 2: launch_flow_end<2>(h->early[k], fqs, fgrid, s, e); break;
