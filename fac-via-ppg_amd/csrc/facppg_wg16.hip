@@ -20,8 +20,8 @@
 //   skip  [B][8][P][Tr]    fp32   end rows of the flow, running over its layers (folded end conv + bias)
 //   aud   [B][8][L]        fp32   flow variable, natural position order (L = T*P)
 //
-// Kernels: k16_mel_pad, k16_noise, k16_begin (sigma*z, start conv of the last flow), k16_wn_layer<LAST, NCB> (one
-// fused WN layer per launch), k16_flow_end (affine inverse, W^-1, early z, next start conv or the final interleave).
+// Kernels: k16_mel_pad, k16_mel_cvt, k16_noise, k16_begin (sigma*z, start conv of the last flow), k16_wn_layer<LAST, NCB, SEED>
+// (one fused WN layer per launch), k16_cond_seed (the conditioning chunks of every layer ahead of time), k16_flow_end (affine inverse, W^-1, early z, next start conv or the final interleave).
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -34,6 +34,7 @@
 typedef _Float16 h16x8 __attribute__((ext_vector_type(8)));
 typedef _Float16 h16x4 __attribute__((ext_vector_type(4)));
 typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
+typedef float f32x4v __attribute__((ext_vector_type(4)));
 
 namespace facppg {
 
@@ -170,7 +171,9 @@ __global__ void k16_noise(_Float16* __restrict__ z, size_t n, uint64_t seed) {
 //   end rows:  wave w multiplies its own 32 channels by the folded end rows (32-row padded A), the eight partials are
 //              summed in wave order and added to the running skip rows (first layer: + the folded end bias)
 // Every output column is computed the same way in every tile width (same K order, same wave-order sum), so an utterance
-// gets the same bits in any batch and any tile width.
+// gets the same bits in any batch and any tile width.  The K order is a run-time argument (cond_first): taps then conditioning
+// (the default), or conditioning first -- the order in which a tile may start from k16_cond_seed's accumulators instead of
+// running the conditioning chunks itself (SEED launches, 32-frame tiles: seeded or not, a column gets the same bits).
 // ------------------------------------------------------------------------------------------
 struct Wn16Args {
   const _Float16* h_in;
@@ -182,13 +185,17 @@ struct Wn16Args {
   const float *b1, *b2, *endb;
   const int* t_valid;
   int T, P, Tr, Tqp, dil, first, nconv, ncond, kc;
+  int cond_first;        // K order: 0 = taps, then conditioning (the default); 1 = conditioning first (what a seed can stand for)
+  const float4* seeds;   // SEED launches: this (flow, layer)'s [P][seed_nt][8 waves][2][4][64 lanes] accumulators (k16_cond_seed)
+  int seed_nt, seed_tiles;   // tiles per phase row of the seed buffer; tiles [0, seed_tiles) of the launch start from their seeds
 };
 
 template <int NCB>
 constexpr int wn16_lds_bytes() { return 32 * NCB * (ZP + 2 * SP) * 2; }
 
-template <bool LAST, int NCB>
+template <bool LAST, int NCB, bool SEED = false>
 __global__ __launch_bounds__(512, 1) void k16_wn_layer(Wn16Args p) {
+  static_assert(!SEED || NCB == 1, "seeds are kept per 32-frame tile");
   constexpr int TW = 32 * NCB;
   constexpr int NV = (8 * TW + 511) / 512;   // staged 16-byte vectors per thread and chunk
   extern __shared__ __align__(16) char smem[];
@@ -209,6 +216,13 @@ __global__ __launch_bounds__(512, 1) void k16_wn_layer(Wn16Args p) {
     qs[t] = f; php[t] = s - f * P;
   }
   const int nch = p.nconv + p.ncond;
+  // The K order is an index mapping of the chunk counter: step c of the loop runs chunk kmap(c).  Tap-first is the identity;
+  // conditioning-first runs the ncond conditioning chunks (in their own order) from zero, then the taps.  A seeded tile of a
+  // SEED launch starts at step ncond from k16_cond_seed's accumulators -- the registers those first steps would have left.
+  const bool cfirst = SEED || p.cond_first != 0;
+  const bool seeded = SEED && (int)blockIdx.x < p.seed_tiles;
+  const int c_lo = seeded ? p.ncond : 0;
+  auto kmap = [&](int c) __attribute__((always_inline)) { return cfirst ? (c < p.ncond ? c + p.nconv : c - p.ncond) : c; };
   const size_t hrow = (size_t)b * P;   // (b, phase) row base of h / xa, in units of Tqp frames
   auto load_stage = [&](int c, u32x4 (&sr)[NV]) __attribute__((always_inline)) {
 #pragma unroll
@@ -260,15 +274,27 @@ __global__ __launch_bounds__(512, 1) void k16_wn_layer(Wn16Args p) {
 #pragma unroll
       for (int r = 0; r < 16; ++r) acc[m][n][r] = 0.0f;
   u32x4 sr[NV], ar[4][2], an[4][2];
-  load_a(0, ar);
-  load_stage(0, sr);
+  load_a(kmap(c_lo), ar);
+  load_stage(kmap(c_lo), sr);
+  if constexpr (SEED) {
+    if (seeded) {
+      const float4* sp = p.seeds + ((size_t)ph * p.seed_nt + blockIdx.x) * 4096 + w * 512 + lane;
+#pragma unroll
+      for (int m = 0; m < 2; ++m)
+#pragma unroll
+        for (int g = 0; g < 4; ++g) {
+          const f32x4v v = __builtin_nontemporal_load((const f32x4v*)(sp + (m * 4 + g) * 64));   // read once
+          acc[m][0][4 * g + 0] = v.x; acc[m][0][4 * g + 1] = v.y; acc[m][0][4 * g + 2] = v.z; acc[m][0][4 * g + 3] = v.w;
+        }
+    }
+  }
   store_stage(0, sr);
   __syncthreads();
-  for (int c = 0; c < nch; ++c) {
-    const int cn = c + 1 < nch ? c + 1 : c;
+  for (int c = c_lo; c < nch; ++c) {
+    const int cn = kmap(c + 1 < nch ? c + 1 : c);
     load_a(cn, an);
     load_stage(cn, sr);
-    const _Float16* sb = stg + (c & 1) * TW * SP;
+    const _Float16* sb = stg + ((c - c_lo) & 1) * TW * SP;
 #pragma unroll
     for (int kk = 0; kk < 4; ++kk)
 #pragma unroll
@@ -277,7 +303,7 @@ __global__ __launch_bounds__(512, 1) void k16_wn_layer(Wn16Args p) {
         acc[0][n] = mfma16(ar[kk][0], bf, acc[0][n]);
         acc[1][n] = mfma16(ar[kk][1], bf, acc[1][n]);
       }
-    if (c + 1 < nch) store_stage((c + 1) & 1, sr);
+    if (c + 1 < nch) store_stage((c + 1 - c_lo) & 1, sr);
     __syncthreads();
 #pragma unroll
     for (int kk = 0; kk < 4; ++kk)
@@ -367,6 +393,124 @@ __global__ __launch_bounds__(512, 1) void k16_wn_layer(Wn16Args p) {
     float* dst = p.skip + (((size_t)b * 8 + j) * P + ph) * p.Tr + q;
     *dst = p.first ? p.endb[j] + s : *dst + s;
   }
+}
+
+// ------------------------------------------------------------------------------------------
+// k16_cond_seed: the conditioning chunks of every (flow, layer, phase) gate GEMM for a block of BT 32-frame tiles of ONE
+// utterance, ahead of the layers (WN.forward's cond_layers, glow.py:154-175, on the upsampled mel, glow.py:253-259).
+// The staged window is k16_wn_layer's load_stage for its conditioning chunks (zeros for kk >= kc), the A fragments are the same
+// u32x4 of wcond, and every chunk issues the same mfma16 sequence from zero accumulators: the registers parked in the seed
+// buffer are those a conditioning-first k16_wn_layer holds after its first ncond steps, bit for bit.  No bias (it stays at
+// the gate).  The window depends on the frames alone: it is staged once per block ([ncond][32 BT][SP] halfs) and stays in
+// LDS while the workgroup streams one 320 KiB (hop 256) weight image after the other past it -- 1.0 GB per pass.
+// Work item = (group of lpw layers, phase, block), block-major so that a workgroup restages only when its block changes.
+// ------------------------------------------------------------------------------------------
+struct Seed16Args {
+  const _Float16* melp;             // [Tqp][80] zero-margined mel frames
+  float4* seeds;                    // [layers_total][P][seed_nt][8][2][4][64]
+  const u32x4* wcond[MAXF * 8];     // per (flow, layer): [P][4 ncond][8][2][64]
+  int lpw, P, Tr, seed_nt;
+  int tile0, tile1, nblk;           // tiles [tile0, tile1) in nblk blocks of BT
+  int ncond, kc;
+  int layer0, layer1, items;
+  const int* skip;                  // optional (device): *skip != 0 -> the launch does nothing
+  int* counter;                     // bounded launch: hands out the items past the first gridDim (zero at launch), or null: strided
+};
+
+template <int BT>
+__global__ __launch_bounds__(512) void k16_cond_seed(Seed16Args p) {
+  constexpr int TW = 32 * BT;
+  extern __shared__ __align__(16) char smem[];
+  _Float16* win = (_Float16*)smem;   // [ncond][TW][SP]
+  __shared__ int next_item;
+  const int tid = threadIdx.x, w = tid >> 6, lane = tid & 63, lr = lane & 31, hf = lane >> 5;
+  if (p.skip && *p.skip) return;
+  const int nlg = (p.layer1 - p.layer0 + p.lpw - 1) / p.lpw, per = nlg * p.P, ncks = 4 * p.ncond;
+  int cur_blk = -1;
+  for (int lin = (int)blockIdx.x; lin < p.items;) {
+    const int blk = lin / per, rest = lin - blk * per, lg = rest / p.P, ph = rest - lg * p.P;
+    const int t0 = p.tile0 + blk * BT;
+    if (blk != cur_blk) {              // (uniform over the workgroup)
+      __syncthreads();
+      for (int v = tid; v < p.ncond * TW * 8; v += 512) {
+        const int c = v / (TW * 8), r = v - c * (TW * 8), col = r >> 3, kv = r & 7;
+        const int q = t0 * 32 + col, kk = 64 * c + 8 * kv;
+        u32x4 val = {0u, 0u, 0u, 0u};
+        if (kk < p.kc && q < p.Tr) {
+          const int j = kk / NMEL, m = kk % NMEL;
+          val = *(const u32x4*)(p.melp + ((size_t)HQ + q - j) * NMEL + m);
+        }
+        *(u32x4*)(win + (c * TW + col) * SP + 8 * kv) = val;
+      }
+      __syncthreads();
+      cur_blk = blk;
+    }
+    const int l0 = p.layer0 + lg * p.lpw, l1 = min(l0 + p.lpw, p.layer1);
+    for (int l = l0; l < l1; ++l) {
+      const u32x4* img = p.wcond[l] + (size_t)ph * ncks * 1024 + w * 128 + lane;   // ((kk*8 + w)*2 + m)*64 + lane of K step kk
+      f32x16 acc[2][BT];
+#pragma unroll
+      for (int m = 0; m < 2; ++m)
+#pragma unroll
+        for (int n = 0; n < BT; ++n)
+#pragma unroll
+          for (int r = 0; r < 16; ++r) acc[m][n][r] = 0.0f;
+      u32x4 ar[4][2], an[4][2];
+#pragma unroll
+      for (int kk = 0; kk < 4; ++kk)
+#pragma unroll
+        for (int m = 0; m < 2; ++m) ar[kk][m] = __builtin_nontemporal_load(img + kk * 1024 + m * 64);
+      for (int c = 0; c < p.ncond; ++c) {
+        const int cn = c + 1 < p.ncond ? c + 1 : c;
+#pragma unroll
+        for (int kk = 0; kk < 4; ++kk)
+#pragma unroll
+          for (int m = 0; m < 2; ++m) an[kk][m] = __builtin_nontemporal_load(img + (size_t)(4 * cn + kk) * 1024 + m * 64);
+        const _Float16* sb = win + c * TW * SP;
+#pragma unroll
+        for (int kk = 0; kk < 4; ++kk)
+#pragma unroll
+          for (int n = 0; n < BT; ++n) {
+            const h16x8 bf = *(const h16x8*)(sb + (32 * n + lr) * SP + 16 * kk + 8 * hf);
+            acc[0][n] = mfma16(ar[kk][0], bf, acc[0][n]);
+            acc[1][n] = mfma16(ar[kk][1], bf, acc[1][n]);
+          }
+#pragma unroll
+        for (int kk = 0; kk < 4; ++kk)
+#pragma unroll
+          for (int m = 0; m < 2; ++m) ar[kk][m] = an[kk][m];
+      }
+#pragma unroll
+      for (int n = 0; n < BT; ++n) {
+        if (t0 + n >= p.tile1) break;
+        float4* dst = p.seeds + (((size_t)l * p.P + ph) * p.seed_nt + t0 + n) * 4096 + w * 512 + lane;
+#pragma unroll
+        for (int m = 0; m < 2; ++m)
+#pragma unroll
+          for (int g = 0; g < 4; ++g)
+            __builtin_nontemporal_store(f32x4v{acc[m][n][4 * g + 0], acc[m][n][4 * g + 1], acc[m][n][4 * g + 2], acc[m][n][4 * g + 3]},
+                                        (f32x4v*)(dst + (m * 4 + g) * 64));   // read back milliseconds later: not through the L2
+      }
+    }
+    if (p.counter) {
+      __syncthreads();
+      if (tid == 0) next_item = (int)gridDim.x + atomicAdd(p.counter, 1);
+      __syncthreads();
+      lin = next_item;
+    } else {
+      lin += (int)gridDim.x;
+    }
+  }
+}
+
+// frames [f0, f0 + n) of an fp32 mel [80][ld] (the streaming postnet's output) -> the zero-margined fp16 [Tqp][80] layout,
+// rounded to nearest even as tensor.half() does
+__global__ void k16_mel_cvt(const float* __restrict__ mel, int ld, _Float16* __restrict__ melp, int f0, int n, const int* __restrict__ skip) {
+  if (skip && *skip) return;
+  const int idx = blockIdx.x * blockDim.x + threadIdx.x;
+  if (idx >= n * NMEL) return;
+  const int m = idx / n, q = f0 + idx % n;
+  melp[((size_t)HQ + q) * NMEL + m] = (_Float16)mel[(size_t)m * ld + q];
 }
 
 // ------------------------------------------------------------------------------------------
@@ -580,6 +724,10 @@ extern "C" int facppg_wg_create_f16(const facppg_wg_config* cfg, const float* we
   if (e == hipSuccess) e = hipStreamSynchronize(s);   // (the fp32 images are read by the packers above)
   if (e == hipSuccess) e = hipFuncSetAttribute((const void*)k16_wn_layer<false, 4>, hipFuncAttributeMaxDynamicSharedMemorySize, wn16_lds_bytes<4>());
   if (e == hipSuccess) e = hipFuncSetAttribute((const void*)k16_wn_layer<true, 4>, hipFuncAttributeMaxDynamicSharedMemorySize, wn16_lds_bytes<4>());
+  if (e == hipSuccess) e = hipFuncSetAttribute((const void*)k16_cond_seed<1>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 64);
+  if (e == hipSuccess) e = hipFuncSetAttribute((const void*)k16_cond_seed<2>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 64);
+  if (e == hipSuccess) e = hipFuncSetAttribute((const void*)k16_cond_seed<3>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 64);
+  if (e == hipSuccess) e = hipFuncSetAttribute((const void*)k16_cond_seed<4>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 64);
   facppg_wg_destroy(f);
   if (e != hipSuccess) {
     set_error("facppg_wg_create_f16: %s", hipGetErrorString(e));
@@ -590,15 +738,15 @@ extern "C" int facppg_wg_create_f16(const facppg_wg_config* cfg, const float* we
   return FACPPG_OK;
 }
 
-extern "C" int facppg_wg_infer_f16(facppg_wg* h, const uint16_t* mel_dev, const int32_t* T_valid_dev, const uint16_t* z_dev,
-                                   uint64_t seed, float sigma, int B, int T, uint16_t* audio_dev, void* ws_, size_t ws_bytes,
-                                   void* stream_) {
-  FACPPG_REQUIRE(h && mel_dev && audio_dev && ws_, FACPPG_EINVAL, "NULL argument");
-  FACPPG_REQUIRE(h->w16, FACPPG_EINVAL,
-                 "facppg_wg_infer_f16: the handle holds fp32 images (facppg_wg_create); use facppg_wg_infer, or make it with facppg_wg_create_f16");
-  FACPPG_REQUIRE(B > 0 && T > 0, FACPPG_EINVAL, "B and T must be positive (got %d, %d)", B, T);
-  FACPPG_REQUIRE(B <= 65535, FACPPG_EINVAL, "B too large");
-  const size_t need = wg16_workspace_bytes(h, B, T);
+// WaveGlow.infer on an fp16 handle.  cond_first: the K order of every layer launch.  melp_ext != null (B = 1): the caller's
+// zero-margined fp16 mel buffer laid out, like `seeds`, for T_layout >= T frames; tiles wholly inside [0, seeded_frames) start
+// from their seeds, the others run conditioning-first with full K in the same 32-frame-tile launches.
+static int wg16_infer(facppg_wg* h, const uint16_t* mel_dev, const int32_t* T_valid_dev, const uint16_t* z_dev, uint64_t seed,
+                      float sigma, int B, int T, uint16_t* audio_dev, void* ws_, size_t ws_bytes, void* stream_, int cond_first,
+                      const uint16_t* melp_ext = nullptr, const float* seeds_dev = nullptr, int seeded_frames = 0, int T_layout = 0,
+                      void* const* flow_events = nullptr) {
+  if (!melp_ext) T_layout = T;
+  const size_t need = wg16_workspace_bytes(h, B, T_layout);
   FACPPG_REQUIRE(ws_bytes >= need, FACPPG_EWORKSPACE, "workspace has %zu bytes, need %zu", ws_bytes, need);
   const facppg_wg_config& c = h->cfg;
   const Wg16State& st = *h->w16;
@@ -607,7 +755,8 @@ extern "C" int facppg_wg_infer_f16(facppg_wg* h, const uint16_t* mel_dev, const 
     for (int k = 0; k < c.n_flows; ++k) tot += h->early[k] ? c.n_early_size : 0;
     FACPPG_REQUIRE(tot == 8, FACPPG_EUNSUPPORTED, "noise channel count %d != n_group", tot);
   }
-  const Ws16 w = ws16_layout(c, B, T);
+  Ws16 w = ws16_layout(c, B, T_layout);   // rows (Tr, Tqp) of the layout; positions of the T frames that are there
+  w.L = T * w.P;
   FACPPG_REQUIRE((1 << (c.wn_layers - 1)) / w.P + 1 <= HQ, FACPPG_EUNSUPPORTED, "hop %d: the dilated taps reach past the %d-frame margins",
                  c.hop_length, HQ);
   FACPPG_REQUIRE((double)B * w.P * w.Tqp * C < 2.0e9, FACPPG_EUNSUPPORTED, "B*T = %d*%d frames is too long", B, T);
@@ -615,12 +764,13 @@ extern "C" int facppg_wg_infer_f16(facppg_wg* h, const uint16_t* mel_dev, const 
   char* ws = (char*)ws_;
   _Float16* hbuf[2] = {(_Float16*)(ws + w.h0), (_Float16*)(ws + w.h1)};
   _Float16* xa = (_Float16*)(ws + w.xa);
-  _Float16* melp = (_Float16*)(ws + w.melp);
+  const _Float16* melp = melp_ext ? (const _Float16*)melp_ext : (const _Float16*)(ws + w.melp);
   float* skip = (float*)(ws + w.skip);
   float* aud[2] = {(float*)(ws + w.aud0), (float*)(ws + w.aud1)};
   const int nf = c.n_flows;
   FACPPG_HIP_CHECK(hipMemsetAsync(ws + w.h0, 0, w.melp - w.h0, s));   // h0, h1, xa: margins and frames past each utterance
-  k16_mel_pad<<<dim3((w.Tqp * NMEL + 255) / 256, B), 256, 0, s>>>((const _Float16*)mel_dev, melp, T_valid_dev, T, w.Tqp);
+  if (!melp_ext)
+    k16_mel_pad<<<dim3((w.Tqp * NMEL + 255) / 256, B), 256, 0, s>>>((const _Float16*)mel_dev, (_Float16*)(ws + w.melp), T_valid_dev, T, w.Tqp);
   const _Float16* z = (const _Float16*)z_dev;
   if (!z) {
     const size_t zn = (size_t)B * 8 * w.L;
@@ -637,6 +787,7 @@ extern "C" int facppg_wg_infer_f16(facppg_wg* h, const uint16_t* mel_dev, const 
     FACPPG_REQUIRE(v == 32 || v == 64 || v == 128, FACPPG_EINVAL, "FACPPG_WG16_TILE=%s: expected 32, 64 or 128", env);
     tw = v;
   }
+  if (melp_ext) tw = 32;   // seeds are kept per 32-frame tile
   const dim3 lgrid((T + tw - 1) / tw, B, w.P);
   h->last_tile = tw; h->last_waves = 8; h->last_tiles = (int)(lgrid.x * lgrid.y * lgrid.z);
 
@@ -663,9 +814,12 @@ extern "C" int facppg_wg_infer_f16(facppg_wg* h, const uint16_t* mel_dev, const 
   memset(&a, 0, sizeof(a));
   a.xa = xa; a.melp = melp; a.skip = skip; a.t_valid = T_valid_dev;
   a.T = T; a.P = w.P; a.Tr = w.Tr; a.Tqp = w.Tqp; a.kc = st.kc; a.ncond = st.kcp / 64;
+  a.cond_first = cond_first; a.seed_nt = w.Tr / 32; a.seed_tiles = melp_ext ? std::min(seeded_frames, round_up(T, 32)) / 32 : 0;
   for (int k = nf - 1; k >= 0; --k) {
+    if (flow_events && flow_events[k]) FACPPG_HIP_CHECK(hipStreamWaitEvent(s, (hipEvent_t)flow_events[k], 0));
     a.endb = st.endb[k];
     for (int i = 0; i < c.wn_layers; ++i) {
+      if (melp_ext) a.seeds = (const float4*)seeds_dev + (size_t)(k * c.wn_layers + i) * w.P * a.seed_nt * 4096;
       const bool last = i == c.wn_layers - 1;
       a.h_in = hbuf[hi]; a.h_out = hbuf[hi ^ 1];
       a.wconv = st.wconv[k][i]; a.wcond = st.wcond[k][i]; a.wres = st.wres[k][i]; a.wend = st.wend[k][i];
@@ -676,7 +830,10 @@ extern "C" int facppg_wg_infer_f16(facppg_wg* h, const uint16_t* mel_dev, const 
     if (last) k16_wn_layer<true, NCB><<<lgrid, 512, wn16_lds_bytes<NCB>(), s>>>(a);                   \
     else k16_wn_layer<false, NCB><<<lgrid, 512, wn16_lds_bytes<NCB>(), s>>>(a);                       \
   } while (0)
-      if (tw == 128) WN16_LAUNCH(4);
+      if (melp_ext) {
+        if (last) k16_wn_layer<true, 1, true><<<lgrid, 512, wn16_lds_bytes<1>(), s>>>(a);
+        else k16_wn_layer<false, 1, true><<<lgrid, 512, wn16_lds_bytes<1>(), s>>>(a);
+      } else if (tw == 128) WN16_LAUNCH(4);
       else if (tw == 64) WN16_LAUNCH(2);
       else WN16_LAUNCH(1);
 #undef WN16_LAUNCH
@@ -704,4 +861,114 @@ extern "C" int facppg_wg_infer_f16(facppg_wg* h, const uint16_t* mel_dev, const 
   }
   FACPPG_HIP_CHECK(hipGetLastError());
   return FACPPG_OK;
+}
+
+static int wg16_infer_checks(const char* fn, facppg_wg* h, const void* mel, const void* audio, const void* ws, int B, int T) {
+  FACPPG_REQUIRE(h && mel && audio && ws, FACPPG_EINVAL, "NULL argument");
+  FACPPG_REQUIRE(h->w16, FACPPG_EINVAL, "%s: the handle holds fp32 images (facppg_wg_create); use the fp32 entry point, or make it with facppg_wg_create_f16", fn);
+  FACPPG_REQUIRE(B > 0 && T > 0, FACPPG_EINVAL, "B and T must be positive (got %d, %d)", B, T);
+  FACPPG_REQUIRE(B <= 65535, FACPPG_EINVAL, "B too large");
+  return FACPPG_OK;
+}
+
+extern "C" int facppg_wg_infer_f16(facppg_wg* h, const uint16_t* mel_dev, const int32_t* T_valid_dev, const uint16_t* z_dev,
+                                   uint64_t seed, float sigma, int B, int T, uint16_t* audio_dev, void* ws_, size_t ws_bytes,
+                                   void* stream_) {
+  if (int rc = wg16_infer_checks("facppg_wg_infer_f16", h, mel_dev, audio_dev, ws_, B, T)) return rc;
+  return wg16_infer(h, mel_dev, T_valid_dev, z_dev, seed, sigma, B, T, audio_dev, ws_, ws_bytes, stream_, 0);
+}
+
+extern "C" int facppg_wg_infer_f16_order(facppg_wg* h, const uint16_t* mel_dev, const int32_t* T_valid_dev, const uint16_t* z_dev,
+                                         uint64_t seed, float sigma, int B, int T, int cond_first, uint16_t* audio_dev, void* ws_,
+                                         size_t ws_bytes, void* stream_) {
+  if (int rc = wg16_infer_checks("facppg_wg_infer_f16_order", h, mel_dev, audio_dev, ws_, B, T)) return rc;
+  FACPPG_REQUIRE(cond_first == 0 || cond_first == 1, FACPPG_EINVAL, "cond_first must be 0 or 1 (got %d)", cond_first);
+  return wg16_infer(h, mel_dev, T_valid_dev, z_dev, seed, sigma, B, T, audio_dev, ws_, ws_bytes, stream_, cond_first);
+}
+
+#define WG_REQUIRE_FP16(h, fn)                                   \
+  FACPPG_REQUIRE(!(h) || (h)->w16, FACPPG_EINVAL,                \
+                 fn ": the handle holds fp32 images (facppg_wg_create); use the fp32 entry point of the same name, or make it with facppg_wg_create_f16")
+
+extern "C" int facppg_wg_seed_layout_f16(const facppg_wg* h, int T, int* Tqp, int* margin, size_t* seed_bytes) {
+  WG_REQUIRE_FP16(h, "facppg_wg_seed_layout_f16");
+  FACPPG_REQUIRE(h && T > 0 && Tqp && margin && seed_bytes, FACPPG_EINVAL, "NULL argument or T <= 0");
+  const Ws16 w = ws16_layout(h->cfg, 1, T);
+  *Tqp = w.Tqp; *margin = HQ;
+  *seed_bytes = (size_t)h->cfg.n_flows * h->cfg.wn_layers * w.P * (w.Tr / 32) * 4096 * sizeof(float4);
+  return FACPPG_OK;
+}
+
+extern "C" int facppg_wg_mel_pad_f16(const facppg_wg* h, const float* mel_dev, int T, int ld, int frame0, int nframes,
+                                     uint16_t* melp_dev, const int32_t* skip_dev, void* stream_) {
+  WG_REQUIRE_FP16(h, "facppg_wg_mel_pad_f16");
+  FACPPG_REQUIRE(h && mel_dev && melp_dev && T > 0, FACPPG_EINVAL, "NULL argument or T <= 0");
+  const Ws16 w = ws16_layout(h->cfg, 1, T);
+  FACPPG_REQUIRE(frame0 >= 0 && nframes >= 0 && frame0 + nframes <= w.Tr && frame0 + nframes <= ld, FACPPG_EINVAL,
+                 "frames [%d, %d) do not lie inside the %d padded frames and the row length %d", frame0, frame0 + nframes, w.Tr, ld);
+  if (nframes == 0) return FACPPG_OK;
+  k16_mel_cvt<<<(nframes * NMEL + 255) / 256, 256, 0, (hipStream_t)stream_>>>(mel_dev, ld, (_Float16*)melp_dev, frame0, nframes, skip_dev);
+  FACPPG_HIP_CHECK(hipGetLastError());
+  return FACPPG_OK;
+}
+
+extern "C" int facppg_wg_cond_seed_f16(facppg_wg* h, const uint16_t* melp_dev, int T, int frame0, int nframes, int block_tiles,
+                                       int layers_per_workgroup, int flow0, int nflows, float* seeds_dev, size_t seed_bytes,
+                                       const int32_t* skip_dev, int max_workgroups, int32_t* counter_dev, void* stream_) {
+  WG_REQUIRE_FP16(h, "facppg_wg_cond_seed_f16");
+  FACPPG_REQUIRE(h && melp_dev && seeds_dev, FACPPG_EINVAL, "NULL argument");
+  FACPPG_REQUIRE(T > 0, FACPPG_EINVAL, "T must be positive (got %d)", T);
+  const facppg_wg_config& c = h->cfg;
+  const Wg16State& st = *h->w16;
+  const Ws16 w = ws16_layout(c, 1, T);
+  size_t need = 0; int tqp = 0, mg = 0;
+  facppg_wg_seed_layout_f16(h, T, &tqp, &mg, &need);
+  FACPPG_REQUIRE(seed_bytes >= need, FACPPG_EWORKSPACE, "seed buffer has %zu bytes, need %zu", seed_bytes, need);
+  FACPPG_REQUIRE(frame0 >= 0 && frame0 % 32 == 0 && nframes > 0 && frame0 + nframes <= w.Tr, FACPPG_EINVAL,
+                 "frames [%d, %d): the first must be a multiple of 32 and the range inside the %d padded frames", frame0, frame0 + nframes, w.Tr);
+  FACPPG_REQUIRE(block_tiles >= 1 && block_tiles <= 4 && layers_per_workgroup >= 1, FACPPG_EINVAL, "block_tiles in 1..4, layers_per_workgroup >= 1");
+  if (nflows <= 0) { flow0 = 0; nflows = c.n_flows; }
+  FACPPG_REQUIRE(flow0 >= 0 && flow0 + nflows <= c.n_flows, FACPPG_EINVAL, "flows [%d, %d) of %d", flow0, flow0 + nflows, c.n_flows);
+  FACPPG_REQUIRE(c.n_flows * c.wn_layers <= MAXF * 8, FACPPG_EUNSUPPORTED, "too many layers");
+  Seed16Args a;
+  memset(&a, 0, sizeof(a));
+  a.melp = (const _Float16*)melp_dev; a.seeds = (float4*)seeds_dev; a.skip = skip_dev;
+  for (int k = 0; k < c.n_flows; ++k)
+    for (int i = 0; i < c.wn_layers; ++i) a.wcond[k * c.wn_layers + i] = st.wcond[k][i];
+  a.lpw = layers_per_workgroup; a.P = w.P; a.Tr = w.Tr; a.seed_nt = w.Tr / 32;
+  const int ntiles = (nframes + 31) / 32;
+  a.tile0 = frame0 / 32; a.tile1 = a.tile0 + ntiles; a.nblk = (ntiles + block_tiles - 1) / block_tiles;
+  a.ncond = st.kcp / 64; a.kc = st.kc;
+  a.layer0 = flow0 * c.wn_layers; a.layer1 = (flow0 + nflows) * c.wn_layers;
+  a.items = (a.layer1 - a.layer0 + a.lpw - 1) / a.lpw * w.P * a.nblk;
+  size_t lds = (size_t)a.ncond * 32 * block_tiles * SP * 2;
+  FACPPG_REQUIRE(lds <= 160 * 1024 - 64, FACPPG_EUNSUPPORTED, "block_tiles = %d needs %zu bytes of LDS", block_tiles, lds);
+  // a BOUNDED launch (the caller shares the GPU with other streams) asks for a CU's whole LDS per workgroup, as
+  // facppg_wg_cond_seed does: one workgroup per CU and no other stream's small workgroups next to it
+  const int max_wgs = max_workgroups / 8 * 8;
+  const bool bounded = max_wgs > 0 && max_wgs < a.items;
+  if (max_workgroups > 0) lds = (size_t)160 * 1024 - 64;
+  a.counter = bounded ? counter_dev : nullptr;
+  const unsigned grid = (unsigned)(bounded ? max_wgs : a.items);
+  hipStream_t s = (hipStream_t)stream_;
+  switch (block_tiles) {
+    case 1: k16_cond_seed<1><<<grid, 512, lds, s>>>(a); break;
+    case 2: k16_cond_seed<2><<<grid, 512, lds, s>>>(a); break;
+    case 3: k16_cond_seed<3><<<grid, 512, lds, s>>>(a); break;
+    default: k16_cond_seed<4><<<grid, 512, lds, s>>>(a); break;
+  }
+  FACPPG_HIP_CHECK(hipGetLastError());
+  return FACPPG_OK;
+}
+
+extern "C" int facppg_wg_infer_seeded_f16(facppg_wg* h, const uint16_t* melp_dev, int T_layout, int T, const float* seeds_dev,
+                                          int seeded_frames, const uint16_t* z_dev, uint64_t seed, float sigma, uint16_t* audio_dev,
+                                          void* ws_, size_t ws_bytes, void* const* flow_events, void* stream_) {
+  WG_REQUIRE_FP16(h, "facppg_wg_infer_seeded_f16");
+  FACPPG_REQUIRE(h && melp_dev && seeds_dev && audio_dev && ws_, FACPPG_EINVAL, "NULL argument");
+  FACPPG_REQUIRE(T > 0 && T_layout >= T, FACPPG_EINVAL, "need 0 < T <= T_layout (got %d, %d)", T, T_layout);
+  FACPPG_REQUIRE(seeded_frames >= 0 && seeded_frames % 32 == 0 && seeded_frames <= round_up(T, 32), FACPPG_EINVAL,
+                 "seeded_frames = %d: expected a multiple of 32 in [0, %d]", seeded_frames, round_up(T, 32));
+  return wg16_infer(h, nullptr, nullptr, z_dev, seed, sigma, 1, T, audio_dev, ws_, ws_bytes, stream_, 1, melp_dev, seeds_dev,
+                    seeded_frames, T_layout, flow_events);
 }

@@ -72,7 +72,14 @@ class ConditioningStream(object):
     block's width (FACPPG_STREAM_CHUNK frames: 32 for utterances up to 320 frames, 64 beyond, the last one before the expected
     end always 32, which keeps the share that has to wait for the decoder's end small).  What the blocks cannot cover -- the frames
     that become final only when the decoder ends -- runs as UNSEEDED 16-frame tiles inside the vocoder's own layer launches
-    (k_wn_layer_mixed) rather than as one more pass in front of them."""
+    (k_wn_layer_mixed) rather than as one more pass in front of them.
+
+    A .half() vocoder (the reference's inference.py --is_fp16 recipe) streams the same way on the fp16 kernels: every block's
+    postnet columns are rounded into the vocoder's fp16 mel buffer behind the postnet (facppg_wg_mel_pad_f16), the seed passes are
+    k16_cond_seed's (raw fp32 conditioning sums, 1.0 GB of fp16 images per pass), the layer launches run conditioning-first
+    (facppg_wg_infer_seeded_f16), and the tail tiles get their seeds from one more pass behind the decoder.  Bit for bit the
+    samples of the unstreamed pipeline, which runs a half vocoder conditioning-first for one utterance too
+    (tests/test_gpu_stream_f16.py)."""
 
     LAG = None   # frames of mel the postnet's output trails its input by (pad * layers; from the model)
 
@@ -90,9 +97,30 @@ class ConditioningStream(object):
             return False
         if os.environ.get("FACPPG_WG_EDGE_FOLD", "1") == "0" or getattr(tacotron, "decoder_workgroups", 0):
             return False
-        if getattr(getattr(waveglow, "upsample", None), "weight", torch.empty(0)).dtype != torch.float32:
-            return False    # the seeds are fp32 accumulators: a half vocoder runs unstreamed
+        if ConditioningStream.precision(waveglow) is None:
+            return False    # fp32, or all fp16 (the reference's .half() recipe): bf16 and mixed modules run unstreamed (or are refused)
         return waveglow.WN[0].n_layers == 8 and waveglow.n_group == 8
+
+    @staticmethod
+    def precision(waveglow):
+        """torch.float32 / torch.float16: the kernels the stream would feed; None: neither (bf16, mixed dtypes)."""
+        dt = getattr(getattr(waveglow, "upsample", None), "weight", torch.empty(0)).dtype
+        if dt == torch.float16:      # every WN / upsample parameter must be (the walk is spent on half vocoders only)
+            if hasattr(waveglow, "_precision"):
+                from facppg.lib import FacppgError
+                try:
+                    return dt if waveglow._precision() == dt else None
+                except FacppgError:
+                    return None
+            dts = {p.dtype for p in waveglow.upsample.parameters()} | {p.dtype for wn in waveglow.WN for p in wn.parameters()}
+            return dt if dts == {dt} else None
+        return dt if dt == torch.float32 else None
+
+    # Utterances shorter than this are not streamed (FACPPG_STREAM_MIN_FRAMES overrides), per vocoder precision.  fp32: see begin().
+    # fp16: streamed wins at every length of the sweep (64 frames 5.8 -> 5.3 ms, 100: 6.7 -> 6.3, 130: 7.4 -> 7.0, 200: 9.2 -> 8.8,
+    # 400: 16.1 -> 15.2; profiles/r11_stream_f16_sweep.txt) -- its layer launches are 32-frame tiles streamed or not, so a seeded
+    # launch is shorter at any length; 64 frames is the shortest utterance the sweep covers.
+    MIN_FRAMES = {torch.float32: 128, torch.float16: 64}
 
     SLACK = 64   # frames past the PPG's length the buffers are laid out for (an utterance that runs on past them is finished unstreamed)
 
@@ -128,15 +156,19 @@ class ConditioningStream(object):
             return t[:numel]
         # (the layout queries validate the models' packed-weight handles -- ~1000 tensors, 0.2 - 0.4 ms of host time in front of the
         #  encoder: asked once per (step limit, layout), not per utterance)
-        lk = (dev, steps, cap)
+        lk = (dev, steps, cap, self.half)
         if self.__dict__.get("layout_key") != lk:
             self.layout = self.waveglow.seed_layout(cap, dev) + (L.facppg_taco_postnet_stream_workspace_bytes(self.tacotron._handle(dev), cap),)
             self.layout_key = lk
         self.tqp, self.margin, seed_bytes, post_ws_bytes = self.layout
         # {value, frame + 1} words + the void flags + the work counters + mel_post in the vocoder's zero-margined layout: ONE allocation,
         # zeroed by one launch before every decode
+        # (a half vocoder: + the same frames in ITS layout, fp16 [tqp][NF], converted block by block behind the postnet)
         nw = steps * self.NF + 512
-        self.zeroed = grown("zeroed", nw + (self.NF * self.tqp + 1) // 2, torch.int64, zero=True)
+        n32 = (self.NF * self.tqp + 1) // 2
+        n16 = (self.NF * self.tqp + 3) // 4 if self.half else 0
+        self.zeroed = grown("zeroed", nw + n32 + n16, torch.int64, zero=True)
+        self.melp16 = self.zeroed[nw + n32:nw + n32 + n16].view(torch.float16)[:self.NF * self.tqp].view(self.tqp, self.NF) if self.half else None
         self.words = self.zeroed[:nw]
         self.void = self.words[steps * self.NF:].view(torch.int32)[:512]                  # one per block
         self.counters = self.words[steps * self.NF:].view(torch.int32)[512:]              # one per bounded seed launch
@@ -188,7 +220,11 @@ class ConditioningStream(object):
         # Short utterances do not gain: up to 128 frames the unstreamed vocoder runs 16-frame tiles, one per CU, and a layer launch
         # lasts as long as ONE tile either way (measured, tools/stream_T_sweep.sh: 64 frames 6.9 -> 8.1 ms, 100 frames 8.2 -> 9.0
         # streamed; 130 frames 10.0 -> 9.7, 200 frames 13.3 -> 11.5, 1000 frames 53.9 -> 48.5).  FACPPG_STREAM_MIN_FRAMES overrides.
-        if not self.usable(tacotron, self.waveglow) or min(steps, Tin) < int(os.environ.get("FACPPG_STREAM_MIN_FRAMES", "128")):
+        if not self.usable(tacotron, self.waveglow):
+            return None
+        # (usable: the vocoder is all fp32 or all fp16, whichever its upsampler is)
+        self.half = getattr(getattr(self.waveglow, "upsample", None), "weight", torch.empty(0)).dtype == torch.float16
+        if min(steps, Tin) < int(os.environ.get("FACPPG_STREAM_MIN_FRAMES", self.MIN_FRAMES[torch.float16 if self.half else torch.float32])):
             return None
         self.cap = min(steps, -(-(Tin + self.SLACK) // 32) * 32)
         try:
@@ -232,7 +268,7 @@ class ConditioningStream(object):
             if self.profile:
                 e0 = torch.cuda.Event(enable_timing=True)
                 e0.record(self.side)
-            self.waveglow.cond_seed(self.melp, self.cap, s_a, n, self.seeds, block_tiles=bt, layers_per_workgroup=lpw, skip=void,
+            self.waveglow.cond_seed(self.melp16 if self.half else self.melp, self.cap, s_a, n, self.seeds, block_tiles=bt, layers_per_workgroup=lpw, skip=void,
                                     handle=self.wg_handle, flows=(lo, hi - lo), max_workgroups=bound,
                                     counter=self.counters[self.n_launch:self.n_launch + 1] if self.n_launch < 500 else None)
             self.n_launch += 1
@@ -254,6 +290,10 @@ class ConditioningStream(object):
                     _lib.check(L.facppg_taco_postnet_range(self.taco_handle, _lib.ptr(self.mel), steps, f_prev, f_new, 0,
                                                            self.melp.data_ptr() + 4 * self.margin, self.tqp, _lib.ptr(self.post_ws),
                                                            self.post_ws.numel(), self.cap, _lib.ptr(void), st))
+                    if self.half:   # the columns that call made final, rounded into the half vocoder's buffer
+                        c0 = max(0, f_prev - self.lag)
+                        self.waveglow.mel_convert(self.melp[:, self.margin:], self.cap, c0, f_new - self.lag - c0, self.melp16, skip=void,
+                                                  handle=self.wg_handle)
                     # (the block's void flag travels to pinned host memory behind its collector, on this stream: when the decoder has
                     #  ended the flags of the blocks it covered have been on the host for milliseconds -- finish() reads them there
                     #  instead of spending a second device->host round trip between the decoder and the vocoder)
@@ -309,6 +349,9 @@ class ConditioningStream(object):
             _lib.check(L.facppg_taco_postnet_range(self.taco_handle, _lib.ptr(self.mel), steps, f_done, Tout, Tout,
                                                    self.melp.data_ptr() + 4 * self.margin, self.tqp, _lib.ptr(self.post_ws),
                                                    self.post_ws.numel(), self.cap, None, st))
+            if self.half:
+                c0 = max(0, f_done - self.lag)
+                self.waveglow.mel_convert(self.melp[:, self.margin:], self.cap, c0, Tout - c0, self.melp16, handle=self.wg_handle)
         self.Tout, self.seeded = Tout, s_done
         return self.melp[:, self.margin:self.margin + Tout].unsqueeze(0)
 
@@ -324,6 +367,26 @@ class ConditioningStream(object):
     def vocode(self, sigma, z=None, seed=None):
         """WaveGlow.infer of the streamed utterance from the seeds (the frames behind the last block get theirs here)."""
         T, s_done = self.Tout, self.seeded
+        if self.half:
+            # The frames behind the last block.  Seeded and unseeded tiles of the fp16 launches are both 32 frames wide, so a launch
+            # with ONE unseeded tile lasts as long as an unseeded launch (every tile has a CU of its own at these lengths): the
+            # tail tiles get their seeds from one more pass in front of the vocoder instead (200 frames, two tail tiles: 8.8 ms
+            # against 9.1 ms end to end with the in-kernel tail, profiles/r11_stream_f16_ab.txt).  FACPPG_STREAM_TAIL=mixed runs
+            # them unseeded, conditioning-first, inside the layer launches -- same samples.  Half audio, widened as the
+            # unstreamed path's is.
+            s_all = -(-T // 32) * 32
+            if s_all > s_done and os.environ.get("FACPPG_STREAM_TAIL", "seed") != "mixed":
+                # (one workgroup per CU walking the work items from a counter: the pass streams the images fastest that way)
+                n_cu = torch.cuda.get_device_properties(self.dev).multi_processor_count
+                bounded = self.n_launch < 500
+                self.waveglow.cond_seed(self.melp16, self.cap, s_done, s_all - s_done, self.seeds, block_tiles=min(4, (s_all - s_done) // 32),
+                                        layers_per_workgroup=1, handle=self.wg_handle, max_workgroups=n_cu if bounded else 0,
+                                        counter=self.counters[self.n_launch:self.n_launch + 1] if bounded else None)
+                self.n_launch += 1
+                s_done = s_all
+            self.active = False
+            return self.waveglow.infer_seeded(self.melp16, T, self.seeds, s_done, sigma=sigma, z=z, seed=seed, handle=self.wg_handle,
+                                              T_layout=self.cap, flow_events=self.flow_events).float()
         s_all = -(-T // 32) * 32
         # The frames behind the last block: as unseeded 16-frame tiles inside the layer launches themselves (k_wn_layer_mixed) while
         # the launch still gives every CU at most one workgroup; otherwise (and with FACPPG_STREAM_TAIL=seed) one more seed pass
@@ -413,14 +476,18 @@ def _vocode(mel_post, tout, waveglow, denoiser, sigma, strength, seed, z, uttera
     multi = len(tout) > 1
     wg_seeds = None if utterance_seeds is None else [int(v) + 1 for v in utterance_seeds]
     half = waveglow.upsample.weight.dtype != torch.float32   # a .half() vocoder: half mel in, its half audio widened to fp32
-    if half:
+    streamed = consumer is not None and consumer.active
+    if half and not streamed:
         mel_post = mel_post.to(waveglow.upsample.weight.dtype)
-    if consumer is not None and consumer.active:
+    if streamed:
         if wg_seeds is not None:
             z = waveglow.draw_noise(wg_seeds, tout[0], mel_post.device)
         audio = consumer.vocode(sigma, z=z, seed=seed)
     else:
-        audio = waveglow.infer(mel_post, sigma=sigma, z=z, lengths=tout if multi else None, seed=seed, utterance_seeds=wg_seeds)
+        # one utterance through a half vocoder: the K order of the streamed path (conditioning first), so that the samples do not
+        # depend on whether this utterance was streamed (too short, FACPPG_STREAM=0, outgrew the layout, stream busy)
+        order = {"cond_first": True} if half and not multi else {}
+        audio = waveglow.infer(mel_post, sigma=sigma, z=z, lengths=tout if multi else None, seed=seed, utterance_seeds=wg_seeds, **order)
         if half:
             audio = audio.float()
     if timer is not None:

@@ -949,7 +949,8 @@ class WaveGlow(torch.nn.Module):
         self._release()
         L = _lib.load()
         cfg = self._config()
-        create = L.facppg_wg_create_f16 if self._precision() == torch.float16 else L.facppg_wg_create
+        prec = self._precision()
+        create = L.facppg_wg_create_f16 if prec == torch.float16 else L.facppg_wg_create
         blob = self._flat_weights().to(device).contiguous()
         if blob.numel() != L.facppg_wg_weight_count(cfg):
             raise _lib.FacppgError("weight blob has %d values, library expects %d (unsupported config: %s)" % (
@@ -958,8 +959,16 @@ class WaveGlow(torch.nn.Module):
         with torch.cuda.device(device):
             _lib.check(create(cfg, _lib.ptr(blob), blob.numel(), device.index,
                               _lib.current_stream(device), _lib.ctypes.byref(out)))
-        self.__dict__["_facppg_handle"] = (out, device, _lib.WeightIdentity(self))
+        self.__dict__["_facppg_handle"] = (out, device, _lib.WeightIdentity(self), prec)
         return out
+
+    def _half_handle(self, h):
+        """Whether ``h`` -- the module's current handle -- holds fp16 images: _precision() as it was when the handle was built
+        (any change of a parameter since then makes _handle() build a new one)."""
+        cur = self.__dict__.get("_facppg_handle")
+        if cur is None or cur[0] is not h:
+            raise _lib.FacppgError("WaveGlow: the handle passed in is not this module's current one (its weights changed since)")
+        return cur[3] == torch.float16
 
     def _precision(self):
         """The inference precision of the module: the dtype of its WN and upsample parameters -- all fp32 (facppg_wg_create)
@@ -1230,62 +1239,95 @@ class WaveGlow(torch.nn.Module):
         column margin + q; the seed buffer has seed_bytes bytes (facppg_wg_seed_layout)."""
         c = _lib.ctypes
         tqp, mg, nb = c.c_int(), c.c_int(), c.c_size_t()
-        _lib.check(_lib.load().facppg_wg_seed_layout(self._handle(device), int(T), c.byref(tqp), c.byref(mg), c.byref(nb)))
+        h = self._handle(device)
+        L = _lib.load()
+        layout = L.facppg_wg_seed_layout_f16 if self._half_handle(h) else L.facppg_wg_seed_layout
+        _lib.check(layout(h, int(T), c.byref(tqp), c.byref(mg), c.byref(nb)))
         return tqp.value, mg.value, nb.value
 
     def mel_pad(self, mel, handle=None):
-        """mel [1, n_mel, T] -> the zero-margined [n_mel, Tqp] buffer cond_seed / infer_seeded read."""
+        """mel [1, n_mel, T] -> the zero-margined [n_mel, Tqp] buffer cond_seed / infer_seeded read; of a .half() module: an fp32
+        (or half) mel -> the fp16 [Tqp, n_mel] buffer, rounded to nearest even."""
         dev = mel.device
         T = mel.shape[2]
         tqp, _, _ = self.seed_layout(T, dev)
+        if self._half_handle(self._handle(dev)):
+            out = torch.zeros(tqp, mel.shape[1], dtype=torch.float16, device=dev)
+            self.mel_convert(mel[0].float(), T, 0, T, out)
+            return out
         out = torch.empty(mel.shape[1], tqp, dtype=torch.float32, device=dev)
         m = mel[0]
         with torch.cuda.device(dev):
             _lib.check(_lib.load().facppg_wg_mel_pad(self._handle(dev), _lib.ptr(m), T, m.stride(0), _lib.ptr(out), _lib.current_stream(dev)))
         return out
 
+    def mel_convert(self, mel, T, frame0, nframes, melp, skip=None, handle=None):
+        """Frames [frame0, frame0 + nframes) of the fp32 ``mel`` [n_mel, >= frame0 + nframes] (row stride mel.stride(0)) into the
+        fp16 zero-margined ``melp`` [Tqp, n_mel] laid out for T frames (k16_mel_cvt), on the current stream.  .half() modules."""
+        dev = melp.device
+        if mel.dtype != torch.float32 or melp.dtype != torch.float16 or mel.stride(1) != 1:
+            raise _lib.FacppgError("mel_convert: fp32 rows in, the fp16 mel buffer out")
+        with torch.cuda.device(dev):
+            _lib.check(_lib.load().facppg_wg_mel_pad_f16(handle if handle is not None else self._handle(dev), _lib.ptr(mel), int(T),
+                                                         mel.stride(0), int(frame0), int(nframes), _lib.ptr(melp), _lib.ptr(skip),
+                                                         _lib.current_stream(dev)))
+
     def cond_seed(self, melp, T, frame0, nframes, seeds, block_tiles=1, layers_per_workgroup=4, skip=None, handle=None, flows=None,
                   max_workgroups=0, counter=None):
         """Form the gate accumulators' seeds (bias + conditioning sums, k_cond_seed) of frames [frame0, frame0 + nframes) of the
         utterance whose zero-margined mel frames are ``melp``, for every flow (or flows = (first, count)), layer and phase, on the
         current stream.  max_workgroups > 0 bounds the launch (its workgroups then take the work items from ``counter``, a zeroed
-        int32 on the device): the CUs it does not fill stay free for whoever else needs one right away."""
+        int32 on the device): the CUs it does not fill stay free for whoever else needs one right away.  A .half() module takes
+        its fp16 mel buffer (mel_pad / mel_convert) and forms the raw conditioning sums, no bias (k16_cond_seed)."""
         dev = melp.device
         f0, nf = flows if flows is not None else (0, 0)
+        h = handle if handle is not None else self._handle(dev)
+        L = _lib.load()
+        half = self._half_handle(h)
+        if melp.dtype != (torch.float16 if half else torch.float32):
+            raise _lib.FacppgError("cond_seed: the module is %s, its mel buffer is %s" % ("fp16" if half else "fp32", melp.dtype))
+        seed_fn = L.facppg_wg_cond_seed_f16 if half else L.facppg_wg_cond_seed
         with torch.cuda.device(dev):
-            _lib.check(_lib.load().facppg_wg_cond_seed(handle if handle is not None else self._handle(dev), _lib.ptr(melp), int(T), int(frame0),
-                                                       int(nframes), int(block_tiles), int(layers_per_workgroup), int(f0), int(nf), _lib.ptr(seeds),
-                                                       seeds.numel() * seeds.element_size(), _lib.ptr(skip), int(max_workgroups), _lib.ptr(counter),
-                                                       _lib.current_stream(dev)))
+            _lib.check(seed_fn(h, _lib.ptr(melp), int(T), int(frame0),
+                       int(nframes), int(block_tiles), int(layers_per_workgroup), int(f0), int(nf), _lib.ptr(seeds),
+                       seeds.numel() * seeds.element_size(), _lib.ptr(skip), int(max_workgroups), _lib.ptr(counter),
+                       _lib.current_stream(dev)))
 
     def infer_seeded(self, melp, T, seeds, seeded_frames, sigma=1.0, z=None, seed=None, handle=None, T_layout=None, flow_events=None):
         """WaveGlow.infer of ONE utterance (glow.py:252-293) whose layers start from ``seeds``: audio [1, T*hop].  Same samples
         as infer() on the same mel frames, bit for bit.  T_layout >= T: the frame count ``melp`` and ``seeds`` were laid out for.
-        flow_events: {flow: torch.cuda.Event} the launches of that flow wait for (its seeds are still being formed elsewhere)."""
+        flow_events: {flow: torch.cuda.Event} the launches of that flow wait for (its seeds are still being formed elsewhere).
+        A .half() module (fp16 ``melp``): half audio, the samples of infer(mel.half(), cond_first=True); seeded_frames may be 0."""
         T_layout = T if T_layout is None else int(T_layout)
         dev = melp.device
         hop = self.upsample.stride[0]
+        h = handle if handle is not None else self._handle(dev)
+        half = self._half_handle(h)
+        dt = torch.float16 if half else torch.float32
+        if melp.dtype != dt:
+            raise _lib.FacppgError("infer_seeded: the module is %s, its mel buffer is %s" % ("fp16" if half else "fp32", melp.dtype))
         zt = None
         if z is not None:
             if isinstance(z, (list, tuple)):
-                z = torch.cat([t.to(dev).float().reshape(-1) for t in z])
-            zt = z.to(dev).float().contiguous()
+                z = torch.cat([t.to(dev).to(dt).reshape(-1) for t in z])
+            zt = z.to(device=dev, dtype=dt).contiguous()
             if zt.numel() != self.n_group * (T * hop // self.n_group):
                 raise _lib.FacppgError("z has %d values, expected n_group*L = %d" % (zt.numel(), self.n_group * (T * hop // self.n_group)))
         if seed is None:
             seed = int(torch.empty((), dtype=torch.int64).random_().item())
-        h = handle if handle is not None else self._handle(dev)
         ws = self._infer_workspace(1, T_layout, dev, 0, h)
-        audio = torch.empty(1, T * hop, dtype=torch.float32, device=dev)
+        audio = torch.empty(1, T * hop, dtype=dt, device=dev)
+        L = _lib.load()
+        infer_fn = L.facppg_wg_infer_seeded_f16 if half else L.facppg_wg_infer_seeded
         evs = None
         if flow_events:
             evs = (_lib.ctypes.c_void_p * self.n_flows)()
             for k, ev in flow_events.items():
                 evs[k] = ev.cuda_event
         with torch.cuda.device(dev):
-            _lib.check(_lib.load().facppg_wg_infer_seeded(h, _lib.ptr(melp), T_layout, int(T), _lib.ptr(seeds), int(seeded_frames), _lib.ptr(zt),
-                                                          seed & 0xFFFFFFFFFFFFFFFF, float(sigma), _lib.ptr(audio), _lib.ptr(ws), ws.numel(),
-                                                          evs, _lib.current_stream(dev)))
+            _lib.check(infer_fn(h, _lib.ptr(melp), T_layout, int(T), _lib.ptr(seeds), int(seeded_frames), _lib.ptr(zt),
+                                seed & 0xFFFFFFFFFFFFFFFF, float(sigma), _lib.ptr(audio), _lib.ptr(ws), ws.numel(),
+                                evs, _lib.current_stream(dev)))
         return audio
 
     def prepare(self, device):
@@ -1302,16 +1344,22 @@ class WaveGlow(torch.nn.Module):
             return pre[0]
         return self._handle(dev)
 
-    def infer(self, spect, sigma=1.0, z=None, lengths=None, seed=None, utterance_seeds=None, groups=None):
+    def infer(self, spect, sigma=1.0, z=None, lengths=None, seed=None, utterance_seeds=None, groups=None, cond_first=False):
         """mel [B, n_mel, T] (GPU, fp32) -> audio [B, T*hop]   (glow.py:252-293); a .half() module takes a half mel and returns
         half audio (the reference's HalfTensor branch, see _infer_half).
         groups: None = decide from the launch shape (ragged batches whose layer launches would idle through >= 3 % of their
         time in the last round run as two concurrent half-batches, see _infer_two_groups), 1 = one launch sequence, 2 = force
-        the two half-batches (needs host-side lengths).  With `seed` alone the noise of a uniform batch is a function of (seed, batch
+        the two half-batches (needs host-side lengths).  cond_first (.half() modules): the K order of the gate GEMMs -- False: taps,
+        then conditioning; True: conditioning first, the order of the seeded path (infer_seeded), whose samples it then equals bit
+        for bit; the two differ in their last bits (fp32 reassociation).  An fp32 module is conditioning-first already and
+        refuses the keyword.  With `seed` alone the noise of a uniform batch is a function of (seed, batch
         layout); a ragged batch with host-side lengths draws per-utterance streams derived from (seed, b), identical in both modes."""
         _lib.require_cuda(spect, "WaveGlow.infer: spect")
         if spect.dtype != torch.float32 or self.upsample.weight.dtype != torch.float32:
-            return self._infer_half(spect, sigma, z, lengths, seed, utterance_seeds, groups)
+            return self._infer_half(spect, sigma, z, lengths, seed, utterance_seeds, groups, cond_first)
+        if cond_first:
+            raise _lib.FacppgError("WaveGlow.infer: cond_first=True is the K order of a .half() module's kernels; the fp32 path sums "
+                                   "the conditioning chunks first already")
         dev = spect.device
         h = self._checked_handle(dev)   # (ONE validity check of the packed weights per call -- it walks ~1000 tensors -- or none:
         spect = spect.contiguous()      #  prepare(); consumed HERE so that no path -- two half-batches included -- leaves the token behind)
@@ -1359,7 +1407,7 @@ class WaveGlow(torch.nn.Module):
         self._infer_launch(spect, lt, zt, seed, sigma, audio, self._infer_workspace(B, T, dev, 0, h), h)
         return audio
 
-    def _infer_half(self, spect, sigma, z, lengths, seed, utterance_seeds, groups):
+    def _infer_half(self, spect, sigma, z, lengths, seed, utterance_seeds, groups, cond_first=False):
         """infer() of a .half() module (glow.py:261-290, the HalfTensor branch): half mel [B, n_mel, T] -> half audio
         [B, T*hop] on the fp16 MFMA kernels (facppg_wg_infer_f16).  Same z / seed / lengths / utterance_seeds semantics as
         the fp32 path; one launch sequence (groups 1)."""
@@ -1408,9 +1456,9 @@ class WaveGlow(torch.nn.Module):
             torch.empty(B, T * hop, dtype=torch.float16, device=dev)
         ws = self._infer_workspace(B, T, dev, 0, h)
         with torch.cuda.device(dev):
-            _lib.check(_lib.load().facppg_wg_infer_f16(h, _lib.ptr(spect), _lib.ptr(lt), _lib.ptr(zt), seed & 0xFFFFFFFFFFFFFFFF,
-                                                       float(sigma), B, T, _lib.ptr(audio), _lib.ptr(ws), ws.numel(),
-                                                       _lib.current_stream(dev)))
+            _lib.check(_lib.load().facppg_wg_infer_f16_order(h, _lib.ptr(spect), _lib.ptr(lt), _lib.ptr(zt), seed & 0xFFFFFFFFFFFFFFFF,
+                                                             float(sigma), B, T, 1 if cond_first else 0, _lib.ptr(audio), _lib.ptr(ws),
+                                                             ws.numel(), _lib.current_stream(dev)))
         return audio
 
     @staticmethod

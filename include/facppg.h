@@ -367,6 +367,38 @@ int facppg_wg_infer_seeded(facppg_wg* h, const float* melp_dev, int T_layout, in
                            int seeded_frames, const float* z_dev, uint64_t seed, float sigma, float* audio_dev,
                            void* workspace_dev, size_t workspace_bytes, void* const* flow_events, void* stream);
 
+/* ---- The same for an fp16 handle (facppg_wg_create_f16): the reference's HalfTensor branch of WaveGlow.infer
+ * (glow.py:252-293, 261-290) with WN.forward's cond_layers (glow.py:154-175) formed ahead of the layers.
+ * The fp16 layer kernel's default K order is taps, then conditioning; a seed can only stand for the conditioning chunks if
+ * they are summed first, and fp32 accumulation is not associative.  So the K order is an argument:
+ * facppg_wg_infer_f16_order: facppg_wg_infer_f16 with cond_first = 0 (its bits) or 1 (the conditioning chunks from zero
+ *   accumulators, then the taps; the bias is added at the gate either way).  The seeded path is conditioning-first throughout:
+ *   facppg_wg_infer_seeded_f16 yields the bits of facppg_wg_infer_f16_order(cond_first = 1) on the same frames, whichever
+ *   tiles were seeded.
+ * facppg_wg_seed_layout_f16: as facppg_wg_seed_layout; the mel buffer is melp [Tqp][n_mel] in fp16 (frame q at row
+ *   *margin + q, margins and missing frames zero), the seeds are raw fp32 gate accumulators (no bias) in the layer kernel's
+ *   register order, 64 KiB per (flow, layer, phase, 32-frame tile).
+ * facppg_wg_mel_pad_f16: frames [frame0, frame0 + nframes) of the fp32 mel_dev [n_mel][ld] -> melp_dev, rounded to nearest
+ *   even; nothing else of melp_dev is written (the caller zeroes it once).  *skip_dev != 0 (may be NULL): does nothing.
+ * facppg_wg_cond_seed_f16: the arguments of facppg_wg_cond_seed; layers_per_workgroup layers form one work item.
+ * facppg_wg_infer_seeded_f16: the arguments of facppg_wg_infer_seeded with fp16 melp, injected z and audio.  The launches use
+ *   32-frame tiles: tiles wholly inside [0, seeded_frames) (a multiple of 32, at most T rounded up to 32; 0 allowed) start from
+ *   their seeds, the others run unseeded, conditioning-first, in the same launches.
+ * An fp32 handle into any of these returns FACPPG_EINVAL (facppg_last_error names the mismatch), as an fp16 handle does into
+ * the fp32 entry points above. */
+int facppg_wg_infer_f16_order(facppg_wg* h, const uint16_t* mel_dev, const int32_t* T_valid_dev, const uint16_t* z_dev,
+                              uint64_t seed, float sigma, int B, int T, int cond_first, uint16_t* audio_dev,
+                              void* workspace_dev, size_t workspace_bytes, void* stream);
+int facppg_wg_seed_layout_f16(const facppg_wg* h, int T, int* Tqp, int* margin, size_t* seed_bytes);
+int facppg_wg_mel_pad_f16(const facppg_wg* h, const float* mel_dev, int T, int ld, int frame0, int nframes,
+                          uint16_t* melp_dev, const int32_t* skip_dev, void* stream);
+int facppg_wg_cond_seed_f16(facppg_wg* h, const uint16_t* melp_dev, int T, int frame0, int nframes, int block_tiles,
+                            int layers_per_workgroup, int flow0, int nflows, float* seeds_dev, size_t seed_bytes,
+                            const int32_t* skip_dev, int max_workgroups, int32_t* counter_dev, void* stream);
+int facppg_wg_infer_seeded_f16(facppg_wg* h, const uint16_t* melp_dev, int T_layout, int T, const float* seeds_dev,
+                               int seeded_frames, const uint16_t* z_dev, uint64_t seed, float sigma, uint16_t* audio_dev,
+                               void* workspace_dev, size_t workspace_bytes, void* const* flow_events, void* stream);
+
 /* ------------------------------------------------------------------------------------
  * STFT / mel analysis / denoiser (src/common/stft.py, src/common/layers.py,
  * src/waveglow/denoiser.py)
