@@ -72,40 +72,54 @@ class ConditioningStream(object):
     block's width (FACPPG_STREAM_CHUNK frames: 32 for utterances up to 320 frames, 64 beyond, the last one before the expected
     end always 32, which keeps the share that has to wait for the decoder's end small).  What the blocks cannot cover -- the frames
     that become final only when the decoder ends -- runs as UNSEEDED 16-frame tiles inside the vocoder's own layer launches
-    (k_wn_layer_mixed) rather than as one more pass in front of them.
+    (k_wn_layer_mixed) or gets its seeds from one more pass in front of them: tail_pass() decides.
 
     A .half() vocoder (the reference's inference.py --is_fp16 recipe) streams the same way on the fp16 kernels: every block's
     postnet columns are rounded into the vocoder's fp16 mel buffer behind the postnet (facppg_wg_mel_pad_f16), the seed passes are
     k16_cond_seed's (raw fp32 conditioning sums, 1.0 GB of fp16 images per pass), the layer launches run conditioning-first
     (facppg_wg_infer_seeded_f16), and the tail tiles get their seeds from one more pass behind the decoder.  Bit for bit the
     samples of the unstreamed pipeline, which runs a half vocoder conditioning-first for one utterance too
-    (tests/test_gpu_stream_f16.py)."""
+    (tests/test_gpu_stream_f16.py).
 
-    LAG = None   # frames of mel the postnet's output trails its input by (pad * layers; from the model)
+    Host flow of one utterance: begin() (precision, layout, zeroed frame words) -> enqueue() (per planned block: _mel_block on
+    the postnet stream, _seed_pass on the seed stream) -> finish() (_mel_block for the frames behind the last block) -> vocode()
+    (tail_pass, possibly one more _seed_pass, WaveGlow.infer_seeded)."""
 
     def __init__(self, tacotron, waveglow):
         self.tacotron, self.waveglow = tacotron, waveglow
-        self.key = None
+        self.key = None            # the device the side streams and ``store`` belong to
+        self.store = {}            # the allocations behind every buffer view: grow only, re-used by every utterance
+        self.layout_key = self.layout = None
         self.active = False
         self.profile = False       # True: hipEvents around every seed pass of the following utterances (pass_ms)
         self.lock = threading.Lock()   # held by synthesize() for the whole utterance (buffers, streams and plan are per model pair)
+        # per utterance: set by begin() (dtype, half, cap), enqueue() (cuts, the events, n_launch), finish() (Tout, seeded, void_blocks)
+        self.dtype, self.half, self.cap, self.lag = None, False, 0, None
+        self.dev = self.steps = self.Tin = self.taco_handle = self.wg_handle = None
+        self.cuts, self.n_extra, self.n_launch = [], 0, 0
+        self.last_final, self.finals, self.flow_events, self.pass_events = None, [], {}, []
+        self.Tout = self.seeded = self.void_blocks = 0
 
     @staticmethod
-    def usable(tacotron, waveglow):
-        """The streamed path exists for the reference's shapes on the folded, phase-major vocoder kernels."""
+    def _switched_on(tacotron, waveglow):
         if os.environ.get("FACPPG_STREAM", "1") == "0" or os.environ.get("FACPPG_WG_UNFOLDED", "0") not in ("", "0"):
             return False
         if os.environ.get("FACPPG_WG_EDGE_FOLD", "1") == "0" or getattr(tacotron, "decoder_workgroups", 0):
             return False
-        if ConditioningStream.precision(waveglow) is None:
-            return False    # fp32, or all fp16 (the reference's .half() recipe): bf16 and mixed modules run unstreamed (or are refused)
         return waveglow.WN[0].n_layers == 8 and waveglow.n_group == 8
 
     @staticmethod
-    def precision(waveglow):
-        """torch.float32 / torch.float16: the kernels the stream would feed; None: neither (bf16, mixed dtypes)."""
+    def usable(tacotron, waveglow):
+        """The streamed path exists for the reference's shapes on the folded, phase-major vocoder kernels, all fp32 or all fp16 (the
+        reference's .half() recipe): bf16 and mixed modules run unstreamed (or are refused)."""
+        return ConditioningStream._switched_on(tacotron, waveglow) and ConditioningStream.precision(waveglow) is not None
+
+    @staticmethod
+    def precision(waveglow, walk=True):
+        """torch.float32 / torch.float16: the kernels the stream would feed; None: neither (bf16, mixed dtypes).  walk=False takes
+        the upsampler's word for a half vocoder (callers whose next step, WaveGlow.infer, refuses a mixed module itself)."""
         dt = getattr(getattr(waveglow, "upsample", None), "weight", torch.empty(0)).dtype
-        if dt == torch.float16:      # every WN / upsample parameter must be (the walk is spent on half vocoders only)
+        if dt == torch.float16 and walk:      # every WN / upsample parameter must be (the walk is spent on half vocoders only)
             if hasattr(waveglow, "_precision"):
                 from facppg.lib import FacppgError
                 try:
@@ -114,7 +128,7 @@ class ConditioningStream(object):
                     return None
             dts = {p.dtype for p in waveglow.upsample.parameters()} | {p.dtype for wn in waveglow.WN for p in wn.parameters()}
             return dt if dts == {dt} else None
-        return dt if dt == torch.float32 else None
+        return dt if dt in (torch.float32, torch.float16) else None
 
     # Utterances shorter than this are not streamed (FACPPG_STREAM_MIN_FRAMES overrides), per vocoder precision.  fp32: see begin().
     # fp16: streamed wins at every length of the sweep (64 frames 5.8 -> 5.3 ms, 100: 6.7 -> 6.3, 130: 7.4 -> 7.0, 200: 9.2 -> 8.8,
@@ -157,7 +171,7 @@ class ConditioningStream(object):
         # (the layout queries validate the models' packed-weight handles -- ~1000 tensors, 0.2 - 0.4 ms of host time in front of the
         #  encoder: asked once per (step limit, layout), not per utterance)
         lk = (dev, steps, cap, self.half)
-        if self.__dict__.get("layout_key") != lk:
+        if self.layout_key != lk:
             self.layout = self.waveglow.seed_layout(cap, dev) + (L.facppg_taco_postnet_stream_workspace_bytes(self.tacotron._handle(dev), cap),)
             self.layout_key = lk
         self.tqp, self.margin, seed_bytes, post_ws_bytes = self.layout
@@ -182,11 +196,12 @@ class ConditioningStream(object):
 
     def footprint_bytes(self):
         """Device memory the stream holds on to between utterances."""
-        return sum(t.numel() * t.element_size() for t in getattr(self, "store", {}).values() if t.is_cuda)
+        return sum(t.numel() * t.element_size() for t in self.store.values() if t.is_cuda)
 
     def plan(self, steps, Tin):
         """[(frames of mel needed, first seeded frame, end of seeded frames)] -- blocks that can be formed before the utterance ends
-        if it runs to about min(steps, Tin) frames; whatever is not covered is left for finish()."""
+        if it runs to about min(steps, Tin) frames; whatever is not covered is left for finish().  Reads ``lag`` and ``cap`` (the
+        frames the vocoder-side buffers are laid out for), leaves ``n_extra``."""
         end = min(steps, max(Tin, 1))
         # 32-frame blocks keep every block's postnet chain clear of the previous block's pass (a block every 0.62 ms, chain + pass
         # 0.6 ms) at 2 GB of weight images per block; utterances of several seconds take 64-frame blocks (half the HBM traffic
@@ -203,7 +218,7 @@ class ConditioningStream(object):
                 w = max(32, min(widths.pop(0), rest))
             cuts.append((s + w + self.lag, s, s + w))
             s += w
-        s_lim = (min(steps, getattr(self, "cap", steps)) - self.lag) // 32 * 32   # the decoder may run on towards its step limit: a few more blocks (inside the layout)
+        s_lim = (min(steps, self.cap) - self.lag) // 32 * 32   # the decoder may run on towards its step limit: a few more blocks (inside the layout)
         extra = 0
         while s < s_lim and extra < 2 and len(cuts) < 120:
             w = min(chunk, s_lim - s)
@@ -220,11 +235,11 @@ class ConditioningStream(object):
         # Short utterances do not gain: up to 128 frames the unstreamed vocoder runs 16-frame tiles, one per CU, and a layer launch
         # lasts as long as ONE tile either way (measured, tools/stream_T_sweep.sh: 64 frames 6.9 -> 8.1 ms, 100 frames 8.2 -> 9.0
         # streamed; 130 frames 10.0 -> 9.7, 200 frames 13.3 -> 11.5, 1000 frames 53.9 -> 48.5).  FACPPG_STREAM_MIN_FRAMES overrides.
-        if not self.usable(tacotron, self.waveglow):
+        self.dtype = self.precision(self.waveglow) if self._switched_on(tacotron, self.waveglow) else None    # (usable(), keeping the answer)
+        if self.dtype is None:
             return None
-        # (usable: the vocoder is all fp32 or all fp16, whichever its upsampler is)
-        self.half = getattr(getattr(self.waveglow, "upsample", None), "weight", torch.empty(0)).dtype == torch.float16
-        if min(steps, Tin) < int(os.environ.get("FACPPG_STREAM_MIN_FRAMES", self.MIN_FRAMES[torch.float16 if self.half else torch.float32])):
+        self.half = self.dtype == torch.float16
+        if min(steps, Tin) < int(os.environ.get("FACPPG_STREAM_MIN_FRAMES", self.MIN_FRAMES[self.dtype])):
             return None
         self.cap = min(steps, -(-(Tin + self.SLACK) // 32) * 32)
         try:
@@ -247,10 +262,8 @@ class ConditioningStream(object):
     def enqueue(self, out_len, decoder_workgroups):
         """The decoder has been launched (on ``decoder_workgroups`` CUs) and publishes its frames: enqueue every planned block on
         the side stream."""
-        from facppg import lib as _lib
-        L = _lib.load()
-        dev, steps = self.dev, self.steps
-        self.cuts = self.plan(steps, self.Tin)
+        dev = self.dev
+        self.cuts = self.plan(self.steps, self.Tin)
         self.wg_handle = self.waveglow._handle(dev)
         f_prev = 0
         lpw = max(1, int(os.environ.get("FACPPG_STREAM_LPW", "1")))
@@ -261,64 +274,77 @@ class ConditioningStream(object):
         spare = int(os.environ.get("FACPPG_STREAM_SPARE_CUS", "8"))
         bound = max(16, n_cu - decoder_workgroups - spare) if spare >= 0 else 0
         self.n_launch = 0
-        self.last_final, self.finals, self.flow_events = None, [], {}
-
-        def seed_pass(job):
-            s_a, n, bt, void, lo, hi = job
-            if self.profile:
-                e0 = torch.cuda.Event(enable_timing=True)
-                e0.record(self.side)
-            self.waveglow.cond_seed(self.melp16 if self.half else self.melp, self.cap, s_a, n, self.seeds, block_tiles=bt, layers_per_workgroup=lpw, skip=void,
-                                    handle=self.wg_handle, flows=(lo, hi - lo), max_workgroups=bound,
-                                    counter=self.counters[self.n_launch:self.n_launch + 1] if self.n_launch < 500 else None)
-            self.n_launch += 1
-            if self.profile:
-                e1 = torch.cuda.Event(enable_timing=True)
-                e1.record(self.side)
-                self.pass_events.append((n, hi - lo, e0, e1))
-        self.seed_pass = seed_pass
-        self.pass_events = []
+        self.last_final, self.finals, self.flow_events, self.pass_events = None, [], {}, []
         self.post.wait_event(self.ready)
-        with torch.cuda.device(dev):
-            for k, (f_new, s_a, s_b) in enumerate(self.cuts):
-                void = self.void[k:k + 1]
-                with torch.cuda.stream(self.post):
-                    st = _lib.current_stream(dev)
-                    _lib.check(L.facppg_taco_collect_frames(self.taco_handle, _lib.ptr(self.words), _lib.ptr(out_len), f_prev, f_new,
-                                                            _lib.ptr(self.mel), steps, _lib.ptr(void),
-                                                            _lib.ptr(self.void[k - 1:k]) if k else None, st))
-                    _lib.check(L.facppg_taco_postnet_range(self.taco_handle, _lib.ptr(self.mel), steps, f_prev, f_new, 0,
-                                                           self.melp.data_ptr() + 4 * self.margin, self.tqp, _lib.ptr(self.post_ws),
-                                                           self.post_ws.numel(), self.cap, _lib.ptr(void), st))
-                    if self.half:   # the columns that call made final, rounded into the half vocoder's buffer
-                        c0 = max(0, f_prev - self.lag)
-                        self.waveglow.mel_convert(self.melp[:, self.margin:], self.cap, c0, f_new - self.lag - c0, self.melp16, skip=void,
-                                                  handle=self.wg_handle)
-                    # (the block's void flag travels to pinned host memory behind its collector, on this stream: when the decoder has
-                    #  ended the flags of the blocks it covered have been on the host for milliseconds -- finish() reads them there
-                    #  instead of spending a second device->host round trip between the decoder and the vocoder)
-                    self.void_host[k:k + 1].copy_(void, non_blocking=True)
-                    final = torch.cuda.Event()
-                    final.record(self.post)
-                    self.last_final = final
-                    self.finals.append(final)
-                with torch.cuda.stream(self.side):
-                    self.side.wait_event(final)                # mel_post is final up to s_b
-                    seed_pass((s_a, s_b - s_a, min(4, (s_b - s_a) // 32), void, 0, self.waveglow.n_flows))
-                    ev = torch.cuda.Event()
-                    ev.record(self.side)
-                    self.flow_events = {self.waveglow.n_flows - 1: ev}   # the vocoder's first launches (last flow) wait for the last pass
-                f_prev = f_new
+        for k, (f_new, s_a, s_b) in enumerate(self.cuts):
+            void = self.void[k:k + 1]
+            with torch.cuda.stream(self.post):
+                self._mel_block(out_len, f_prev, f_new, void=void, void_before=self.void[k - 1:k] if k else None)
+                # (the block's void flag travels to pinned host memory behind its collector, on this stream: when the decoder has
+                #  ended the flags of the blocks it covered have been on the host for milliseconds -- finish() reads them there
+                #  instead of spending a second device->host round trip between the decoder and the vocoder)
+                self.void_host[k:k + 1].copy_(void, non_blocking=True)
+                final = torch.cuda.Event()
+                final.record(self.post)
+                self.last_final = final
+                self.finals.append(final)
+            with torch.cuda.stream(self.side):
+                self.side.wait_event(final)                # mel_post is final up to s_b
+                self._seed_pass(s_a, s_b - s_a, min(4, (s_b - s_a) // 32), lpw, bound, skip=void, timed=self.profile)
+                ev = torch.cuda.Event()
+                ev.record(self.side)
+                self.flow_events = {self.waveglow.n_flows - 1: ev}   # the vocoder's first launches (last flow) wait for the last pass
+            f_prev = f_new
         self.active = True
+
+    def _mel_block(self, out_len, f0, f1, Tout=0, void=None, void_before=None):
+        """Decoder frames [f0, f1) on the current stream: collected, through the streaming postnet into the vocoder's mel buffer, and
+        the postnet columns they make final rounded into a half vocoder's.  Tout (finish(): f1 is the utterance's end) makes every
+        column up to f1 final; under the decoder the postnet trails by ``lag`` frames.  void / void_before: the block's flag and the
+        flag of the block in front of it (a block whose frames do not arrive in time raises its flag and writes nothing)."""
+        from facppg import lib as _lib
+        L = _lib.load()
+        with torch.cuda.device(self.dev):
+            st = _lib.current_stream(self.dev)
+            if f1 > f0:
+                _lib.check(L.facppg_taco_collect_frames(self.taco_handle, _lib.ptr(self.words), _lib.ptr(out_len), f0, f1,
+                                                        _lib.ptr(self.mel), self.steps, _lib.ptr(void), _lib.ptr(void_before), st))
+            _lib.check(L.facppg_taco_postnet_range(self.taco_handle, _lib.ptr(self.mel), self.steps, f0, f1, Tout,
+                                                   self.melp.data_ptr() + 4 * self.margin, self.tqp, _lib.ptr(self.post_ws),
+                                                   self.post_ws.numel(), self.cap, _lib.ptr(void), st))
+        if self.half:
+            c0 = max(0, f0 - self.lag)
+            self.waveglow.mel_convert(self.melp[:, self.margin:], self.cap, c0, (f1 if Tout else f1 - self.lag) - c0, self.melp16, skip=void,
+                                      handle=self.wg_handle)
+
+    def _seed_pass(self, frame0, nframes, block_tiles, layers_per_workgroup, max_workgroups, skip=None, timed=False):
+        """One k_cond_seed launch over frames [frame0, frame0 + nframes), every flow, on the current stream.  max_workgroups None:
+        an unbounded launch; otherwise (0 included: the bound may come from the environment) the launch takes the utterance's next
+        zeroed work counter, and runs unbounded once the counters are used up.  timed: hipEvents around it for pass_ms()."""
+        counter = None
+        if max_workgroups is not None:
+            if self.n_launch < 500:
+                counter = self.counters[self.n_launch:self.n_launch + 1]
+            else:
+                max_workgroups = 0
+            self.n_launch += 1
+        if timed:
+            stream = torch.cuda.current_stream(self.dev)
+            e0 = torch.cuda.Event(enable_timing=True)
+            e0.record(stream)
+        self.waveglow.cond_seed(self.melp16 if self.half else self.melp, self.cap, frame0, nframes, self.seeds, block_tiles=block_tiles,
+                                layers_per_workgroup=layers_per_workgroup, skip=skip, handle=self.wg_handle,
+                                max_workgroups=max_workgroups or 0, counter=counter)
+        if timed:
+            e1 = torch.cuda.Event(enable_timing=True)
+            e1.record(stream)
+            self.pass_events.append((nframes, self.waveglow.n_flows, e0, e1))
 
     def finish(self, Tout, out_len):
         """The decoder has ended at Tout frames (known on the host): what the blocks could not cover, on the caller's stream.
         Returns mel_post [1, NF, Tout] (a view of the vocoder's mel buffer, valid until the next streamed utterance on these models),
         or None when the utterance outgrew the stream's layout: the caller then runs the one-shot postnet and the ordinary vocoder."""
-        from facppg import lib as _lib
-        L = _lib.load()
-        dev, steps = self.dev, self.steps
-        cur = torch.cuda.current_stream(dev)
+        cur = torch.cuda.current_stream(self.dev)
         if Tout > self.cap:       # the decoder ran on past the frames the buffers were laid out for (PPG length + SLACK): unstreamed
             cur.wait_stream(self.post)
             cur.wait_stream(self.side)
@@ -338,20 +364,8 @@ class ConditioningStream(object):
             self.finals[n_cov - 1].synchronize()          # (block k's flag is copied to the host ahead of its event)
             first_void = next((k for k in range(n_cov) if int(self.void_host[k])), n_cov)
             self.void_blocks, n_cov = n_cov - first_void, first_void
-        f_done = s_done = 0
-        for f_new, s_a, s_b in self.cuts[:n_cov]:
-            f_done, s_done = f_new, s_b
-        with torch.cuda.device(dev):
-            st = _lib.current_stream(dev)
-            if Tout > f_done:
-                _lib.check(L.facppg_taco_collect_frames(self.taco_handle, _lib.ptr(self.words), _lib.ptr(out_len), f_done, Tout,
-                                                        _lib.ptr(self.mel), steps, None, None, st))
-            _lib.check(L.facppg_taco_postnet_range(self.taco_handle, _lib.ptr(self.mel), steps, f_done, Tout, Tout,
-                                                   self.melp.data_ptr() + 4 * self.margin, self.tqp, _lib.ptr(self.post_ws),
-                                                   self.post_ws.numel(), self.cap, None, st))
-            if self.half:
-                c0 = max(0, f_done - self.lag)
-                self.waveglow.mel_convert(self.melp[:, self.margin:], self.cap, c0, Tout - c0, self.melp16, handle=self.wg_handle)
+        f_done, _, s_done = self.cuts[n_cov - 1] if n_cov else (0, 0, 0)
+        self._mel_block(out_len, f_done, Tout, Tout=Tout)
         self.Tout, self.seeded = Tout, s_done
         return self.melp[:, self.margin:self.margin + Tout].unsqueeze(0)
 
@@ -364,49 +378,45 @@ class ConditioningStream(object):
         return out
 
     # ---- called by the vocoder stage
-    def vocode(self, sigma, z=None, seed=None):
-        """WaveGlow.infer of the streamed utterance from the seeds (the frames behind the last block get theirs here)."""
-        T, s_done = self.Tout, self.seeded
-        if self.half:
-            # The frames behind the last block.  Seeded and unseeded tiles of the fp16 launches are both 32 frames wide, so a launch
-            # with ONE unseeded tile lasts as long as an unseeded launch (every tile has a CU of its own at these lengths): the
-            # tail tiles get their seeds from one more pass in front of the vocoder instead (200 frames, two tail tiles: 8.8 ms
-            # against 9.1 ms end to end with the in-kernel tail, profiles/r11_stream_f16_ab.txt).  FACPPG_STREAM_TAIL=mixed runs
-            # them unseeded, conditioning-first, inside the layer launches -- same samples.  Half audio, widened as the
-            # unstreamed path's is.
-            s_all = -(-T // 32) * 32
-            if s_all > s_done and os.environ.get("FACPPG_STREAM_TAIL", "seed") != "mixed":
-                # (one workgroup per CU walking the work items from a counter: the pass streams the images fastest that way)
-                n_cu = torch.cuda.get_device_properties(self.dev).multi_processor_count
-                bounded = self.n_launch < 500
-                self.waveglow.cond_seed(self.melp16, self.cap, s_done, s_all - s_done, self.seeds, block_tiles=min(4, (s_all - s_done) // 32),
-                                        layers_per_workgroup=1, handle=self.wg_handle, max_workgroups=n_cu if bounded else 0,
-                                        counter=self.counters[self.n_launch:self.n_launch + 1] if bounded else None)
-                self.n_launch += 1
-                s_done = s_all
-            self.active = False
-            return self.waveglow.infer_seeded(self.melp16, T, self.seeds, s_done, sigma=sigma, z=z, seed=seed, handle=self.wg_handle,
-                                              T_layout=self.cap, flow_events=self.flow_events).float()
+    @staticmethod
+    def tail_pass(precision, T, seeded, P, n_cu, tail=None):
+        """How the frames behind the last block -- [seeded, T) -- get their conditioning sums: None = inside the vocoder's layer
+        launches, as unseeded tiles (or nothing is left); otherwise the seed pass to run in front of the vocoder, (first frame,
+        frames, block_tiles, layers_per_workgroup, bounded).  P: phases (hop / 8); n_cu: CUs of the device; tail: the value of
+        FACPPG_STREAM_TAIL ("seed" / "mixed" force either side; default fp32 "auto", fp16 "seed").
+
+        fp32: unseeded 16-frame tiles inside the layer launches (k_wn_layer_mixed) while the mixed launch needs no more ROUNDS of one
+        workgroup per CU than the all-seeded one would (measured: 230 frames, 288 against 256 workgroups: 17.5 against 13.4 ms per
+        step; 300 / 350 / 450 frames, two rounds either way: the mixed launch is 0.35 - 0.85 ms ahead of the extra pass); needs
+        seeded tiles in front (0 < seeded < T).
+        fp16: seeded and unseeded tiles of the fp16 launches are both 32 frames wide, so a launch with ONE unseeded tile lasts as long
+        as an unseeded launch (every tile has a CU of its own at these lengths): one more pass, one workgroup per CU walking the
+        work items from a counter -- the pass streams the images fastest that way (200 frames, two tail tiles: 8.8 ms against
+        9.1 ms end to end with the in-kernel tail, profiles/r11_stream_f16_ab.txt).  Same samples either way."""
         s_all = -(-T // 32) * 32
-        # The frames behind the last block: as unseeded 16-frame tiles inside the layer launches themselves (k_wn_layer_mixed) while
-        # the launch still gives every CU at most one workgroup; otherwise (and with FACPPG_STREAM_TAIL=seed) one more seed pass
-        # over them in front of the vocoder.
-        P = self.waveglow.upsample.stride[0] // 8
-        mixed_wgs = P * (s_done // 32 + -(-(T - s_done) // 16))
+        if s_all <= seeded:
+            return None
+        if precision == torch.float16:
+            return None if tail == "mixed" else (seeded, s_all - seeded, min(4, (s_all - seeded) // 32), 1, True)
+        mixed_wgs = P * (seeded // 32 + -(-(T - seeded) // 16))
         seeded_wgs = P * (s_all // 32)
+        in_kernel = 0 < seeded < T and tail != "seed" and (tail == "mixed" or -(-mixed_wgs // n_cu) <= -(-seeded_wgs // n_cu))
+        return None if in_kernel else (seeded, s_all - seeded, 1, 2, False)
+
+    def vocode(self, sigma, z=None, seed=None):
+        """WaveGlow.infer of the streamed utterance from the seeds (the frames behind the last block get theirs here, or run
+        unseeded: tail_pass); fp32 audio (a half vocoder's is widened as the unstreamed path's is)."""
         n_cu = torch.cuda.get_device_properties(self.dev).multi_processor_count
-        tail = os.environ.get("FACPPG_STREAM_TAIL", "auto")
-        # ... i.e. while the mixed launch needs no more ROUNDS of one workgroup per CU than the all-seeded one would (measured: 230
-        # frames, 288 against 256 workgroups: 17.5 against 13.4 ms per step; 300 / 350 / 450 frames, two rounds either way: the
-        # mixed launch is 0.35 - 0.85 ms ahead of the extra pass)
-        in_kernel = s_done > 0 and s_done < T and tail != "seed" and (tail == "mixed" or -(-mixed_wgs // n_cu) <= -(-seeded_wgs // n_cu))
-        if s_all > s_done and not in_kernel:
-            self.waveglow.cond_seed(self.melp, self.cap, s_done, s_all - s_done, self.seeds, block_tiles=1, layers_per_workgroup=2,
-                                    handle=self.wg_handle)
-            s_done = s_all
+        s_done = self.seeded
+        job = self.tail_pass(self.dtype, self.Tout, s_done, self.waveglow.upsample.stride[0] // 8, n_cu, os.environ.get("FACPPG_STREAM_TAIL"))
+        if job is not None:
+            frame0, nframes, block_tiles, lpw, bounded = job
+            self._seed_pass(frame0, nframes, block_tiles, lpw, n_cu if bounded else None)
+            s_done = frame0 + nframes
         self.active = False
-        return self.waveglow.infer_seeded(self.melp, T, self.seeds, s_done, sigma=sigma, z=z, seed=seed, handle=self.wg_handle,
-                                          T_layout=self.cap, flow_events=self.flow_events)
+        audio = self.waveglow.infer_seeded(self.melp16 if self.half else self.melp, self.Tout, self.seeds, s_done, sigma=sigma, z=z, seed=seed,
+                                           handle=self.wg_handle, T_layout=self.cap, flow_events=self.flow_events)
+        return audio.float() if self.half else audio
 
 
 class StageTimer(object):
@@ -475,8 +485,9 @@ def _vocode(mel_post, tout, waveglow, denoiser, sigma, strength, seed, z, uttera
     hop = waveglow.upsample.stride[0]
     multi = len(tout) > 1
     wg_seeds = None if utterance_seeds is None else [int(v) + 1 for v in utterance_seeds]
-    half = waveglow.upsample.weight.dtype != torch.float32   # a .half() vocoder: half mel in, its half audio widened to fp32
     streamed = consumer is not None and consumer.active
+    # a .half() vocoder: half mel in, its half audio widened to fp32 (infer refuses a module that is neither all fp32 nor all fp16)
+    half = (consumer.dtype if streamed else ConditioningStream.precision(waveglow, walk=False)) == torch.float16
     if half and not streamed:
         mel_post = mel_post.to(waveglow.upsample.weight.dtype)
     if streamed:

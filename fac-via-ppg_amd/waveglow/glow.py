@@ -1216,7 +1216,7 @@ class WaveGlow(torch.nn.Module):
         return out
 
     def _infer_workspace(self, B, T, dev, slot, handle=None):
-        nbytes = _lib.load().facppg_wg_workspace_bytes(handle if handle is not None else self._handle(dev), B, T)
+        nbytes = _lib.load().facppg_wg_workspace_bytes(self._resolve(dev, handle)[0], B, T)
         wss = self.__dict__.setdefault("_facppg_ws", {})
         ws = wss.get(slot)
         if ws is None or ws.numel() < nbytes or ws.device != dev:
@@ -1224,41 +1224,59 @@ class WaveGlow(torch.nn.Module):
             wss[slot] = ws
         return ws
 
-    def _infer_launch(self, spect, lt, zt, seed, sigma, audio, ws, handle=None):
-        """The launch sequence of one batch on the current stream; no host-side waits."""
+    def _infer_launch(self, spect, lt, zt, seed, sigma, audio, ws, handle=None, cond_first=False):
+        """The launch sequence of one batch on the current stream; no host-side waits.  fp16 images: facppg_wg_infer_f16_order,
+        which takes the K order of the gate GEMMs (cond_first)."""
         dev = spect.device
         B, _, T = spect.shape
+        h, dt, _ = self._resolve(dev, handle)
+        L = _lib.load()
+        order = (1 if cond_first else 0,) if dt == torch.float16 else ()
         with torch.cuda.device(dev):
-            _lib.check(_lib.load().facppg_wg_infer(handle if handle is not None else self._handle(dev), _lib.ptr(spect), _lib.ptr(lt), _lib.ptr(zt),
-                                                   seed & 0xFFFFFFFFFFFFFFFF, float(sigma), B, T, _lib.ptr(audio),
-                                                   _lib.ptr(ws), ws.numel(), _lib.current_stream(dev)))
+            _lib.check((L.facppg_wg_infer_f16_order if order else L.facppg_wg_infer)(
+                h, _lib.ptr(spect), _lib.ptr(lt), _lib.ptr(zt), seed & 0xFFFFFFFFFFFFFFFF, float(sigma), B, T, *order, _lib.ptr(audio),
+                _lib.ptr(ws), ws.numel(), _lib.current_stream(dev)))
 
     # ---- seeded inference of ONE utterance: the conditioning part of every layer's gate GEMM formed ahead of time
+    # (seed layout, cond seed, infer seeded): the C entry points by the precision of the handle's weight images
+    _SEEDED_ENTRY = {torch.float32: ("facppg_wg_seed_layout", "facppg_wg_cond_seed", "facppg_wg_infer_seeded"),
+                     torch.float16: ("facppg_wg_seed_layout_f16", "facppg_wg_cond_seed_f16", "facppg_wg_infer_seeded_f16")}
+
+    def _resolve(self, dev, handle=None):
+        """(handle, dtype of its weight images, its _SEEDED_ENTRY functions) of ``handle`` -- the module's current one, anything else
+        is refused -- or, with None, of the module's handle for ``dev`` (validated or built now)."""
+        h = handle if handle is not None else self._handle(dev)
+        dt = torch.float16 if self._half_handle(h) else torch.float32
+        L = _lib.load()
+        return h, dt, [getattr(L, name) for name in self._SEEDED_ENTRY[dt]]
+
+    def _seed_layout(self, h, layout, T):
+        c = _lib.ctypes
+        tqp, mg, nb = c.c_int(), c.c_int(), c.c_size_t()
+        _lib.check(layout(h, int(T), c.byref(tqp), c.byref(mg), c.byref(nb)))
+        return tqp.value, mg.value, nb.value
+
     def seed_layout(self, T, device):
         """(Tqp, margin, seed_bytes) for an utterance of T frames: the zero-margined mel buffer is [n_mel, Tqp] with frame q at
         column margin + q; the seed buffer has seed_bytes bytes (facppg_wg_seed_layout)."""
-        c = _lib.ctypes
-        tqp, mg, nb = c.c_int(), c.c_int(), c.c_size_t()
-        h = self._handle(device)
-        L = _lib.load()
-        layout = L.facppg_wg_seed_layout_f16 if self._half_handle(h) else L.facppg_wg_seed_layout
-        _lib.check(layout(h, int(T), c.byref(tqp), c.byref(mg), c.byref(nb)))
-        return tqp.value, mg.value, nb.value
+        h, _, (layout, _, _) = self._resolve(device)
+        return self._seed_layout(h, layout, T)
 
     def mel_pad(self, mel, handle=None):
         """mel [1, n_mel, T] -> the zero-margined [n_mel, Tqp] buffer cond_seed / infer_seeded read; of a .half() module: an fp32
         (or half) mel -> the fp16 [Tqp, n_mel] buffer, rounded to nearest even."""
         dev = mel.device
         T = mel.shape[2]
-        tqp, _, _ = self.seed_layout(T, dev)
-        if self._half_handle(self._handle(dev)):
+        h, dt, (layout, _, _) = self._resolve(dev, handle)
+        tqp = self._seed_layout(h, layout, T)[0]
+        if dt == torch.float16:
             out = torch.zeros(tqp, mel.shape[1], dtype=torch.float16, device=dev)
-            self.mel_convert(mel[0].float(), T, 0, T, out)
+            self.mel_convert(mel[0].float(), T, 0, T, out, handle=h)
             return out
         out = torch.empty(mel.shape[1], tqp, dtype=torch.float32, device=dev)
         m = mel[0]
         with torch.cuda.device(dev):
-            _lib.check(_lib.load().facppg_wg_mel_pad(self._handle(dev), _lib.ptr(m), T, m.stride(0), _lib.ptr(out), _lib.current_stream(dev)))
+            _lib.check(_lib.load().facppg_wg_mel_pad(h, _lib.ptr(m), T, m.stride(0), _lib.ptr(out), _lib.current_stream(dev)))
         return out
 
     def mel_convert(self, mel, T, frame0, nframes, melp, skip=None, handle=None):
@@ -1268,7 +1286,7 @@ class WaveGlow(torch.nn.Module):
         if mel.dtype != torch.float32 or melp.dtype != torch.float16 or mel.stride(1) != 1:
             raise _lib.FacppgError("mel_convert: fp32 rows in, the fp16 mel buffer out")
         with torch.cuda.device(dev):
-            _lib.check(_lib.load().facppg_wg_mel_pad_f16(handle if handle is not None else self._handle(dev), _lib.ptr(mel), int(T),
+            _lib.check(_lib.load().facppg_wg_mel_pad_f16(self._resolve(dev, handle)[0], _lib.ptr(mel), int(T),
                                                          mel.stride(0), int(frame0), int(nframes), _lib.ptr(melp), _lib.ptr(skip),
                                                          _lib.current_stream(dev)))
 
@@ -1281,17 +1299,18 @@ class WaveGlow(torch.nn.Module):
         its fp16 mel buffer (mel_pad / mel_convert) and forms the raw conditioning sums, no bias (k16_cond_seed)."""
         dev = melp.device
         f0, nf = flows if flows is not None else (0, 0)
-        h = handle if handle is not None else self._handle(dev)
-        L = _lib.load()
-        half = self._half_handle(h)
-        if melp.dtype != (torch.float16 if half else torch.float32):
-            raise _lib.FacppgError("cond_seed: the module is %s, its mel buffer is %s" % ("fp16" if half else "fp32", melp.dtype))
-        seed_fn = L.facppg_wg_cond_seed_f16 if half else L.facppg_wg_cond_seed
+        h, dt, (_, seed_fn, _) = self._resolve(dev, handle)
+        self._check_mel_buffer("cond_seed", melp, dt)
         with torch.cuda.device(dev):
             _lib.check(seed_fn(h, _lib.ptr(melp), int(T), int(frame0),
                        int(nframes), int(block_tiles), int(layers_per_workgroup), int(f0), int(nf), _lib.ptr(seeds),
                        seeds.numel() * seeds.element_size(), _lib.ptr(skip), int(max_workgroups), _lib.ptr(counter),
                        _lib.current_stream(dev)))
+
+    @staticmethod
+    def _check_mel_buffer(who, melp, dt):
+        if melp.dtype != dt:
+            raise _lib.FacppgError("%s: the module is %s, its mel buffer is %s" % (who, "fp16" if dt == torch.float16 else "fp32", melp.dtype))
 
     def infer_seeded(self, melp, T, seeds, seeded_frames, sigma=1.0, z=None, seed=None, handle=None, T_layout=None, flow_events=None):
         """WaveGlow.infer of ONE utterance (glow.py:252-293) whose layers start from ``seeds``: audio [1, T*hop].  Same samples
@@ -1300,25 +1319,11 @@ class WaveGlow(torch.nn.Module):
         A .half() module (fp16 ``melp``): half audio, the samples of infer(mel.half(), cond_first=True); seeded_frames may be 0."""
         T_layout = T if T_layout is None else int(T_layout)
         dev = melp.device
-        hop = self.upsample.stride[0]
-        h = handle if handle is not None else self._handle(dev)
-        half = self._half_handle(h)
-        dt = torch.float16 if half else torch.float32
-        if melp.dtype != dt:
-            raise _lib.FacppgError("infer_seeded: the module is %s, its mel buffer is %s" % ("fp16" if half else "fp32", melp.dtype))
-        zt = None
-        if z is not None:
-            if isinstance(z, (list, tuple)):
-                z = torch.cat([t.to(dev).to(dt).reshape(-1) for t in z])
-            zt = z.to(device=dev, dtype=dt).contiguous()
-            if zt.numel() != self.n_group * (T * hop // self.n_group):
-                raise _lib.FacppgError("z has %d values, expected n_group*L = %d" % (zt.numel(), self.n_group * (T * hop // self.n_group)))
-        if seed is None:
-            seed = int(torch.empty((), dtype=torch.int64).random_().item())
+        h, dt, (_, _, infer_fn) = self._resolve(dev, handle)
+        self._check_mel_buffer("infer_seeded", melp, dt)
+        zt, _, seed, _ = self._infer_args(1, T, dt, z, None, seed, None, dev)
         ws = self._infer_workspace(1, T_layout, dev, 0, h)
-        audio = torch.empty(1, T * hop, dtype=dt, device=dev)
-        L = _lib.load()
-        infer_fn = L.facppg_wg_infer_seeded_f16 if half else L.facppg_wg_infer_seeded
+        audio = torch.empty(1, T * self.upsample.stride[0], dtype=dt, device=dev)
         evs = None
         if flow_events:
             evs = (_lib.ctypes.c_void_p * self.n_flows)()
@@ -1344,9 +1349,45 @@ class WaveGlow(torch.nn.Module):
             return pre[0]
         return self._handle(dev)
 
+    def _infer_args(self, B, T, dtype, z, lengths, seed, utterance_seeds, device=None):
+        """The arguments infer() and infer_seeded() share, checked and normalised -> (z, lengths, seed, utterance_seeds):
+          z                None, or the injected noise as ONE flat contiguous ``dtype`` tensor (fp32: .float(); fp16: rounded to
+                           half, as the reference's draw is);
+          lengths          None, the host-side lengths as a list of ints, or the caller's tensor as contiguous int32;
+          seed             the caller's, or a fresh one from torch's generator;
+          utterance_seeds  the caller's; for ``seed`` alone on a ragged batch with host-side lengths, streams derived from
+                           (seed, b) -- the same for both precisions and whatever launch plan infer() picks.
+        Everything that needs no device is checked first; only then do z and a lengths tensor move to ``device`` (None: they stay
+        where they are, so CPU tensors are checked on the CPU) and is the lengths tensor read back for its range."""
+        n = B * self.n_group * (T * self.upsample.stride[0] // self.n_group)
+        host = lengths is not None and not torch.is_tensor(lengths)
+        if host:
+            lengths = [int(v) for v in lengths]
+            if len(lengths) != B or max(lengths) > T or min(lengths) < 1:
+                raise _lib.FacppgError("lengths must be B values in [1, T]")
+        if utterance_seeds is not None:
+            if z is not None or len(utterance_seeds) != B:
+                raise _lib.FacppgError("utterance_seeds: B integers, and not together with z")
+        elif z is not None:
+            parts = list(z) if isinstance(z, (list, tuple)) else [z]
+            if sum(t.numel() for t in parts) != n:
+                raise _lib.FacppgError("z has %d values, expected B*n_group*L = %d" % (sum(t.numel() for t in parts), n))
+            parts = [t.to(device=device, dtype=dtype).reshape(-1) for t in parts]
+            z = (parts[0] if len(parts) == 1 else torch.cat(parts)).contiguous()
+        if seed is None:
+            seed = int(torch.empty((), dtype=torch.int64).random_().item())
+        if utterance_seeds is None and z is None and host and B >= 2:
+            utterance_seeds = [(int(seed) * 0x9E3779B97F4A7C15 + (b + 1) * 0xBF58476D1CE4E5B9) & 0x7FFFFFFFFFFFFFFF for b in range(B)]
+        if lengths is not None and not host:
+            lengths = lengths.to(device=device, dtype=torch.int32).contiguous()
+            if lengths.numel() != B or int(lengths.max()) > T or int(lengths.min()) < 1:
+                raise _lib.FacppgError("lengths must be B values in [1, T]")
+        return z, lengths, seed, utterance_seeds
+
     def infer(self, spect, sigma=1.0, z=None, lengths=None, seed=None, utterance_seeds=None, groups=None, cond_first=False):
         """mel [B, n_mel, T] (GPU, fp32) -> audio [B, T*hop]   (glow.py:252-293); a .half() module takes a half mel and returns
-        half audio (the reference's HalfTensor branch, see _infer_half).
+        half audio on the fp16 MFMA kernels (glow.py:261-290, the reference's HalfTensor branch), with the same z / seed / lengths /
+        utterance_seeds semantics and one launch sequence (groups 1).
         groups: None = decide from the launch shape (ragged batches whose layer launches would idle through >= 3 % of their
         time in the last round run as two concurrent half-batches, see _infer_two_groups), 1 = one launch sequence, 2 = force
         the two half-batches (needs host-side lengths).  cond_first (.half() modules): the K order of the gate GEMMs -- False: taps,
@@ -1356,8 +1397,15 @@ class WaveGlow(torch.nn.Module):
         layout); a ragged batch with host-side lengths draws per-utterance streams derived from (seed, b), identical in both modes."""
         _lib.require_cuda(spect, "WaveGlow.infer: spect")
         if spect.dtype != torch.float32 or self.upsample.weight.dtype != torch.float32:
-            return self._infer_half(spect, sigma, z, lengths, seed, utterance_seeds, groups, cond_first)
-        if cond_first:
+            if self._precision() != torch.float16:
+                raise _lib.FacppgError("WaveGlow.infer: fp32 only for this module (its WN / upsample parameters are fp32; "
+                                       "got a %s mel) -- .half() the module for half inference" % spect.dtype)
+            if spect.dtype != torch.float16:
+                raise _lib.FacppgError("WaveGlow.infer: the module is fp16 (.half()), the mel must be fp16 too (got %s)" % spect.dtype)
+            if groups not in (None, 1):
+                raise _lib.FacppgError("WaveGlow.infer: groups=%r: the fp16 path runs one launch sequence (groups=1)" % (groups,))
+            groups = 1
+        elif cond_first:
             raise _lib.FacppgError("WaveGlow.infer: cond_first=True is the K order of a .half() module's kernels; the fp32 path sums "
                                    "the conditioning chunks first already")
         dev = spect.device
@@ -1365,100 +1413,19 @@ class WaveGlow(torch.nn.Module):
         spect = spect.contiguous()      #  prepare(); consumed HERE so that no path -- two half-batches included -- leaves the token behind)
         B, _, T = spect.shape
         hop = self.upsample.stride[0]
-        host_lengths = lengths is not None and not torch.is_tensor(lengths)
-        if host_lengths and (len(lengths) != B or max(int(n) for n in lengths) > T or min(int(n) for n in lengths) < 1):
-            raise _lib.FacppgError("lengths must be B values in [1, T]")
+        zt, lengths, seed, utterance_seeds = self._infer_args(B, T, spect.dtype, z, lengths, seed, utterance_seeds, dev)
+        host_lengths = isinstance(lengths, list)
         if groups is None:
             groups = 2 if (host_lengths and B >= 4 and self._tail_loss(lengths, hop) >= 0.03) else 1
-        if groups == 2 and (not host_lengths or B < 2):
-            raise _lib.FacppgError("WaveGlow.infer: groups=2 needs B >= 2 utterances and their lengths as a host list")
-        zt = None
-        if utterance_seeds is not None:
-            if z is not None or len(utterance_seeds) != B:
-                raise _lib.FacppgError("utterance_seeds: B integers, and not together with z")
-        elif z is not None:
-            if isinstance(z, (list, tuple)):
-                z = torch.cat([t.to(dev).float().reshape(-1) for t in z])
-            zt = z.to(dev).float().contiguous()
-            if zt.numel() != B * self.n_group * (T * hop // self.n_group):
-                raise _lib.FacppgError("z has %d values, expected B*n_group*L = %d" % (
-                    zt.numel(), B * self.n_group * (T * hop // self.n_group)))
-        if seed is None:
-            seed = int(torch.empty((), dtype=torch.int64).random_().item())
-        if utterance_seeds is None and zt is None and host_lengths and B >= 2:
-            # `seed` alone on a ragged batch: give every utterance its own stream derived from (seed, b), so that the noise --
-            # and the audio -- do not depend on whether the launch-shape heuristic above picks one launch sequence or two
-            # half-batches (whose batch layouts differ)
-            utterance_seeds = [(int(seed) * 0x9E3779B97F4A7C15 + (b + 1) * 0xBF58476D1CE4E5B9) & 0x7FFFFFFFFFFFFFFF for b in range(B)]
         if groups == 2:
-            return self._infer_two_groups(spect, sigma, zt, lengths, seed, utterance_seeds)
+            if not host_lengths or B < 2:
+                raise _lib.FacppgError("WaveGlow.infer: groups=2 needs B >= 2 utterances and their lengths as a host list")
+            return self._infer_two_groups(spect, sigma, zt, lengths, seed, utterance_seeds)   # (draws the noise per half-batch)
         if utterance_seeds is not None:
-            zt = self.draw_noise(utterance_seeds, T, dev)
-        lt = None
-        if lengths is not None:
-            if host_lengths:
-                lt = _lib.upload([int(n) for n in lengths], torch.int32, dev)
-            else:
-                lt = lengths.to(device=dev, dtype=torch.int32).contiguous()
-                if lt.numel() != B or int(lt.max()) > T or int(lt.min()) < 1:
-                    raise _lib.FacppgError("lengths must be B values in [1, T]")
-        audio = torch.zeros(B, T * hop, dtype=torch.float32, device=dev) if lt is not None else \
-            torch.empty(B, T * hop, dtype=torch.float32, device=dev)
-        self._infer_launch(spect, lt, zt, seed, sigma, audio, self._infer_workspace(B, T, dev, 0, h), h)
-        return audio
-
-    def _infer_half(self, spect, sigma, z, lengths, seed, utterance_seeds, groups, cond_first=False):
-        """infer() of a .half() module (glow.py:261-290, the HalfTensor branch): half mel [B, n_mel, T] -> half audio
-        [B, T*hop] on the fp16 MFMA kernels (facppg_wg_infer_f16).  Same z / seed / lengths / utterance_seeds semantics as
-        the fp32 path; one launch sequence (groups 1)."""
-        if self._precision() != torch.float16:
-            raise _lib.FacppgError("WaveGlow.infer: fp32 only for this module (its WN / upsample parameters are fp32; "
-                                   "got a %s mel) -- .half() the module for half inference" % spect.dtype)
-        if spect.dtype != torch.float16:
-            raise _lib.FacppgError("WaveGlow.infer: the module is fp16 (.half()), the mel must be fp16 too (got %s)" % spect.dtype)
-        if groups not in (None, 1):
-            raise _lib.FacppgError("WaveGlow.infer: groups=%r: the fp16 path runs one launch sequence (groups=1)" % (groups,))
-        dev = spect.device
-        h = self._checked_handle(dev)
-        spect = spect.contiguous()
-        B, _, T = spect.shape
-        hop = self.upsample.stride[0]
-        n = B * self.n_group * (T * hop // self.n_group)
-        host_lengths = lengths is not None and not torch.is_tensor(lengths)
-        if host_lengths and (len(lengths) != B or max(int(v) for v in lengths) > T or min(int(v) for v in lengths) < 1):
-            raise _lib.FacppgError("lengths must be B values in [1, T]")
-        zt = None
-        if utterance_seeds is not None:
-            if z is not None or len(utterance_seeds) != B:
-                raise _lib.FacppgError("utterance_seeds: B integers, and not together with z")
-        elif z is not None:
-            if isinstance(z, (list, tuple)):
-                z = torch.cat([t.to(dev).reshape(-1) for t in z])
-            zt = z.to(device=dev, dtype=torch.float16).contiguous()   # injected z is rounded to half, as the reference's draw is
-            if zt.numel() != n:
-                raise _lib.FacppgError("z has %d values, expected B*n_group*L = %d" % (zt.numel(), n))
-        if seed is None:
-            seed = int(torch.empty((), dtype=torch.int64).random_().item())
-        if utterance_seeds is None and zt is None and host_lengths and B >= 2:
-            # the fp32 path's per-utterance streams for `seed` on a ragged batch, so both precisions draw the same noise
-            utterance_seeds = [(int(seed) * 0x9E3779B97F4A7C15 + (b + 1) * 0xBF58476D1CE4E5B9) & 0x7FFFFFFFFFFFFFFF for b in range(B)]
-        if utterance_seeds is not None:
-            zt = self.draw_noise(utterance_seeds, T, dev).half()
-        lt = None
-        if lengths is not None:
-            if host_lengths:
-                lt = _lib.upload([int(v) for v in lengths], torch.int32, dev)
-            else:
-                lt = lengths.to(device=dev, dtype=torch.int32).contiguous()
-                if lt.numel() != B or int(lt.max()) > T or int(lt.min()) < 1:
-                    raise _lib.FacppgError("lengths must be B values in [1, T]")
-        audio = torch.zeros(B, T * hop, dtype=torch.float16, device=dev) if lt is not None else \
-            torch.empty(B, T * hop, dtype=torch.float16, device=dev)
-        ws = self._infer_workspace(B, T, dev, 0, h)
-        with torch.cuda.device(dev):
-            _lib.check(_lib.load().facppg_wg_infer_f16_order(h, _lib.ptr(spect), _lib.ptr(lt), _lib.ptr(zt), seed & 0xFFFFFFFFFFFFFFFF,
-                                                             float(sigma), B, T, 1 if cond_first else 0, _lib.ptr(audio), _lib.ptr(ws),
-                                                             ws.numel(), _lib.current_stream(dev)))
+            zt = self.draw_noise(utterance_seeds, T, dev).to(spect.dtype)
+        lt = _lib.upload(lengths, torch.int32, dev) if host_lengths else lengths
+        audio = (torch.empty if lt is None else torch.zeros)(B, T * hop, dtype=spect.dtype, device=dev)
+        self._infer_launch(spect, lt, zt, seed, sigma, audio, self._infer_workspace(B, T, dev, 0, h), h, cond_first)
         return audio
 
     @staticmethod

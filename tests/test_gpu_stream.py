@@ -4,62 +4,21 @@ the same utterance with FACPPG_STREAM=0 -- bit for bit, at lengths that end on a
 running to its step limit and stopping early on its gate (blocks that never become final are void)."""
 import contextlib
 import io
-import os
 
 import numpy as np
 import pytest
 import torch
 
-from helpers import masks_from_seed
 from facppg import synth
+from helpers import masks_from_seed
+from stream_helpers import HOP, acoustic, late_encode, make_vocoder, run, utterance
 
 pytestmark = pytest.mark.gpu
-
-HOP = 256
 
 
 @pytest.fixture(scope="module")
 def vocoder():
-    from waveglow.denoiser import Denoiser
-    from waveglow.glow import WaveGlow
-    cfg = dict(synth.WAVEGLOW_CONFIG, hop_length=HOP)
-    wg = WaveGlow.remove_weightnorm(WaveGlow(**cfg))
-    wg.load_state_dict(synth.waveglow_state_dict(cfg))
-    wg = wg.cuda().eval()
-    return cfg, wg, Denoiser(wg, hop_length=HOP, mode="zeros")
-
-
-def acoustic(steps, gate_bias):
-    from common.hparams import create_hparams_stage
-    from script.train_ppg2mel import load_model
-    hp = create_hparams_stage(max_decoder_steps=steps)
-    with contextlib.redirect_stdout(io.StringIO()):
-        taco = load_model(hp)
-    taco.load_state_dict(synth.tacotron_state_dict(hp, gate_bias=gate_bias))
-    taco.eval()
-    return hp, taco
-
-
-def run(taco, wg, den, ppg, em, dm, zs, stream, monkeypatch):
-    from facppg import pipeline
-    monkeypatch.setenv("FACPPG_STREAM", "1" if stream else "0")
-    monkeypatch.setenv("FACPPG_STREAM_MIN_FRAMES", "64")     # (short utterances are not streamed by default: they do not gain)
-    seen = {}
-    inference = taco.inference
-
-    def spy(*a, **kw):
-        out = inference(*a, **kw)
-        seen["mel_post"] = out[1].detach().clone()
-        seen["streamed"] = kw.get("frame_consumer") is not None and kw["frame_consumer"].active
-        seen["published"] = out.launch.streamed
-        return out
-    taco.inference = spy
-    try:
-        with contextlib.redirect_stdout(io.StringIO()):
-            wavs, tout = pipeline.synthesize([ppg], taco, wg, den, sigma=0.6, strength=0.005, dropout_masks=(em, dm), z=zs)
-    finally:
-        del taco.inference
-    return wavs[0], tout[0], seen
+    return make_vocoder()
 
 
 @pytest.mark.parametrize("Tin,steps,gate_bias", [(200, 200, -10.0), (170, 170, -10.0), (96, 96, -10.0), (75, 75, -10.0),
@@ -70,9 +29,7 @@ def test_streamed_utterance_equals_the_unstreamed_path_bit_for_bit(vocoder, Tin,
     if Tin == 96:                  # (the optional mode of the stream: unbounded seed passes)
         monkeypatch.setenv("FACPPG_STREAM_SPARE_CUS", "-1")
     hp, taco = acoustic(steps, gate_bias)
-    ppg = synth.synthetic_ppg(Tin, 5816, seed=Tin, alpha=0.002)
-    em = masks_from_seed(21, (2, 1, Tin, hp.symbols_embedding_dim))
-    dm = masks_from_seed(22, (steps, 2, 1, hp.prenet_dim))
+    ppg, em, dm = utterance(hp, Tin, steps, Tin)
     ref, t_ref, seen_ref = run(taco, wg, den, ppg, em, dm, None, False, monkeypatch)
     zs = synth.synthetic_z(1, t_ref * HOP // 8, cfg, seed=23)
     ref, t_ref, seen_ref = run(taco, wg, den, ppg, em, dm, zs, False, monkeypatch)
@@ -91,6 +48,59 @@ def test_streamed_utterance_equals_the_unstreamed_path_bit_for_bit(vocoder, Tin,
     assert out.shape == ref.shape == (t_ref * HOP,) and np.array_equal(out, ref)    # ... and so the samples
 
 
+def test_fp32_tail_by_one_more_pass_or_inside_the_layer_launches_same_bits(vocoder, monkeypatch):
+    """75 frames: 64 seeded under the decoder and an 11-frame, half-filled tail tile -- the shortest utterance with both a
+    seeded part and a ragged tail.  The tail gets its seeds from one more pass in front of the vocoder (FACPPG_STREAM_TAIL=seed:
+    frames [64, 96), every layer launch all-seeded 32-frame tiles) or runs unseeded inside the layer launches (the default at
+    this length: k_wn_layer_mixed, two seeded 32-frame tiles and one 16-frame tile per phase); both equal the unstreamed path bit
+    for bit.  (At 75 frames both launches have 3 tiles per phase, so last_launch_shape() reads the same for either; which side
+    ran is read off the calls the stream made on the vocoder.)"""
+    cfg, wg, den = vocoder
+    Tin = steps = 75
+    P = HOP // 8
+    hp, taco = acoustic(steps, -10.0)
+    ppg, em, dm = utterance(hp, Tin, steps, Tin)
+    zs = synth.synthetic_z(1, steps * HOP // 8, cfg, seed=23)
+    ref, t_ref, seen_ref = run(taco, wg, den, ppg, em, dm, zs, False, monkeypatch)
+    assert not seen_ref["streamed"] and t_ref == steps
+    calls = []
+    cond_seed, infer_seeded = wg.cond_seed, wg.infer_seeded
+
+    def spy_seed(melp, T, frame0, nframes, seeds, block_tiles=1, layers_per_workgroup=4, max_workgroups=0, **kw):
+        calls.append(("seed", frame0, nframes, block_tiles, layers_per_workgroup, max_workgroups > 0))
+        return cond_seed(melp, T, frame0, nframes, seeds, block_tiles=block_tiles, layers_per_workgroup=layers_per_workgroup,
+                         max_workgroups=max_workgroups, **kw)
+
+    def spy_infer(melp, T, seeds, seeded_frames, **kw):
+        calls.append(("infer", T, seeded_frames))
+        return infer_seeded(melp, T, seeds, seeded_frames, **kw)
+    wg.cond_seed, wg.infer_seeded = spy_seed, spy_infer
+    outs = {}
+    try:
+        for tail in ("seed", None):
+            if tail is None:
+                monkeypatch.delenv("FACPPG_STREAM_TAIL", raising=False)
+            else:
+                monkeypatch.setenv("FACPPG_STREAM_TAIL", tail)
+            del calls[:]
+            out, t_out, seen = run(taco, wg, den, ppg, em, dm, zs, True, monkeypatch)
+            cs = wg.__dict__["_facppg_cond_stream"]
+            print("tail %s: seeded %d, blocks %s, calls %s, launch shape %s" % (tail, cs.seeded, cs.cuts, calls, wg.last_launch_shape()))
+            assert seen["streamed"] and t_out == t_ref and not cs.half and cs.void_blocks == 0
+            assert cs.seeded == 64                               # frames seeded under the decoder, before any tail pass
+            outs[tail] = (out, list(calls), wg.last_launch_shape())
+    finally:
+        del wg.cond_seed, wg.infer_seeded
+    under_decoder = [("seed", 0, 32, 1, 1, True), ("seed", 32, 32, 1, 1, True)]      # two bounded passes, one per planned block
+    # the default: nothing more in front of the vocoder, whose launches carry the tail as a 16-frame tile behind two seeded ones
+    assert outs[None][1] == under_decoder + [("infer", 75, 64)]
+    assert outs[None][2] == (32, 8, P * (64 // 32 + -(-(75 - 64) // 16)))
+    # seed: one more, unbounded pass over the tail tile, then all 32-frame tiles
+    assert outs["seed"][1] == under_decoder + [("seed", 64, 32, 1, 2, False), ("infer", 75, 96)]
+    assert outs["seed"][2] == (32, 8, 3 * 32)
+    assert np.array_equal(outs["seed"][0], ref) and np.array_equal(outs[None][0], ref) and np.array_equal(outs["seed"][0], outs[None][0])
+
+
 def test_blocks_that_time_out_are_redone_behind_the_decoder(vocoder, monkeypatch):
     """k_collect_frames gives a block up when its frames do not arrive within FACPPG_STREAM_WAIT_MS (a profiler that serialises
     kernels, a cooperative launch queued behind another process): the block and every block behind it is void -- no postnet
@@ -99,27 +109,14 @@ def test_blocks_that_time_out_are_redone_behind_the_decoder(vocoder, monkeypatch
     cfg, wg, den = vocoder
     Tin = steps = 200
     hp, taco = acoustic(steps, -10.0)
-    ppg = synth.synthetic_ppg(Tin, 5816, seed=5, alpha=0.002)
-    em = masks_from_seed(61, (2, 1, Tin, hp.symbols_embedding_dim))
-    dm = masks_from_seed(62, (steps, 2, 1, hp.prenet_dim))
+    ppg, em, dm = utterance(hp, Tin, steps, 5, mask_seeds=(61, 62))
     zs = synth.synthetic_z(1, steps * HOP // 8, cfg, seed=63)
     ref, t_ref, _ = run(taco, wg, den, ppg, em, dm, zs, False, monkeypatch)
     out, t_out, seen = run(taco, wg, den, ppg, em, dm, zs, True, monkeypatch)
     cs = wg.__dict__["_facppg_cond_stream"]
     assert seen["streamed"] and cs.void_blocks == 0 and np.array_equal(out, ref)
     monkeypatch.setenv("FACPPG_STREAM_WAIT_MS", "0.001")
-    # The frames must really be late.  The collectors start with the encoder and test the limit only every few hundred polls,
-    # and the first frame follows about a millisecond later: a fast encoder wins that race and no block times out.  A spin
-    # kernel behind the encoder, on the stream the decoder is launched on, holds the frames back for milliseconds.
-    from facppg import lib as flib
-    L = flib.load()
-    encode = L.facppg_taco_encode
-
-    def late_encode(*a):
-        rc = encode(*a)
-        torch.cuda._sleep(20_000_000)
-        return rc
-    monkeypatch.setattr(L, "facppg_taco_encode", late_encode)
+    late_encode(monkeypatch)     # (the frames must really be late)
     out, t_out, seen = run(taco, wg, den, ppg, em, dm, zs, True, monkeypatch)
     print("blocks", cs.cuts, "void", cs.void_blocks, "seeded frames", cs.seeded)
     assert seen["streamed"] and cs.void_blocks > 0 and cs.seeded < 160
@@ -134,9 +131,7 @@ def test_a_decode_inside_a_streamed_call_publishes_nothing_into_it(vocoder, monk
     cfg, wg, den = vocoder
     Tin = steps = 200
     hp, taco = acoustic(steps, -10.0)
-    ppg = synth.synthetic_ppg(Tin, 5816, seed=8, alpha=0.002)
-    em = masks_from_seed(81, (2, 1, Tin, hp.symbols_embedding_dim))
-    dm = masks_from_seed(82, (steps, 2, 1, hp.prenet_dim))
+    ppg, em, dm = utterance(hp, Tin, steps, 8, mask_seeds=(81, 82))
     zs = synth.synthetic_z(1, steps * HOP // 8, cfg, seed=83)
     x2 = torch.from_numpy(synth.synthetic_ppg(Tin, 5816, seed=9, alpha=0.002).T.copy()).unsqueeze(0).cuda()
     em2 = masks_from_seed(84, (2, 1, Tin, hp.symbols_embedding_dim))
@@ -179,9 +174,7 @@ def test_stream_footprint_follows_the_utterance_not_the_step_limit(vocoder, monk
     wg.__dict__.pop("_facppg_cond_stream", None)
     held = []
     for Tin in (136, 200, 150):
-        ppg = synth.synthetic_ppg(Tin, 5816, seed=Tin, alpha=0.002)
-        em = masks_from_seed(71, (2, 1, Tin, hp.symbols_embedding_dim))
-        dm = masks_from_seed(72, (Tin, 2, 1, hp.prenet_dim))
+        ppg, em, dm = utterance(hp, Tin, Tin, Tin, mask_seeds=(71, 72))
         from facppg import pipeline
         monkeypatch.setenv("FACPPG_STREAM", "1")
         with contextlib.redirect_stdout(io.StringIO()):
@@ -202,9 +195,7 @@ def test_stream_buffers_are_reused_across_utterances(vocoder, monkeypatch):
     hp, taco = acoustic(steps, -10.0)
     cases = []
     for i, Tin in enumerate((136, 90, 120)):
-        ppg = synth.synthetic_ppg(Tin, 5816, seed=70 + i, alpha=0.002)
-        em = masks_from_seed(31 + i, (2, 1, Tin, hp.symbols_embedding_dim))
-        dm = masks_from_seed(41 + i, (steps, 2, 1, hp.prenet_dim))
+        ppg, em, dm = utterance(hp, Tin, steps, 70 + i, mask_seeds=(31 + i, 41 + i))
         zs = synth.synthetic_z(1, steps * HOP // 8, cfg, seed=51 + i)
         cases.append((ppg, em, dm, zs))
     refs = [run(taco, wg, den, *c, False, monkeypatch)[0] for c in cases]

@@ -2,86 +2,24 @@
 seed passes and the fp32 -> fp16 mel conversion under the decoder, seeded 32-frame tiles of k16_wn_layer behind it) against the
 same utterance unstreamed -- bit for bit --, the seed kernel and the seeded tiles directly on WaveGlow, the accuracy of the
 conditioning-first K order, and the refusals.  Hop 256, the synthetic 12-flow vocoder halved by the reference's recipe
-(inference.py:40-43: convinv kept in float), injected dropout masks and z; the harness of tests/test_gpu_stream.py."""
-import contextlib
+(inference.py:40-43: convinv kept in float), injected dropout masks and z; the harness of tests/stream_helpers.py."""
 import ctypes
-import io
 
 import numpy as np
 import pytest
 import torch
 
-from helpers import golden, masks_from_seed, rms
+from helpers import golden, rms
 from facppg import lib as flib
 from facppg import synth
+from stream_helpers import HOP, acoustic, halve, late_encode, make_vocoder, run, utterance
 
 pytestmark = pytest.mark.gpu
-
-HOP = 256
-
-
-def _halve(m):
-    m.half()
-    for k in m.convinv:
-        k.float()
-    return m
-
-
-def _vocoder(half):
-    from waveglow.denoiser import Denoiser
-    from waveglow.glow import WaveGlow
-    cfg = dict(synth.WAVEGLOW_CONFIG, hop_length=HOP)
-    wg = WaveGlow.remove_weightnorm(WaveGlow(**cfg))
-    wg.load_state_dict(synth.waveglow_state_dict(cfg))
-    wg = wg.cuda().eval()
-    if half:
-        _halve(wg)
-    return cfg, wg, Denoiser(wg, hop_length=HOP, mode="zeros")
 
 
 @pytest.fixture(scope="module")
 def vocoder():
-    return _vocoder(True)
-
-
-def acoustic(steps, gate_bias):
-    from common.hparams import create_hparams_stage
-    from script.train_ppg2mel import load_model
-    hp = create_hparams_stage(max_decoder_steps=steps)
-    with contextlib.redirect_stdout(io.StringIO()):
-        taco = load_model(hp)
-    taco.load_state_dict(synth.tacotron_state_dict(hp, gate_bias=gate_bias))
-    taco.eval()
-    return hp, taco
-
-
-def run(taco, wg, den, ppg, em, dm, zs, stream, monkeypatch):
-    from facppg import pipeline
-    monkeypatch.setenv("FACPPG_STREAM", "1" if stream else "0")
-    monkeypatch.setenv("FACPPG_STREAM_MIN_FRAMES", "64")
-    seen = {}
-    inference = taco.inference
-
-    def spy(*a, **kw):
-        out = inference(*a, **kw)
-        seen["mel_post"] = out[1].detach().clone()
-        seen["streamed"] = kw.get("frame_consumer") is not None and kw["frame_consumer"].active
-        seen["published"] = out.launch.streamed
-        return out
-    taco.inference = spy
-    try:
-        with contextlib.redirect_stdout(io.StringIO()):
-            wavs, tout = pipeline.synthesize([ppg], taco, wg, den, sigma=0.6, strength=0.005, dropout_masks=(em, dm), z=zs)
-    finally:
-        del taco.inference
-    return wavs[0], tout[0], seen
-
-
-def utterance(hp, Tin, steps, seed):
-    ppg = synth.synthetic_ppg(Tin, 5816, seed=seed, alpha=0.002)
-    em = masks_from_seed(21, (2, 1, Tin, hp.symbols_embedding_dim))
-    dm = masks_from_seed(22, (steps, 2, 1, hp.prenet_dim))
-    return ppg, em, dm
+    return make_vocoder(half=True)
 
 
 @pytest.mark.parametrize("Tin,steps,gate_bias", [(64, 64, -10.0), (75, 75, -10.0), (96, 96, -10.0), (150, 1000, -0.02), (130, 400, -10.0)])
@@ -133,14 +71,7 @@ def test_void_blocks_change_no_bit(vocoder, monkeypatch):
     seeded_all = cs.seeded
     assert seen["streamed"] and cs.void_blocks == 0 and seeded_all == 64 and np.array_equal(out, ref)
     monkeypatch.setenv("FACPPG_STREAM_WAIT_MS", "0.001")
-    L = flib.load()
-    encode = L.facppg_taco_encode
-
-    def late_encode(*a):
-        rc = encode(*a)
-        torch.cuda._sleep(20_000_000)
-        return rc
-    monkeypatch.setattr(L, "facppg_taco_encode", late_encode)
+    late_encode(monkeypatch)
     out, t_out, seen = run(taco, wg, den, ppg, em, dm, zs, True, monkeypatch)
     print("blocks", cs.cuts, "void", cs.void_blocks, "seeded frames", cs.seeded)
     assert seen["streamed"] and cs.void_blocks > 0 and cs.seeded < seeded_all
@@ -235,7 +166,7 @@ def test_conditioning_first_order_at_least_as_accurate_as_reference_half_branch(
 
 def test_streamed_half_against_the_fp32_pipeline(vocoder, monkeypatch):
     cfg, wg, den = vocoder
-    _, wg32, den32 = _vocoder(False)
+    _, wg32, den32 = make_vocoder()
     Tin = steps = 96
     hp, taco = acoustic(steps, -10.0)
     ppg, em, dm = utterance(hp, Tin, steps, Tin)
@@ -304,7 +235,7 @@ def test_refusals(vocoder):
 def test_precision_switch_between_streamed_utterances(monkeypatch):
     """.float() + reload, then .half() again, between streamed utterances on the same model pair: the handle, the stream and its
     layouts are rebuilt for the precision at hand, and every utterance still equals its unstreamed run."""
-    cfg, wg, den = _vocoder(True)
+    cfg, wg, den = make_vocoder(half=True)
     sd = synth.waveglow_state_dict(cfg)
     Tin = steps = 96
     hp, taco = acoustic(steps, -10.0)
@@ -315,7 +246,7 @@ def test_precision_switch_between_streamed_utterances(monkeypatch):
             wg.float()
             wg.load_state_dict(sd)
         elif i == 2:
-            _halve(wg)
+            halve(wg)
         ppg, em, dm = utterance(hp, Tin, steps, 300 + i)
         ref, _, seen_ref = run(taco, wg, den, ppg, em, dm, zs, False, monkeypatch)
         out, _, seen = run(taco, wg, den, ppg, em, dm, zs, True, monkeypatch)

@@ -7,9 +7,10 @@ import pytest
 from facppg.pipeline import ConditioningStream
 
 
-def planner(lag=10):
+def planner(lag=10, cap=None):
+    """A stream with the two fields plan() reads: the postnet's lag and the frames begin() lays the vocoder-side buffers out for."""
     cs = ConditioningStream.__new__(ConditioningStream)
-    cs.lag = lag
+    cs.lag, cs.cap = lag, cap
     return cs
 
 
@@ -37,7 +38,7 @@ def test_block_plan_invariants(steps, Tin, monkeypatch):
 
 
 def test_plan_env_overrides(monkeypatch):
-    cs = planner()
+    cs = planner(cap=200)
     monkeypatch.setenv("FACPPG_STREAM_PLAN", "64,32")
     assert [c[1:] for c in cs.plan(200, 200)][:3] == [(0, 64), (64, 96), (96, 128)]
     monkeypatch.delenv("FACPPG_STREAM_PLAN")
@@ -60,3 +61,40 @@ def test_usable_switches(monkeypatch):
     monkeypatch.delenv("FACPPG_WG_EDGE_FOLD")
     taco.decoder_workgroups = 32                             # a caller that bounds the decoder runs it under something else
     assert not ConditioningStream.usable(taco, wg)
+
+
+# hop 256 (P = 32 phases), 256 CUs: the cases of the comments in ConditioningStream.tail_pass, worked out by hand from its rules
+IN_KERNEL = None
+
+
+@pytest.mark.parametrize("T,seeded,expected", [
+    (200, 160, IN_KERNEL),                  # 32 * (5 + 3) = 256 workgroups against 32 * 7 = 224: one round each
+    (230, 192, (192, 64, 1, 2, False)),     # 32 * (6 + 3) = 288 against 256: two rounds against one
+    (300, 288, IN_KERNEL),                  # 320 against 320: two rounds either way
+    (75, 64, IN_KERNEL),                    # 96 against 96
+    (200, 0, (0, 224, 1, 2, False)),        # every block void: nothing seeded in front of the tail
+])
+def test_tail_decision_fp32(T, seeded, expected):
+    import torch
+    assert ConditioningStream.tail_pass(torch.float32, T, seeded, 32, 256) == expected
+    assert ConditioningStream.tail_pass(torch.float32, T, seeded, 32, 256, "auto") == expected
+
+
+def test_tail_decision_forced_and_fp16():
+    import torch
+    f32, f16 = torch.float32, torch.float16
+    tail = ConditioningStream.tail_pass
+    # FACPPG_STREAM_TAIL forces either side of the fp32 decision
+    assert tail(f32, 200, 160, 32, 256, "seed") == (160, 64, 1, 2, False)
+    assert tail(f32, 75, 64, 32, 256, "seed") == (64, 32, 1, 2, False)
+    assert tail(f32, 230, 192, 32, 256, "mixed") is IN_KERNEL
+    assert tail(f32, 200, 0, 32, 256, "mixed") == (0, 224, 1, 2, False)       # (no seeded tile in front: nothing to mix with)
+    # fp16: one more bounded pass of up to 4 tiles per block, unless "mixed"
+    assert tail(f16, 200, 160, 32, 256) == tail(f16, 200, 160, 32, 256, "seed") == (160, 64, 2, 1, True)
+    assert tail(f16, 200, 0, 32, 256) == (0, 224, 4, 1, True)
+    assert tail(f16, 200, 160, 32, 256, "mixed") is IN_KERNEL
+    assert tail(f16, 200, 160, 32, 256, "auto") == (160, 64, 2, 1, True)     # (only "mixed" selects the in-kernel tail)
+    # nothing behind the last block: no pass whatever the knob says
+    for dt in (f32, f16):
+        for knob in (None, "seed", "mixed"):
+            assert tail(dt, 64, 64, 32, 256, knob) is None and tail(dt, 75, 96, 32, 256, knob) is None

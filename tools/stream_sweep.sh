@@ -6,4 +6,3 @@ run FACPPG_STREAM_SPARE_CUS=-1
 run FACPPG_STREAM_SPARE_CUS=4
 run FACPPG_STREAM_SPARE_CUS=16
 run FACPPG_STREAM_CHUNK=32
-run FACPPG_STREAM_GROUPS=1
