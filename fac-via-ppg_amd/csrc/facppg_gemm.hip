@@ -5,6 +5,9 @@
 // of chunk c); the weight operand streams straight from its packed image into registers.
 #include "facppg_gemm.h"
 
+#include <cstdlib>
+#include <cstring>
+
 namespace facppg {
 namespace {
 
@@ -137,6 +140,133 @@ __global__ __launch_bounds__(256) void k_gemm(KArgs ka) {
   }
 }
 
+// Latency shape of k_gemm for launches of at most LAT_MAX_N columns (one short utterance through the encoder, the postnet tail,
+// the denoiser): there the grid of 64-column tiles does not fill the chip and a workgroup's few chunks are a chain of waits --
+// operands of chunk c + 1 requested during chunk c, ~2 us of latency in front of 1.7 us of MFMAs.  Same MFMA sequence per output
+// element (same split, chunk range, k-group and s order: the results are the legacy kernel's bit for bit), different schedule:
+//  - 32-column tiles: twice the workgroups, half the MFMAs per chunk, two workgroups per CU (48 KiB of LDS each);
+//  - the activation chunks of a split are ALL requested before the K loop, LAT_D = 6 deep (a split has 4 - 6 chunks; a longer
+//    one refills the ring as it goes), so the loop's only vector-memory waits are the weight ring's;
+//  - the weight ring is 7 k-groups ahead (the groups are half as long), its index clamped to the split's last group so that it
+//    never leaves the packed image;
+//  - a thread stages 8 consecutive k of one column: tap / channel advance by increments (no division per element) and go to
+//    LDS as two float4 ([k / 4][column][k % 4]), which a lane reads back as ONE ds_read_b128 per k-group: its four s steps.
+constexpr int LAT_MAX_N = 256, LTN = 32, LAT_D = 6, LAT_RING = 8;
+
+__global__ __launch_bounds__(256) void k_gemm_lat(KArgs ka) {
+  const GemmArgs& p = ka.g;
+  __shared__ float4 smem[LAT_D][(KCH / 4) * LTN];
+  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, li = lane & 31, kh = lane >> 5;
+  const int b = blockIdx.z / ka.sk, ks = blockIdx.z % ka.sk, n0 = p.col0 + blockIdx.x * LTN;
+  const int Nb = p.n_valid ? min(p.N, p.n_valid[b] * p.n_valid_mul + p.n_valid_add) : p.N;
+  if (n0 >= Nb) return;
+  if (p.skip && *p.skip) return;
+  const int Ns = p.src_hi > 0 ? (p.n_valid ? min(p.src_hi, p.n_valid[b] * p.n_valid_mul + p.n_valid_add) : p.src_hi) : Nb;
+  const int mb = blockIdx.y * 4 + w;
+  const int MB = (p.M + 31) / 32;
+  const bool active = mb < MB;
+  const int K = p.Cin * p.taps;
+  const int nch_all = ka.KG / 8;
+  const int c_lo = ks * nch_all / ka.sk, c_hi = (ks + 1) * nch_all / ka.sk;   // this split's chunks
+
+  f32x16 acc;
+#pragma unroll
+  for (int r = 0; r < 16; ++r) acc[r] = 0.0f;
+
+  // staging: thread (r8, column li) carries the k rows 8 r8 .. 8 r8 + 7 of a chunk; (kk0, tap0, ch0) = its first row of the NEXT
+  // chunk to request (chunks are requested in ascending order)
+  const float* xb = p.X + (size_t)b * p.x_bs;
+  const int r8 = tid >> 5, col = n0 + li;
+  // (no division and no 64-bit address arithmetic per element: channel and tap shift advance by increments, the element's
+  // offset from X is an unsigned 32-bit number -- gemm_launch sends slabs beyond that to the legacy kernel -- and an element
+  // outside the source reads X[0] and is replaced by zero: no branch around the load)
+  const int q64 = KCH / p.Cin, r64 = KCH % p.Cin;
+  const unsigned ldx = (unsigned)p.ldx, Nsu = Ns > 0 ? (unsigned)Ns : 0u;
+  int kk0 = c_lo * KCH + r8 * 8, ch0 = kk0 % p.Cin, tsh0 = (kk0 / p.Cin - p.pad) * p.dil;
+  float st[LAT_D][8];
+  unsigned st_ok[LAT_D];   // bit j: element j is inside the source (applied when the chunk goes to LDS: a select here would wait for the load)
+  auto stage_load = [&](float (&v)[8], unsigned& okm, bool live) {
+    int ch = ch0, tsh = tsh0;
+    okm = 0u;
+    unsigned off = (unsigned)ch * ldx;
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+      const unsigned sc = (unsigned)(col + tsh);
+      const bool ok = live && kk0 + j < K && sc < Nsu;
+      v[j] = xb[ok ? off + sc : 0u];
+      okm |= (ok ? 1u : 0u) << j;
+      off += ldx;
+      if (++ch == p.Cin) { ch = 0; off = 0u; tsh += p.dil; }
+    }
+    kk0 += KCH; tsh0 += q64 * p.dil; ch0 += r64;
+    if (ch0 >= p.Cin) { ch0 -= p.Cin; tsh0 += p.dil; }
+  };
+  auto stage_write = [&](const float (&v)[8], unsigned okm, int slot) {
+    float z[8];
+#pragma unroll
+    for (int j = 0; j < 8; ++j) z[j] = (okm >> j) & 1u ? v[j] : 0.0f;
+    float4* dst = smem[slot] + (2 * r8) * LTN + li;
+    dst[0] = make_float4(z[0], z[1], z[2], z[3]);
+    dst[LTN] = make_float4(z[4], z[5], z[6], z[7]);
+  };
+
+  // Vector-memory loads retire in order: chunk 0 first, then the weight ring, then the other chunks -- every wait of the K loop
+  // is on a load with nothing but weight loads (and, in a split of more than LAT_D chunks, one refill) behind it.
+  const float4* ap = p.A + (size_t)(active ? mb : 0) * (ka.KG + 1) * 64 + lane;
+  const int g_last = c_hi * 8 - 1;
+  float4 ar[LAT_RING];
+  stage_load(st[0], st_ok[0], true);
+#pragma unroll
+  for (int i = 0; i < LAT_RING - 1; ++i) ar[i] = ap[(size_t)min(c_lo * 8 + i, g_last) * 64];
+#pragma unroll
+  for (int j = 1; j < LAT_D; ++j)
+    stage_load(st[j], st_ok[j], c_lo + j < c_hi);   // (unconditional: a branch's shorter path would set the waits of the K loop)
+  stage_write(st[0], st_ok[0], 0);
+  __syncthreads();
+  // one round = up to LAT_D chunks, slot j = chunk base + j.  The first round stands outside the loop over the rounds: with a
+  // loop's back edge in front of it the compiler has to size its waits for the refilled registers, i.e. it drains the weight ring
+  // at every chunk; a split of at most LAT_D chunks (every split of a product whose K loop is split) never enters the loop.
+  auto round = [&](int base) __attribute__((always_inline)) {
+#pragma unroll
+    for (int j = 0; j < LAT_D; ++j) {
+      const int c = base + j;
+      // (uniform over the workgroup, like every branch around a barrier here; leaving instead of skipping tells the compiler
+      // that chunk c ran only if every chunk before it did, which is what its vmcnt values for the staged registers rest on)
+      if (c >= c_hi) return;
+      if (c + 1 < c_hi) stage_write(st[(j + 1) % LAT_D], st_ok[(j + 1) % LAT_D], (j + 1) % LAT_D);   // slot last read in chunk c + 1 - LAT_D
+      const float4* lb = smem[j] + kh * LTN + li;
+      const int G = c * 8;
+      float4 bv[8];   // the chunk's B operands, all requested before the first MFMA
+#pragma unroll
+      for (int g = 0; g < 8; ++g) bv[g] = lb[2 * g * LTN];
+#pragma unroll
+      for (int g = 0; g < 8; ++g) {
+        ar[(g + LAT_RING - 1) % LAT_RING] = ap[(size_t)min(G + g + LAT_RING - 1, g_last) * 64];
+        __builtin_amdgcn_sched_barrier(0);
+        const float4 a0 = ar[g % LAT_RING], b0 = bv[g];
+        acc = mfma32x32x2(a0.x, b0.x, acc);
+        acc = mfma32x32x2(a0.y, b0.y, acc);
+        acc = mfma32x32x2(a0.z, b0.z, acc);
+        acc = mfma32x32x2(a0.w, b0.w, acc);
+      }
+      if (c + LAT_D < c_hi) stage_load(st[j], st_ok[j], true);   // (st[j] went to LDS during chunk c - 1)
+      __syncthreads();
+    }
+  };
+  round(c_lo);
+  for (int base = c_lo + LAT_D; base < c_hi; base += LAT_D) round(base);
+  if (!active) return;
+  const int n = n0 + li;
+  if (n >= Nb) return;
+#pragma unroll
+  for (int r = 0; r < 16; ++r) {
+    const int m = mb * 32 + 8 * (r >> 2) + (r & 3) + 4 * kh;
+    if (m >= p.M) continue;
+    if (ka.sk > 1) p.splitk_ws[(((size_t)ks * p.B + b) * p.M + m) * p.N + n] = acc[r];
+    else gemm_epilogue(p, b, m, n, acc[r]);
+  }
+}
+
 // second pass of a split-K product: fixed-order sum of the partials, then the epilogue
 __global__ void k_gemm_reduce(KArgs ka) {
   const GemmArgs& p = ka.g;
@@ -185,7 +315,14 @@ int gemm_launch(const GemmArgs& a, hipStream_t s) {
     ka.sk = sk;
   }
   grid.z = a.B * ka.sk;
-  k_gemm<<<grid, 256, 0, s>>>(ka);
+  // FACPPG_GEMM_SHAPE=legacy: the 64-column kernel for every launch (read per call: the tests flip it)
+  const char* shape = getenv("FACPPG_GEMM_SHAPE");
+  if (a.N - a.col0 <= LAT_MAX_N && (long)a.Cin * a.ldx + a.N < (1l << 31) && !(shape && !strcmp(shape, "legacy"))) {
+    grid.x = (a.N - a.col0 + LTN - 1) / LTN;
+    k_gemm_lat<<<grid, 256, 0, s>>>(ka);
+  } else {
+    k_gemm<<<grid, 256, 0, s>>>(ka);
+  }
   if (ka.sk > 1) k_gemm_reduce<<<dim3((a.N - a.col0 + 255) / 256, a.M, a.B), 256, 0, s>>>(ka);
   FACPPG_HIP_CHECK(hipGetLastError());
   return FACPPG_OK;

@@ -276,23 +276,35 @@ __device__ __forceinline__ unsigned long long poll_tag(const unsigned long long*
   return v;
 }
 
-// BU = hidden units per workgroup, BKR = max columns of a gate row held per thread (NTC / (4*BU) K parts):
-// <32, 96>: 10 workgroups per direction at H = 300 (H <= 384), B <= 12;  <64, 152>: 5 per direction (H <= 304), B <= 24.
+// One DPP move (no LDS, no wait): every lane receives v of the lane CTRL names -- quad_perm (0x00..0xFF: a lane of its own
+// group of 4) or row_shl:n (0x100 + n: lane + n of its own row of 16; 0 from beyond the row)
+template <int CTRL>
+__device__ __forceinline__ float lane_mov(float v) {
+  return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), CTRL, 0xF, 0xF, true));
+}
+
+struct BilstmCoopArgs {
+  const float *xproj, *whh_t0, *whh_t1;
+  const int* lengths;
+  int Tin, H;
+  unsigned long long* xchg;   // [B][2][2][H]
+  float *mem_tm, *mem_cm;
+};
+
+// The step of k_bilstm_coop up to round 12 (FACPPG_BILSTM_STEP=legacy): thread = (gate row r = tid % 4BU, K part tid / 4BU); the K
+// parts and the four gates of a unit meet through LDS (part, gates), three barriers per step.
 template <int BU, int BKR>
-__global__ __launch_bounds__(NTC) void k_bilstm_coop(const float* __restrict__ xproj, const float* __restrict__ whh_t0,
-                                                     const float* __restrict__ whh_t1, const int* __restrict__ lengths, int Tin,
-                                                     int H, unsigned long long* __restrict__ xchg /*[B][2][2][H]*/,
-                                                     float* __restrict__ mem_tm, float* __restrict__ mem_cm) {
+__device__ __forceinline__ void bilstm_coop_legacy(const BilstmCoopArgs& p) {
   constexpr int BKP = NTC / (4 * BU);    // K parts per gate row
   __shared__ float hv[BKP * BKR];        // gathered hidden vector [H]
   __shared__ float part[BKP][4 * BU];    // K-part partial sums per gate row
   __shared__ float gates[4 * BU];
   const int wg = blockIdx.x, dir = blockIdx.y, b = blockIdx.z, tid = threadIdx.x;
-  const int R = 4 * H, KR = (H + BKP - 1) / BKP;
+  const int Tin = p.Tin, H = p.H, R = 4 * H, KR = (H + BKP - 1) / BKP;
   const int r = tid % (4 * BU), kp = tid / (4 * BU);
   const int u = wg * BU + r % BU, row = (r / BU) * H + u;    // this thread's gate row of W_hh
-  const float* WT = dir ? whh_t1 : whh_t0;                   // [H][4H] k-major
-  const int len = lengths ? lengths[b] : Tin;
+  const float* WT = dir ? p.whh_t1 : p.whh_t0;               // [H][4H] k-major
+  const int len = p.lengths ? p.lengths[b] : Tin;
   float w[BKR];
 #pragma unroll
   for (int i = 0; i < BKR; ++i) {
@@ -301,12 +313,12 @@ __global__ __launch_bounds__(NTC) void k_bilstm_coop(const float* __restrict__ x
   }
   for (int i = tid; i < BKP * BKR; i += NTC) hv[i] = 0.0f;
   float c = 0.0f;
-  unsigned long long* xb = xchg + (size_t)(b * 2 + dir) * 2 * H;
+  unsigned long long* xb = p.xchg + (size_t)(b * 2 + dir) * 2 * H;
   __syncthreads();
   for (int s = 0; s < len; ++s) {
     const int t = dir ? len - 1 - s : s;
     // input projection of this row (independent of h): issued first, consumed after the matvec
-    const float xp = (kp == 0 && u < H) ? xproj[((size_t)b * Tin + t) * (2 * R) + dir * R + row] : 0.0f;
+    const float xp = (kp == 0 && u < H) ? p.xproj[((size_t)b * Tin + t) * (2 * R) + dir * R + row] : 0.0f;
     float acc = 0.0f;
     const float* hk = hv + kp * KR;
 #pragma unroll
@@ -327,8 +339,8 @@ __global__ __launch_bounds__(NTC) void k_bilstm_coop(const float* __restrict__ x
       const int uu = wg * BU + tid;
       __hip_atomic_store(xb + (size_t)((s + 1) & 1) * H + uu, ((unsigned long long)(unsigned)(s + 1) << 32) | __float_as_uint(h),
                          __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      mem_tm[((size_t)b * Tin + t) * (2 * H) + dir * H + uu] = h;
-      mem_cm[((size_t)b * 2 * H + dir * H + uu) * Tin + t] = h;
+      p.mem_tm[((size_t)b * Tin + t) * (2 * H) + dir * H + uu] = h;
+      p.mem_cm[((size_t)b * 2 * H + dir * H + uu) * Tin + t] = h;
     }
     if (s + 1 < len) {
       const unsigned long long* src = xb + (size_t)((s + 1) & 1) * H;
@@ -338,6 +350,112 @@ __global__ __launch_bounds__(NTC) void k_bilstm_coop(const float* __restrict__ x
     }
     __syncthreads();
   }
+}
+
+// The one-barrier step.  A wave holds whole units: lane = K part + BKP * (gate + 4 * unit of the wave), so the BKP partial sums of a
+// gate row sit in one group of BKP lanes and the four gate sums of a unit in one row of 16 lanes.  They meet by DPP moves, in the
+// legacy step's order ((((xp + p0) + p1) + p2) + p3); the unit's first lane runs the legacy pointwise expression, publishes the word
+// and stores.  No LDS array but hv, which is double buffered by step parity like the exchange words (a fast wave gathers step s + 1
+// while a slow one still reads step s), so the barrier behind the gather is the only one: it keeps a wave from gathering step s + 2
+// into the buffer that step s is read from, and it is what the exchange words' overwrite argument above rests on.
+// The dot product keeps the legacy order (one accumulator, ascending k) but reads hv as float4 and runs over NB groups of 4 = the
+// live KR columns rounded up to 4, not BKR (the padding is zero in hv and in w).  NB is a template parameter so that the loop is
+// straight-line code with all its LDS reads in flight; the K parts sit HVS = BKR + 4 floats apart, which puts the (up to) four
+// distinct 16-byte reads of a ds_read_b128 lane group on distinct banks.
+template <int BU, int BKR, int NB>
+__device__ __forceinline__ void bilstm_coop_steps(const BilstmCoopArgs& p, const float (&w)[BKR], float (*hv)[(NTC / (4 * BU)) * (BKR + 4)],
+                                                  int u, int row, int kp, bool head, int hslot, int len) {
+  constexpr int BKP = NTC / (4 * BU), HVS = BKR + 4;
+  const int dir = blockIdx.y, b = blockIdx.z, tid = threadIdx.x;
+  const int Tin = p.Tin, H = p.H, R = 4 * H;
+  unsigned long long* xb = p.xchg + (size_t)(b * 2 + dir) * 2 * H;
+  float c = 0.0f;
+  for (int s = 0; s < len; ++s) {
+    const int t = dir ? len - 1 - s : s;
+    // input projection of this row (independent of h): issued first, consumed after the matvec
+    const float xp = (kp == 0 && u < H) ? p.xproj[((size_t)b * Tin + t) * (2 * R) + dir * R + row] : 0.0f;
+    const float4* hk = reinterpret_cast<const float4*>(hv[s & 1] + kp * HVS);
+    // chunks of CH reads, the next chunk requested before the FMAs of this one (left alone, the compiler keeps one read in flight)
+    constexpr int CH = 8, NC = (NB + CH - 1) / CH;
+    float4 hb[2][CH];
+#pragma unroll
+    for (int i = 0; i < CH; ++i)
+      if (i < NB) hb[0][i] = hk[i];
+    float acc = 0.0f;
+#pragma unroll
+    for (int ch = 0; ch < NC; ++ch) {
+#pragma unroll
+      for (int i = 0; i < CH; ++i)
+        if ((ch + 1) * CH + i < NB) hb[(ch + 1) & 1][i] = hk[(ch + 1) * CH + i];
+      __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+      for (int i = 0; i < CH; ++i) {
+        const int j = ch * CH + i;
+        if (j < NB) {
+          const float4 h4 = hb[ch & 1][i];
+          acc = fmaf(w[4 * j], h4.x, acc); acc = fmaf(w[4 * j + 1], h4.y, acc);
+          acc = fmaf(w[4 * j + 2], h4.z, acc); acc = fmaf(w[4 * j + 3], h4.w, acc);
+        }
+      }
+    }
+    float g = xp;   // (the sum is the gate's in the K part 0 lane, which alone loaded xp)
+    if constexpr (BKP == 4) {
+      g += lane_mov<0x00>(acc); g += lane_mov<0x55>(acc); g += lane_mov<0xAA>(acc); g += lane_mov<0xFF>(acc);
+    } else {
+      g += lane_mov<0xA0>(acc); g += lane_mov<0xF5>(acc);   // quad_perm [0,0,2,2], [1,1,3,3]
+    }
+    const float gf = lane_mov<0x100 + BKP>(g), gg = lane_mov<0x100 + 2 * BKP>(g), go = lane_mov<0x100 + 3 * BKP>(g);
+    if (head) {
+      const float cn = sigm(gf) * c + sigm(g) * tanhf(gg);
+      const float h = sigm(go) * tanhf(cn);
+      c = cn;
+      __hip_atomic_store(xb + (size_t)((s + 1) & 1) * H + u, ((unsigned long long)(unsigned)(s + 1) << 32) | __float_as_uint(h),
+                         __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      p.mem_tm[((size_t)b * Tin + t) * (2 * H) + dir * H + u] = h;
+      p.mem_cm[((size_t)b * 2 * H + dir * H + u) * Tin + t] = h;
+    }
+    if (s + 1 < len && tid < H)
+      hv[(s + 1) & 1][hslot] = __uint_as_float((unsigned)poll_tag(xb + (size_t)((s + 1) & 1) * H + tid, (unsigned)(s + 1)));
+    __syncthreads();
+  }
+}
+template <int BU, int BKR, int NB>
+__device__ __forceinline__ void bilstm_coop_dispatch(int nb, const BilstmCoopArgs& p, const float (&w)[BKR],
+                                                     float (*hv)[(NTC / (4 * BU)) * (BKR + 4)], int u, int row, int kp, bool head,
+                                                     int hslot, int len) {
+  if (nb == NB) bilstm_coop_steps<BU, BKR, NB>(p, w, hv, u, row, kp, head, hslot, len);
+  else if constexpr (NB > 1) bilstm_coop_dispatch<BU, BKR, NB - 1>(nb, p, w, hv, u, row, kp, head, hslot, len);
+}
+
+template <int BU, int BKR>
+__device__ __forceinline__ void bilstm_coop_fused(const BilstmCoopArgs& p) {
+  constexpr int BKP = NTC / (4 * BU), HVS = BKR + 4, UW = 16 / BKP;   // UW = units per wave
+  static_assert(BKP * 4 * BU == NTC && (BKP == 2 || BKP == 4) && BKR % 4 == 0 && BKP * BKR <= NTC, "bilstm_coop_fused: thread map");
+  __shared__ __attribute__((aligned(16))) float hv[2][BKP * HVS];   // gathered hidden vector by step parity, K part kp at kp * HVS
+  const int wg = blockIdx.x, dir = blockIdx.y, b = blockIdx.z, tid = threadIdx.x, lane = tid & 63;
+  const int H = p.H, R = 4 * H, KR = (H + BKP - 1) / BKP;
+  const int kp = lane % BKP, gate = (lane / BKP) & 3;
+  const int u = wg * BU + (tid >> 6) * UW + lane / (4 * BKP), row = gate * H + u;   // this thread's gate row of W_hh
+  const float* WT = dir ? p.whh_t1 : p.whh_t0;                                      // [H][4H] k-major
+  const int len = p.lengths ? p.lengths[b] : p.Tin;
+  float w[BKR];
+#pragma unroll
+  for (int i = 0; i < BKR; ++i) {
+    const int k = kp * KR + i;
+    w[i] = (i < KR && k < H && u < H) ? WT[(size_t)k * R + row] : 0.0f;
+  }
+  for (int i = tid; i < 2 * BKP * HVS; i += NTC) (&hv[0][0])[i] = 0.0f;
+  const int hslot = tid < H ? (tid / KR) * HVS + tid % KR : 0;   // where this thread puts the word it gathers (H <= BKP * BKR <= NTC)
+  __syncthreads();
+  bilstm_coop_dispatch<BU, BKR, BKR / 4>((KR + 3) / 4, p, w, hv, u, row, kp, lane % (4 * BKP) == 0 && u < H, hslot, len);
+}
+
+// BU = hidden units per workgroup, BKR = max columns of a gate row held per thread (NTC / (4*BU) K parts):
+// <32, 96>: 10 workgroups per direction at H = 300 (H <= 384), B <= 12;  <64, 152>: 5 per direction (H <= 304), B <= 24.
+template <int BU, int BKR, bool FUSED>
+__global__ __launch_bounds__(NTC) void k_bilstm_coop(BilstmCoopArgs p) {
+  if constexpr (FUSED) bilstm_coop_fused<BU, BKR>(p);
+  else bilstm_coop_legacy<BU, BKR>(p);
 }
 
 // ------------------------------------------------------------------------------------------
@@ -1744,7 +1862,8 @@ extern "C" int facppg_taco_create(const facppg_taco_config* cfg, const float* ws
     const struct { const void* fn; size_t lds; } coop_kernels[] = {
         {(const void*)k_decoder_coop, 150 * 1024}, {(const void*)k_decoder_forced<false>, 150 * 1024}, {(const void*)k_decoder_forced<true>, 150 * 1024}, {(const void*)k_decoder_split<1>, 150 * 1024},
         {(const void*)k_decoder_split<2>, 150 * 1024}, {(const void*)k_decoder_split<3>, 150 * 1024},
-        {(const void*)k_bilstm_coop<32, 96>, 0}, {(const void*)k_bilstm_coop<64, 152>, 0}};
+        {(const void*)k_bilstm_coop<32, 96, true>, 0}, {(const void*)k_bilstm_coop<64, 152, true>, 0},
+        {(const void*)k_bilstm_coop<32, 96, false>, 0}, {(const void*)k_bilstm_coop<64, 152, false>, 0}};
     for (const auto& k : coop_kernels) {
       int nb = 0;
       if (k.lds) FACPPG_HIP_CHECK(hipFuncSetAttribute(k.fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)k.lds));
@@ -2002,13 +2121,14 @@ static int taco_encode_impl(const facppg_taco* h, const float* ppg_dev, const in
   if (!no_coop && (fit32 || fit64)) {
     unsigned long long* xchg = (unsigned long long*)(ws + w.xchg);
     FACPPG_HIP_CHECK(hipMemsetAsync(xchg, 0, (size_t)B * 2 * 2 * H * 8, s));
-    const float *w0 = h->whh_t[0], *w1 = h->whh_t[1];
-    const float* xp = xproj;
-    int Tin_ = Tin, H_ = H;
-    void* args[] = {(void*)&xp, (void*)&w0, (void*)&w1, (void*)&lengths_dev, (void*)&Tin_, (void*)&H_, (void*)&xchg,
-                    (void*)&memory_dev, (void*)&mem_cm};
-    if (fit32) FACPPG_HIP_CHECK(launch_coop((const void*)k_bilstm_coop<32, 96>, dim3((H + 31) / 32, 2, B), dim3(NTC), args, 0, s));
-    else FACPPG_HIP_CHECK(launch_coop((const void*)k_bilstm_coop<64, 152>, dim3((H + 63) / 64, 2, B), dim3(NTC), args, 0, s));
+    // FACPPG_BILSTM_STEP=legacy: the three-barrier step (read per call: the tests flip it)
+    const char* step_env = getenv("FACPPG_BILSTM_STEP");
+    const bool legacy = step_env && !strcmp(step_env, "legacy");
+    BilstmCoopArgs ba{xproj, h->whh_t[0], h->whh_t[1], lengths_dev, Tin, H, xchg, memory_dev, mem_cm};
+    void* args[] = {(void*)&ba};
+    const void* fn = fit32 ? (legacy ? (const void*)k_bilstm_coop<32, 96, false> : (const void*)k_bilstm_coop<32, 96, true>)
+                           : (legacy ? (const void*)k_bilstm_coop<64, 152, false> : (const void*)k_bilstm_coop<64, 152, true>);
+    FACPPG_HIP_CHECK(launch_coop(fn, fit32 ? dim3((H + 31) / 32, 2, B) : dim3((H + 63) / 64, 2, B), dim3(NTC), args, 0, s));
   } else {
     const int KS = NT / H < H ? NT / H : H;
     const size_t smem = (size_t)(2 * H + (KS > 0 ? KS : 1) * 4 * H) * 4;
