@@ -155,6 +155,11 @@ def _declare(lib):
         "facppg_wg_mel_pad_f16": (c.c_int, [vp, vp, c.c_int, c.c_int, c.c_int, c.c_int, vp, vp, vp]),
         "facppg_wg_cond_seed_f16": (c.c_int, [vp, vp, c.c_int, c.c_int, c.c_int, c.c_int, c.c_int, c.c_int, c.c_int, vp, sz, vp, c.c_int, vp, vp]),
         "facppg_wg_infer_seeded_f16": (c.c_int, [vp, vp, c.c_int, c.c_int, vp, c.c_int, vp, c.c_uint64, f32, vp, vp, sz, vp, vp]),
+        "facppg_wg_split_create": (c.c_int, [c.POINTER(WgConfig), vp, sz, c.c_int, vp, c.POINTER(vp)]),
+        "facppg_wg_split_destroy": (None, [vp]),
+        "facppg_wg_split_workspace_bytes": (sz, [vp, c.c_int, c.c_int]),
+        "facppg_wg_split_infer": (c.c_int, [vp, vp, vp, vp, u64, f32, c.c_int, c.c_int, vp, vp, sz, vp]),
+        "facppg_wg_split_last_launch_shape": (c.c_int, [vp, c.POINTER(c.c_int), c.POINTER(c.c_int), c.POINTER(c.c_int)]),
         "facppg_stft_create": (c.c_int, [c.c_int, c.c_int, vp, vp, vp, vp, c.c_int, c.c_int, vp, c.POINTER(vp)]),
         "facppg_stft_destroy": (None, [vp]),
         "facppg_stft_workspace_bytes": (sz, [vp, c.c_int, c.c_int]),

@@ -18,7 +18,7 @@ class Synthesizer(object):
     (``{'model': ...}``, train_waveglow.py:56-64) once with weight norm removed for synthesis
     (utils.py:177-181) and once as pickled for the denoiser's bias estimate (generate_synthesis.py:58-61)."""
 
-    def __init__(self, ppg2mel_path, waveglow_path, hparams=None, denoiser_mode='zeros'):
+    def __init__(self, ppg2mel_path, waveglow_path, hparams=None, denoiser_mode='zeros', vocoder_arithmetic=None):
         from common.hparams import create_hparams_stage
         from common.utils import load_waveglow_model
         from script.train_ppg2mel import load_model
@@ -29,12 +29,17 @@ class Synthesizer(object):
         self.tacotron.eval()
         self.denoiser = Denoiser(torch.load(waveglow_path, weights_only=False)['model'].cuda(), mode=denoiser_mode)
         self.waveglow = load_waveglow_model(waveglow_path)
+        # the vocoder's arithmetic of every call (WaveGlow.infer's ``arithmetic``); the denoiser's bias spectrum above is formed on
+        # the fp32 path either way
+        self.vocoder_arithmetic = _checked_arithmetic(vocoder_arithmetic)
 
     def __call__(self, ppgs, sigma=0.6, strength=0.005, **kw):
+        kw.setdefault("vocoder_arithmetic", self.vocoder_arithmetic)
         return synthesize(ppgs, self.tacotron, self.waveglow, self.denoiser, sigma=sigma, strength=strength, **kw)
 
     def stream(self, jobs, sigma=0.6, strength=0.005, **kw):
         """synthesize_stream over this synthesizer's models: batch i+1's acoustic model under batch i's vocoder."""
+        kw.setdefault("vocoder_arithmetic", self.vocoder_arithmetic)
         return synthesize_stream(jobs, self.tacotron, self.waveglow, self.denoiser, sigma=sigma, strength=strength, **kw)
 
     @staticmethod
@@ -479,9 +484,18 @@ def _acoustic(ppgs, tacotron, seed, dropout_masks, utterance_seeds, step_limits,
     return mel_post.contiguous(), tout
 
 
-def _vocode(mel_post, tout, waveglow, denoiser, sigma, strength, seed, z, utterance_seeds, timer=None, consumer=None):
+def _checked_arithmetic(arithmetic):
+    """The ``vocoder_arithmetic`` of a call -> what WaveGlow.infer takes as ``arithmetic`` (None: the module's own path);
+    an unknown value is refused here, before any model runs."""
+    if arithmetic not in (None, "fp32", "bf16x3"):
+        from facppg.lib import FacppgError
+        raise FacppgError("vocoder_arithmetic=%r: expected None, 'fp32' or 'bf16x3'" % (arithmetic,))
+    return None if arithmetic == "fp32" else arithmetic
+
+
+def _vocode(mel_post, tout, waveglow, denoiser, sigma, strength, seed, z, utterance_seeds, timer=None, consumer=None, arithmetic=None):
     """WaveGlow.infer + Denoiser on the current stream -> audio [B, Tout_max * hop] on the device; no host waits beyond the
-    small uploads (lengths, seeds)."""
+    small uploads (lengths, seeds).  arithmetic: WaveGlow.infer's ("bf16x3": never streamed, ``consumer`` is None)."""
     hop = waveglow.upsample.stride[0]
     multi = len(tout) > 1
     wg_seeds = None if utterance_seeds is None else [int(v) + 1 for v in utterance_seeds]
@@ -498,6 +512,8 @@ def _vocode(mel_post, tout, waveglow, denoiser, sigma, strength, seed, z, uttera
         # one utterance through a half vocoder: the K order of the streamed path (conditioning first), so that the samples do not
         # depend on whether this utterance was streamed (too short, FACPPG_STREAM=0, outgrew the layout, stream busy)
         order = {"cond_first": True} if half and not multi else {}
+        if arithmetic is not None:
+            order["arithmetic"] = arithmetic
         audio = waveglow.infer(mel_post, sigma=sigma, z=z, lengths=tout if multi else None, seed=seed, utterance_seeds=wg_seeds, **order)
         if half:
             audio = audio.float()
@@ -511,21 +527,24 @@ def _vocode(mel_post, tout, waveglow, denoiser, sigma, strength, seed, z, uttera
 
 
 def synthesize(ppgs, tacotron, waveglow, denoiser=None, sigma=0.6, strength=0.005, seed=None, dropout_masks=None, z=None,
-               return_device=False, utterance_seeds=None, step_limits=None, timer=None):
+               return_device=False, utterance_seeds=None, step_limits=None, timer=None, vocoder_arithmetic=None):
     """Returns (list of float32 waveforms [N_i], list of mel lengths).  Models must be on the GPU.
 
     One utterance (the latency path, the metric's "batch = 1"): the postnet and the conditioning part of the vocoder's gate GEMMs
     run while the decoder is still producing frames (ConditioningStream; FACPPG_STREAM=0 switches it off) -- same samples.
     utterance_seeds: one integer per utterance -- its dropout and noise streams then depend on that seed alone,
     so the result for an utterance is the same whatever batch, batch size or GPU it is synthesised in.
-    step_limits: per-utterance max_decoder_steps (e.g. its PPG length)."""
+    step_limits: per-utterance max_decoder_steps (e.g. its PPG length).
+    vocoder_arithmetic: WaveGlow.infer's ``arithmetic`` (None / "fp32": the module's own path; "bf16x3": split-bf16 operands on the
+    bf16 MFMA, fp32 samples out).  A "bf16x3" call always takes the unstreamed path: ConditioningStream is not used."""
+    arithmetic = _checked_arithmetic(vocoder_arithmetic)
     if timer is not None:
         timer.__init__()
     hop = waveglow.upsample.stride[0]
     with torch.no_grad():
         dev = next(waveglow.parameters()).device
         consumer = None
-        if len(ppgs) == 1 and ConditioningStream.usable(tacotron, waveglow):
+        if len(ppgs) == 1 and arithmetic is None and ConditioningStream.usable(tacotron, waveglow):
             consumer = waveglow.__dict__.get("_facppg_cond_stream")
             if consumer is None or consumer.tacotron is not tacotron:
                 consumer = waveglow.__dict__["_facppg_cond_stream"] = ConditioningStream(tacotron, waveglow)
@@ -536,9 +555,10 @@ def synthesize(ppgs, tacotron, waveglow, denoiser=None, sigma=0.6, strength=0.00
         try:
             mel_post, tout = _acoustic(ppgs, tacotron, seed, dropout_masks, utterance_seeds, step_limits, timer,
                                        # host work under the decoder's milliseconds: the vocoder's weight check (the stream does its own)
-                                       while_decoding=lambda: None if (consumer is not None and consumer.active) else waveglow.prepare(dev),
+                                       while_decoding=lambda: None if (consumer is not None and consumer.active) else
+                                       (waveglow.prepare(dev, arithmetic) if arithmetic is not None else waveglow.prepare(dev)),
                                        consumer=consumer)
-            audio = _vocode(mel_post, tout, waveglow, denoiser, sigma, strength, seed, z, utterance_seeds, timer, consumer)
+            audio = _vocode(mel_post, tout, waveglow, denoiser, sigma, strength, seed, z, utterance_seeds, timer, consumer, arithmetic)
         finally:
             if consumer is not None:
                 consumer.lock.release()
@@ -559,7 +579,7 @@ def _acoustic_stream(device):
 
 
 def synthesize_stream(jobs, tacotron, waveglow, denoiser=None, sigma=0.6, strength=0.005, return_device=True, overlap=True,
-                      acoustic_workgroups=32):
+                      acoustic_workgroups=32, vocoder_arithmetic=None):
     """A sequence of batches, software-pipelined: generator of (waveforms, mel lengths), one per job, in order.
 
     jobs: iterable of dicts with ``ppgs`` and optionally ``seed``, ``utterance_seeds``, ``step_limits`` (as synthesize()).
@@ -576,7 +596,8 @@ def synthesize_stream(jobs, tacotron, waveglow, denoiser=None, sigma=0.6, streng
     batch), on 32 CUs the decoder takes 60 instead of 18 ms -- still hidden -- and the vocoder keeps 7/8 of the chip
     (128.3 ms; profiles/r03_experiments.txt).  The slice width that goes with the bound cuts the decoder's LSTM sums
     differently: samples then equal those of synthesize() with the same Tacotron2.decoder_workgroups bit for bit, and those
-    of the unbounded decoder to rounding."""
+    of the unbounded decoder to rounding.  vocoder_arithmetic: as synthesize()."""
+    arithmetic = _checked_arithmetic(vocoder_arithmetic)
     dev = next(tacotron.parameters()).device
     hop = waveglow.upsample.stride[0]
     main = torch.cuda.current_stream(dev)
@@ -609,7 +630,8 @@ def synthesize_stream(jobs, tacotron, waveglow, denoiser=None, sigma=0.6, streng
         job, mel_post, tout, done = ready
         main.wait_event(done)
         with torch.no_grad():
-            audio = _vocode(mel_post, tout, waveglow, denoiser, sigma, strength, job.get("seed"), None, job.get("utterance_seeds"))
+            audio = _vocode(mel_post, tout, waveglow, denoiser, sigma, strength, job.get("seed"), None, job.get("utterance_seeds"),
+                            arithmetic=arithmetic)
         vocoder_done = torch.cuda.Event()
         vocoder_done.record(main)
         nxt = next(it, None)

@@ -46,6 +46,9 @@ def parse(argv=None):
                     help='run the batches strictly one after the other instead of starting the acoustic model of the next batch '
                          'under the vocoder of the current one (same waveforms, slower)')
     ap.add_argument('--dist_backend', default='nccl', help='nccl = RCCL over xGMI (default); gloo for CPU tests')
+    ap.add_argument('--vocoder_arithmetic', choices=('fp32', 'bf16x3'), default=None,
+                    help="arithmetic of the vocoder's WaveGlow.infer: fp32 (exact, the default) or bf16x3 (fp32 operands split into two "
+                         "bf16 terms on the bf16 MFMA: fp32-class accuracy, fp32 samples out)")
     ap.add_argument('--hparams', default='',
                     help='comma separated "name=value" overrides of create_hparams_stage (train_ppg2mel.py:291-292), '
                          'e.g. n_symbols=40 for monophone PPGs (data_utils.py:253-258)')
@@ -124,7 +127,8 @@ def main(argv=None, synthesizer=None):
         lengths = [p.shape[0] for p in ppgs]
         if synthesizer is None:
             from facppg.pipeline import Synthesizer
-            synthesizer = Synthesizer(args.ppg2mel_model, args.waveglow_model, hparams=parse_hparams(args.hparams))
+            synthesizer = Synthesizer(args.ppg2mel_model, args.waveglow_model, hparams=parse_hparams(args.hparams),
+                                      vocoder_arithmetic=args.vocoder_arithmetic)
         wavs, ids = synthesize_shard(synthesizer, ppgs, lengths, rank, world, args)
         gathered = collect(wavs, ids, world)
         if rank == 0:

@@ -915,23 +915,31 @@ class WaveGlow(torch.nn.Module):
             parts += [wn.end.weight, wn.end.bias, self.convinv[k].inverse_matrix(), self.convinv[k].conv.weight.squeeze(-1)]
         return torch.cat([p.detach().float().reshape(-1) for p in parts])
 
-    def _release(self):
+    def _release(self, keep_split=False):
+        """Drop the packed-weight handles and what hangs on them.  keep_split: all but the split-bf16 handle (the fp32 handle is
+        being rebuilt -- first use, another device -- while the split one is still valid)."""
         self.__dict__.pop("_facppg_prepared", None)
         self.__dict__.pop("_facppg_cond_stream", None)    # its buffers belong to the handle's weights and device
         h = self.__dict__.pop("_facppg_handle", None)
         if h is not None:
             _lib.load().facppg_wg_destroy(h[0])
+        hs = None if keep_split else self.__dict__.pop("_facppg_split_handle", None)
+        if hs is not None:
+            _lib.load().facppg_wg_split_destroy(hs[0])
         self.__dict__.pop("_facppg_ws", None)
 
-    def last_launch_shape(self):
+    def last_launch_shape(self, arithmetic=None):
         """(frames per tile, waves per workgroup, workgroups per launch) of the WN-layer kernels of the most recent
-        infer() -- which instantiation of the fused layer kernel ran (facppg_wg_last_launch_shape)."""
-        h = self.__dict__.get("_facppg_handle")
+        infer() -- which instantiation of the fused layer kernel ran (facppg_wg_last_launch_shape); arithmetic="bf16x3": of the
+        most recent infer(arithmetic="bf16x3") (facppg_wg_split_last_launch_shape)."""
+        split = self._check_arithmetic(arithmetic)
+        h = self.__dict__.get("_facppg_split_handle" if split else "_facppg_handle")
         if h is None:
             raise _lib.FacppgError("last_launch_shape: no inference has run on this model yet")
         c = _lib.ctypes
         tile, waves, tiles = c.c_int(0), c.c_int(0), c.c_int(0)
-        _lib.check(_lib.load().facppg_wg_last_launch_shape(h[0], c.byref(tile), c.byref(waves), c.byref(tiles)))
+        query = _lib.load().facppg_wg_split_last_launch_shape if split else _lib.load().facppg_wg_last_launch_shape
+        _lib.check(query(h[0], c.byref(tile), c.byref(waves), c.byref(tiles)))
         return tile.value, waves.value, tiles.value
 
     def invalidate_packed_weights(self):
@@ -946,7 +954,8 @@ class WaveGlow(torch.nn.Module):
         h = self.__dict__.get("_facppg_handle")
         if h is not None and h[1] == device and h[2].unchanged():
             return h[0]
-        self._release()
+        hs = self.__dict__.get("_facppg_split_handle")
+        self._release(keep_split=hs is not None and hs[2].unchanged())
         L = _lib.load()
         cfg = self._config()
         prec = self._precision()
@@ -961,6 +970,61 @@ class WaveGlow(torch.nn.Module):
                               _lib.current_stream(device), _lib.ctypes.byref(out)))
         self.__dict__["_facppg_handle"] = (out, device, _lib.WeightIdentity(self), prec)
         return out
+
+    ARITHMETICS = (None, "fp32", "bf16x3")
+
+    @classmethod
+    def _check_arithmetic(cls, arithmetic):
+        """True for "bf16x3", False for None / "fp32"; anything else is refused (no device is touched)."""
+        if arithmetic not in cls.ARITHMETICS:
+            raise _lib.FacppgError("WaveGlow: arithmetic=%r: expected None, 'fp32' or 'bf16x3'" % (arithmetic,))
+        return arithmetic == "bf16x3"
+
+    def _split_handle(self, device):
+        """The split-bf16 handle (facppg_wg_split_create) for ``device``: lives beside the fp32 one, validated by WeightIdentity
+        in the same way and dropped by everything that drops it (_release)."""
+        h = self.__dict__.get("_facppg_split_handle")
+        if h is not None and h[1] == device and h[2].unchanged():
+            return h[0]
+        if h is not None:              # its weights changed (or it is another device's): the fp32 handle's did too
+            self._release()
+        L = _lib.load()
+        cfg = self._config()
+        blob = self._flat_weights().to(device).contiguous()
+        if blob.numel() != L.facppg_wg_weight_count(cfg):
+            raise _lib.FacppgError("weight blob has %d values, library expects %d (unsupported config: %s)" % (
+                blob.numel(), L.facppg_wg_weight_count(cfg), L.facppg_last_error().decode()))
+        out = _lib.ctypes.c_void_p()
+        with torch.cuda.device(device):
+            _lib.check(L.facppg_wg_split_create(cfg, _lib.ptr(blob), blob.numel(), device.index,
+                                                _lib.current_stream(device), _lib.ctypes.byref(out)))
+        self.__dict__["_facppg_split_handle"] = (out, device, _lib.WeightIdentity(self))
+        return out
+
+    def _infer_split(self, spect, sigma, z, lengths, seed, utterance_seeds):
+        """infer(arithmetic="bf16x3"): one launch sequence of facppg_wg_split_infer, the arguments normalised by _infer_args."""
+        dev = spect.device
+        pre = self.__dict__.pop("_facppg_prepared", None)
+        cur = self.__dict__.get("_facppg_split_handle")
+        h = pre[0] if (pre is not None and pre[1] == dev and cur is not None and cur[0] is pre[0]) else self._split_handle(dev)
+        spect = spect.contiguous()
+        B, _, T = spect.shape
+        hop = self.upsample.stride[0]
+        zt, lengths, seed, utterance_seeds = self._infer_args(B, T, torch.float32, z, lengths, seed, utterance_seeds, dev)
+        if utterance_seeds is not None:
+            zt = self.draw_noise(utterance_seeds, T, dev)
+        lt = _lib.upload(lengths, torch.int32, dev) if isinstance(lengths, list) else lengths
+        audio = (torch.empty if lt is None else torch.zeros)(B, T * hop, dtype=torch.float32, device=dev)
+        L = _lib.load()
+        nbytes = L.facppg_wg_split_workspace_bytes(h, B, T)
+        wss = self.__dict__.setdefault("_facppg_ws", {})
+        ws = wss.get("bf16x3")
+        if ws is None or ws.numel() < nbytes or ws.device != dev:
+            ws = wss["bf16x3"] = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+        with torch.cuda.device(dev):
+            _lib.check(L.facppg_wg_split_infer(h, _lib.ptr(spect), _lib.ptr(lt), _lib.ptr(zt), seed & 0xFFFFFFFFFFFFFFFF, float(sigma),
+                                               B, T, _lib.ptr(audio), _lib.ptr(ws), ws.numel(), _lib.current_stream(dev)))
+        return audio
 
     def _half_handle(self, h):
         """Whether ``h`` -- the module's current handle -- holds fp16 images: _precision() as it was when the handle was built
@@ -993,6 +1057,7 @@ class WaveGlow(torch.nn.Module):
     def __getstate__(self):                              # never pickle device handles
         d = dict(self.__dict__)
         d.pop("_facppg_handle", None)
+        d.pop("_facppg_split_handle", None)
         d.pop("_facppg_prepared", None)
         d.pop("_facppg_ws", None)
         d.pop("_facppg_cond_stream", None)                # (facppg.pipeline.ConditioningStream: streams, events, GBs of seeds)
@@ -1335,12 +1400,14 @@ class WaveGlow(torch.nn.Module):
                                 evs, _lib.current_stream(dev)))
         return audio
 
-    def prepare(self, device):
+    def prepare(self, device, arithmetic=None):
         """Validate (or build) the packed weights for ``device`` NOW and remember that for the next ``infer`` on this thread's
         next call: the check walks ~1000 tensors (0.4 ms of host time); facppg.pipeline runs it while the acoustic model's
         decoder keeps the GPU busy instead of between the two models.  Single use: the next infer() -- whatever path it takes --
-        consumes it, and it is only honoured while the handle it validated is still the model's handle."""
-        self.__dict__["_facppg_prepared"] = (self._handle(device), device)
+        consumes it, and it is only honoured while the handle it validated is still the model's handle.  arithmetic: the one that
+        infer() will be called with (its handle is the one validated)."""
+        split = self._check_arithmetic(arithmetic)
+        self.__dict__["_facppg_prepared"] = (self._split_handle(device) if split else self._handle(device), device)
 
     def _checked_handle(self, dev):
         pre = self.__dict__.pop("_facppg_prepared", None)
@@ -1384,7 +1451,8 @@ class WaveGlow(torch.nn.Module):
                 raise _lib.FacppgError("lengths must be B values in [1, T]")
         return z, lengths, seed, utterance_seeds
 
-    def infer(self, spect, sigma=1.0, z=None, lengths=None, seed=None, utterance_seeds=None, groups=None, cond_first=False):
+    def infer(self, spect, sigma=1.0, z=None, lengths=None, seed=None, utterance_seeds=None, groups=None, cond_first=False,
+              arithmetic=None):
         """mel [B, n_mel, T] (GPU, fp32) -> audio [B, T*hop]   (glow.py:252-293); a .half() module takes a half mel and returns
         half audio on the fp16 MFMA kernels (glow.py:261-290, the reference's HalfTensor branch), with the same z / seed / lengths /
         utterance_seeds semantics and one launch sequence (groups 1).
@@ -1394,7 +1462,20 @@ class WaveGlow(torch.nn.Module):
         then conditioning; True: conditioning first, the order of the seeded path (infer_seeded), whose samples it then equals bit
         for bit; the two differ in their last bits (fp32 reassociation).  An fp32 module is conditioning-first already and
         refuses the keyword.  With `seed` alone the noise of a uniform batch is a function of (seed, batch
-        layout); a ragged batch with host-side lengths draws per-utterance streams derived from (seed, b), identical in both modes."""
+        layout); a ragged batch with host-side lengths draws per-utterance streams derived from (seed, b), identical in both modes.
+        arithmetic (per call): None / "fp32" = the module's own path, above; "bf16x3" (all-fp32 modules only) = the WaveNet
+        contractions on the bf16 MFMA with every fp32 operand split into two bf16 terms and three partial products accumulated
+        in fp32 (facppg_wg_split_infer): fp32 mel in, fp32 audio out, relative RMS ~7e-6 against the fp32 path; one launch
+        sequence (no groups=, no cond_first); an utterance gets the same bits in any batch."""
+        if self._check_arithmetic(arithmetic):
+            if groups is not None or cond_first:
+                raise _lib.FacppgError("WaveGlow.infer: arithmetic='bf16x3' runs one launch sequence in its own K order; "
+                                       "it takes neither groups= nor cond_first=True")
+            if spect.dtype != torch.float32 or self._precision() != torch.float32:
+                raise _lib.FacppgError("WaveGlow.infer: arithmetic='bf16x3' splits fp32 operands: an all-fp32 module and an fp32 mel "
+                                       "(a .half() module runs the fp16 kernels)")
+            _lib.require_cuda(spect, "WaveGlow.infer: spect")
+            return self._infer_split(spect, sigma, z, lengths, seed, utterance_seeds)
         _lib.require_cuda(spect, "WaveGlow.infer: spect")
         if spect.dtype != torch.float32 or self.upsample.weight.dtype != torch.float32:
             if self._precision() != torch.float16:

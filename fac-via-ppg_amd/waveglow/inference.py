@@ -3,7 +3,8 @@
 per file.  Files are synthesised as ONE padded batch with per-file lengths (same audio as one call per
 file; the reference loops one by one, inference.py:43-56).  ``--is_fp16`` does what the reference does (inference.py:38-48):
 the module is cast to half with its convinv layers kept in float, the mels are cast to half, and WaveGlow.infer runs the
-fp16 MFMA kernels (facppg_wg_infer_f16)."""
+fp16 MFMA kernels (facppg_wg_infer_f16).  ``--arithmetic bf16x3`` (not together with ``--is_fp16``) keeps the fp32 module and mels
+and runs WaveGlow.infer on split-bf16 operands (facppg_wg_split_infer)."""
 import argparse
 import os
 
@@ -13,7 +14,9 @@ from scipy.io.wavfile import write
 from waveglow.mel2samp import MAX_WAV_VALUE, files_to_list
 
 
-def main(mel_files, waveglow_path, sigma, output_dir, sampling_rate, is_fp16, batch_size=16):
+def main(mel_files, waveglow_path, sigma, output_dir, sampling_rate, is_fp16, batch_size=16, arithmetic=None):
+    if is_fp16 and arithmetic == "bf16x3":
+        raise ValueError("--arithmetic bf16x3 splits fp32 operands; it does not go with --is_fp16")
     mel_files = files_to_list(mel_files)
     waveglow = torch.load(waveglow_path, weights_only=False)['model']
     waveglow = waveglow.remove_weightnorm(waveglow)
@@ -32,7 +35,8 @@ def main(mel_files, waveglow_path, sigma, output_dir, sampling_rate, is_fp16, ba
         for b, m in enumerate(mels):
             batch[b, :, :lens[b]] = m
         with torch.no_grad():
-            audio = MAX_WAV_VALUE * waveglow.infer(batch.cuda(), sigma=sigma, lengths=lens if len(lens) > 1 else None).float()
+            audio = MAX_WAV_VALUE * waveglow.infer(batch.cuda(), sigma=sigma, lengths=lens if len(lens) > 1 else None,
+                                                       arithmetic=arithmetic).float()
         audio = audio.cpu().numpy()
         for b, p in enumerate(paths):
             name = os.path.splitext(os.path.basename(p))[0]
@@ -41,7 +45,7 @@ def main(mel_files, waveglow_path, sigma, output_dir, sampling_rate, is_fp16, ba
             print(audio_path)
 
 
-if __name__ == "__main__":
+def parse(argv=None):
     parser = argparse.ArgumentParser()
     parser.add_argument('-f', "--filelist_path", required=True)
     parser.add_argument('-w', '--waveglow_path', help='Path to waveglow decoder checkpoint with model')
@@ -49,5 +53,16 @@ if __name__ == "__main__":
     parser.add_argument("-s", "--sigma", default=1.0, type=float)
     parser.add_argument("--sampling_rate", default=22050, type=int)
     parser.add_argument("--is_fp16", action="store_true")
-    args = parser.parse_args()
-    main(args.filelist_path, args.waveglow_path, args.sigma, args.output_dir, args.sampling_rate, args.is_fp16)
+    parser.add_argument("--arithmetic", choices=("fp32", "bf16x3"), default=None,
+                        help="arithmetic of an fp32 module's WaveGlow.infer: fp32 (exact, the default) or bf16x3 (fp32 operands split "
+                             "into two bf16 terms on the bf16 MFMA, fp32-class accuracy); not together with --is_fp16")
+    args = parser.parse_args(argv)
+    if args.is_fp16 and args.arithmetic is not None:
+        parser.error("--arithmetic names the arithmetic of an fp32 module; it does not go with --is_fp16")
+    return args
+
+
+if __name__ == "__main__":
+    args = parse()
+    main(args.filelist_path, args.waveglow_path, args.sigma, args.output_dir, args.sampling_rate, args.is_fp16,
+         arithmetic=args.arithmetic)

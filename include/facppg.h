@@ -399,6 +399,33 @@ int facppg_wg_infer_seeded_f16(facppg_wg* h, const uint16_t* melp_dev, int T_lay
                                int seeded_frames, const uint16_t* z_dev, uint64_t seed, float sigma, uint16_t* audio_dev,
                                void* workspace_dev, size_t workspace_bytes, void* const* flow_events, void* stream);
 
+/* ---- WaveGlow.infer (glow.py:252-293) on SPLIT bf16 operands: fp32 interface and fp32-class accuracy on the bf16 MFMA.
+ * Every fp32 operand x of a WaveNet contraction (glow.py:154-175) is written as hi + lo, hi = RNE_bf16(x), lo = RNE_bf16(x - hi),
+ * and a product A.B is A_hi.B_hi + A_hi.B_lo + A_lo.B_hi accumulated in fp32 (v_mfma_f32_32x32x16_bf16).  The hidden state, mel,
+ * noise and audio stay fp32 in memory; accumulators, biases, the gate, the skip sum and all flow-edge arithmetic (affine inverse,
+ * W_inverse, early z, start conv) are fp32.  The handle is a type of its own: it keeps only split weight images and is
+ * accepted by these five entry points alone.
+ * facppg_wg_split_create (glow.py:252-293; weights as glow.py:179-206 / common/utils.py:177-181): takes the SAME fp32 blob as
+ *   facppg_wg_create, folds it in fp32 and keeps each image as two bf16 planes; accepts the configurations
+ *   facppg_wg_create_f16 accepts and returns FACPPG_EUNSUPPORTED for the rest.
+ * facppg_wg_split_destroy (glow.py:252-293): frees the handle (NULL allowed).
+ * facppg_wg_split_workspace_bytes (glow.py:252-293): scratch bytes facppg_wg_split_infer needs for B mels of (max) T frames.
+ * facppg_wg_split_infer (glow.py:252-293): the signature and semantics of facppg_wg_infer -- fp32 mel_dev [B][n_mel][T],
+ *   T_valid_dev, flat injected z_dev or `seed` (facppg_wg_infer's Philox draw, unrounded), sigma, fp32 audio_dev [B][T*hop],
+ *   caller-owned workspace, caller's stream.  An utterance gets the same bits in any batch and any tile width.
+ * facppg_wg_split_last_launch_shape (glow.py:252-293, the layer launches of glow.py:154-175): frames per tile (32 or 64), waves
+ *   per workgroup and workgroups per launch of the most recent facppg_wg_split_infer.  The width is picked per call
+ *   from the launch shape; FACPPG_WG_SPLIT_TILE=32|64 in the environment forces one. */
+typedef struct facppg_wg_split facppg_wg_split;
+int facppg_wg_split_create(const facppg_wg_config* cfg, const float* weights_dev, size_t n_floats,
+                           int device, void* stream, facppg_wg_split** out);
+void facppg_wg_split_destroy(facppg_wg_split* h);
+size_t facppg_wg_split_workspace_bytes(const facppg_wg_split* h, int B, int T);
+int facppg_wg_split_infer(facppg_wg_split* h, const float* mel_dev, const int32_t* T_valid_dev,
+                          const float* z_dev, uint64_t seed, float sigma, int B, int T,
+                          float* audio_dev, void* workspace_dev, size_t workspace_bytes, void* stream);
+int facppg_wg_split_last_launch_shape(const facppg_wg_split* h, int* tile_frames, int* waves, int* n_tiles);
+
 /* ------------------------------------------------------------------------------------
  * STFT / mel analysis / denoiser (src/common/stft.py, src/common/layers.py,
  * src/waveglow/denoiser.py)
