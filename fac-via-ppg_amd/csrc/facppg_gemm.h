@@ -9,8 +9,9 @@
 // zero padding; also what makes padded batches equal to independent batch-1 runs).
 //
 // W is pre-packed once into the MFMA A-operand image (pack_a): float4 index
-// (mb * KG + g) * 64 + lane holds row mb*32 + (lane & 31), K entries 8g + 4(lane>>5) + {0..3},
-// K ordered tap-major (k = tap * Cin + c), zero padded to a multiple of 64.
+// (mb * (KG + 1) + g) * 64 + lane holds row mb*32 + (lane & 31), K entries 8g + 4(lane>>5) + {0..3},
+// K ordered tap-major (k = tap * Cin + c), zero padded to a multiple of 64 (KG = Kpad / 8 k-groups) and
+// followed by one all-zero k-group (g = KG) per row block; rows >= M are zero.
 #pragma once
 #include "facppg_common.h"
 

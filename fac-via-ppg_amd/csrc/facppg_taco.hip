@@ -1431,7 +1431,9 @@ __global__ __launch_bounds__(NTC) void k_decoder_split(DecArgs p) {
         if (has_pre) stat_mv16n<SKR_PROJ, NU>(w_p1, KP, sm + KA + KD, ustride, alive, part, tid);
         if (has_pre) FOR_ALIVE(u) {
           UTT(u);
-          const uint8_t* mk = p.masks + ((size_t)t * 2 * p.B + b) * p.P;
+          // (this runs ahead of the stop check below: an utterance that reaches max_steps comes here once more with t = max_steps,
+          //  one step past the caller's [max_steps][2][B][P] masks -- the row is formed and never read, from the last step's mask)
+          const uint8_t* mk = p.masks + ((size_t)min(t, p.max_steps - 1) * 2 * p.B + b) * p.P;
           if (tid < SSC && row0 + tid < p.P)
             xpub(X1 + row0 + tid, fmaxf(part[512 + u * SSC + tid] + p.b1p[row0 + tid], 0.0f) * (float)mk[row0 + tid] * 2.0f, tag);
         }
