@@ -1933,7 +1933,7 @@ __global__ void k_from_posmajor_f32(const float* __restrict__ src, float* __rest
 // accumulators so every weight it loads is reused UQ times; the mel values are LDS broadcasts.
 constexpr int UQ = 16, UMAXJ = 8;
 __global__ __launch_bounds__(256) void k_up_fwd(const float* __restrict__ mel, const float* __restrict__ W, const float* __restrict__ bias,
-                                                bf16_t* __restrict__ spect, int T, int nm, int hop, int ksize, int Lr, int n_limit) {
+                                                bf16_t* __restrict__ spect, int T, int Tq, int nm, int hop, int ksize, int Lr, int n_limit) {
   extern __shared__ __attribute__((aligned(16))) float smel[];  // [nm][UQ + UMAXJ]
   const int b = blockIdx.z, m = blockIdx.y, q0 = blockIdx.x * UQ;
   const int nj = (ksize + hop - 1) / hop, SW = UQ + UMAXJ;
@@ -1962,7 +1962,7 @@ __global__ __launch_bounds__(256) void k_up_fwd(const float* __restrict__ mel, c
 #pragma unroll
     for (int q = 0; q < UQ; ++q) {
       const int n = (q0 + q) * hop + pp;
-      if (q0 + q < T && n < n_limit) spect[((size_t)b * Lr + (n >> 3)) * (nm * 8) + m * 8 + (n & 7)] = f2bf(acc[q]);
+      if (q0 + q < Tq && n < n_limit) spect[((size_t)b * Lr + (n >> 3)) * (nm * 8) + m * 8 + (n & 7)] = f2bf(acc[q]);
     }
   }
 }
@@ -2155,7 +2155,7 @@ __global__ void k_up_pack_mel(const float* __restrict__ mel, float4* __restrict_
     float x = 0.0f;
     if (row < M && col < K && g < KG) {
       const int bb = r / d.Tq, q = r - bb * d.Tq, j = k / d.nm, mp = k - j * d.nm;
-      if (q - j >= 0) x = mel[((size_t)bb * d.nm + mp) * d.T + q - j];
+      if (q - j >= 0 && q - j < d.T) x = mel[((size_t)bb * d.nm + mp) * d.T + q - j];
     }
     v[t] = x;
   }
@@ -2204,7 +2204,9 @@ __global__ void k_up_unfold(const float* __restrict__ fold, float* __restrict__ 
 UpDims up_dims(int B, int T, int nm, int hop, int ksize, int L) {
   UpDims d;
   d.B = B; d.T = T; d.nm = nm; d.hop = hop; d.ksize = ksize; d.L = L; d.Lr = pad_len(L);
-  d.Tq = std::min(T, (L * 8 + hop - 1) / hop);     // frames q with q*hop < N produce samples < N
+  // output frames q with q*hop < 8 L.  Tq exceeds T when 8 L > T hop: the frames q >= T hold only the kernel tails of the mel
+  // frames q - j < T (taps j >= 1) plus the bias; the callers' (T - 1) hop + ksize >= 8 L bounds Tq by T - 1 + nj
+  d.Tq = (L * 8 + hop - 1) / hop;
   d.nj = (ksize + hop - 1) / hop; d.K = d.nj * nm; d.N = nm * hop; d.rows = B * d.Tq;
   return d;
 }
@@ -2237,9 +2239,9 @@ extern "C" int facppg_upsample_regroup_bf16(const float* mel_dev, const float* u
   FACPPG_REQUIRE((long)(T - 1) * hop + ksize >= (long)L * 8, FACPPG_EINVAL, "upsampled mel is shorter than the audio (glow.py:216)");
   hipStream_t s = (hipStream_t)stream_;
   const UpDims d = up_dims(B, T, n_mel, hop, ksize, L);
-  FACPPG_HIP_CHECK(hipMemsetAsync(spect_pm_dev, 0, (size_t)B * d.Lr * n_mel * 8 * 2, s));   // rows >= L (and samples no frame reaches) are zero
+  FACPPG_HIP_CHECK(hipMemsetAsync(spect_pm_dev, 0, (size_t)B * d.Lr * n_mel * 8 * 2, s));   // rows >= L are zero
   if (!upsample_gemm() || !ws_dev) {
-    k_up_fwd<<<dim3((d.Tq + UQ - 1) / UQ, n_mel, B), 256, (size_t)n_mel * (UQ + UMAXJ) * 4, s>>>(mel_dev, up_w_dev, up_b_dev, (bf16_t*)spect_pm_dev, T,
+    k_up_fwd<<<dim3((d.Tq + UQ - 1) / UQ, n_mel, B), 256, (size_t)n_mel * (UQ + UMAXJ) * 4, s>>>(mel_dev, up_w_dev, up_b_dev, (bf16_t*)spect_pm_dev, T, d.Tq,
                                                                                               n_mel, hop, ksize, d.Lr, L * 8);
     FACPPG_HIP_CHECK(hipGetLastError());
     return FACPPG_OK;
