@@ -672,9 +672,14 @@ __global__ __launch_bounds__(256, 2) void k_wn_layer(WnArgs p) {
 
   // residual inputs h_in[ch][pos] for this lane's res rows are fetched BEFORE the gate so their
   // latency hides under its VALU work; they seed the second GEMM's accumulators (bias + h_in), which
-  // makes the residual add free and takes the loads out of the epilogue
+  // makes the residual add free and takes the loads out of the epilogue.  Not in training (SAVE): a chain
+  // that starts at h_in rounds each of its 128 steps at the magnitude of h instead of that of the small
+  // residual -- h_{i+1} came out 8-10 x further from float64 than one rounded add -- so there
+  // the chain starts at the bias and h_in is added once, in the epilogue (64-wide training tiles have no 64 registers to
+  // carry it through the second GEMM: they fetch it again there, from L2).
+  constexpr bool RES_EARLY = !LAST && !PM && !(SAVE && NCB == 2);
   float hres[(LAST || PM) ? 1 : 2][NCB][16];
-  if constexpr (!LAST && !PM) {
+  if constexpr (RES_EARLY) {
 #pragma unroll
     for (int rb = 0; rb < 2; ++rb)
 #pragma unroll
@@ -724,7 +729,7 @@ __global__ __launch_bounds__(256, 2) void k_wn_layer(WnArgs p) {
     }
 #pragma unroll
     for (int cb = 1; cb < NCB; ++cb) acc[rb][cb] = acc[rb][0];
-    if constexpr (!LAST && !PM) {
+    if constexpr (!LAST && !PM && !SAVE) {
       if (rb < 2) {
 #pragma unroll
         for (int cb = 0; cb < NCB; ++cb)
@@ -863,7 +868,9 @@ __global__ __launch_bounds__(256, 2) void k_wn_layer(WnArgs p) {
           const int ch = chb + 8 * (r >> 2) + (r & 3);
           if (is_res) {
             const size_t o = ((size_t)b * C + ch) * p.Lp + in_off + col;
-            p.h_out[o] = acc[rb][cb][r];   // bias + h_in + res (h_in was folded into the accumulator)
+            float v = acc[rb][cb][r];      // bias + h_in + res (h_in was folded into the accumulator; training: added here)
+            if constexpr (SAVE && !LAST && !PM) v += RES_EARLY ? hres[rb & 1][cb][r] : p.h_in[o];
+            p.h_out[o] = v;
           } else {
             const size_t o = ((size_t)b * C + ch) * p.Lr + sk_off + col;
             p.skip[o] = (p.first ? 0.0f : p.skip[o]) + acc[rb][cb][r];
@@ -3461,7 +3468,12 @@ static int wn_check(const facppg_wn_weights* w, int n_in, int n_layers, int B, i
 //   h_all  [n_layers+1][B][256][Lp]  layer inputs (zero margins = conv padding), Lp = 128 + Lr + 128
 //   ts_all [n_layers][B][512][Lr]    tanh / sigmoid halves of each gate
 //   skip   [B][256][Lr]              total skip sum (input of the end conv)
-// a0 [B][n_in][L], spect_pad [B][640][Lr] (columns >= L must be readable), out [B][2*n_in][L].
+// a0 [B][n_in][L], spect_pad [B][640][Lr], out [B][2*n_in][L].  Columns [L, Lr) of spect_pad must be readable and may hold
+// anything, NaN included: they are B-operand columns of a tile's GEMMs, a column of the product depends on that column alone,
+// and every store is masked to columns < L.  h_all comes back EXACTLY zero outside columns [128, 128 + L) of its first n_layers
+// slabs and in the whole of h_all[n_layers] (the memset below; the taps of the next layer and of facppg_wn_weight_grads read
+// up to 128 columns either side); columns [L, Lr) of ts_all and skip are not written.  tests/test_gpu_wn_train.py holds all
+// of this with NaN-filled buffers.
 extern "C" int facppg_wn_forward_save(const facppg_wn_weights* wts, int n_in, int n_layers, const float* a0_dev,
                                       const float* spect_pad_dev, int B, int L, float* out_dev, float* h_all_dev,
                                       float* ts_all_dev, float* skip_dev, void* ws_, size_t ws_bytes, void* stream_) {
