@@ -412,7 +412,7 @@ class Tacotron2(nn.Module):
         return enc_m, dec_m
 
     def inference(self, inputs, lengths=None, dropout_masks=None, seed=None, utterance_seeds=None, step_limits=None, timer=None,
-                  while_decoding=None, frame_consumer=None, decoder_workgroups=None):
+                  while_decoding=None, frame_consumer=None, decoder_workgroups=None, frame_consumer_arithmetic=None):
         """inputs [B, n_symbols, Tin] (GPU fp32) -> [mel, mel_post, gate, alignments]
         = [B,80,Tout], [B,80,Tout], [B,Tout,1], [B,Tout,Tin]  (model.py:597-610).  For B > 1 the
         outputs are zero beyond each utterance's own Tout, kept in the result's ``out_lengths`` (InferenceOutputs).
@@ -424,7 +424,8 @@ class Tacotron2(nn.Module):
         acoustic model and the vocoder with the GPU idle).
         frame_consumer: optional (B = 1; facppg.pipeline.ConditioningStream): the split decoder publishes every mel frame the
         moment it exists and the consumer runs the postnet -- and whatever else it wants of the frames -- on a second stream
-        WHILE the decoder is still running; mel_post is then the consumer's (the same values bit for bit)."""
+        WHILE the decoder is still running; mel_post is then the consumer's (the same values bit for bit).
+        frame_consumer_arithmetic: handed to the consumer's begin() when not None (the vocoder arithmetic of this utterance)."""
         inputs = self.parse_input(inputs)
         _lib.require_cuda(inputs, "Tacotron2.inference: inputs")
         L = _lib.load()
@@ -482,7 +483,8 @@ class Tacotron2(nn.Module):
         out_len = arena[offs[5]:offs[5] + sizes[5]].view(torch.int32)
         opts = _lib.TacoDecodeOpts(max_workgroups=int(self.decoder_workgroups if decoder_workgroups is None else decoder_workgroups))
         if frame_consumer is not None and B == 1:
-            words = frame_consumer.begin(self, h, dev, steps, Tin)          # (zeroed on this stream, ahead of the decoder launch)
+            kind = {} if frame_consumer_arithmetic is None else {"arithmetic": frame_consumer_arithmetic}
+            words = frame_consumer.begin(self, h, dev, steps, Tin, **kind)   # (zeroed on this stream, ahead of the decoder launch)
             if words is not None:
                 opts.frame_words_dev, opts.frame_words_frames = words.data_ptr(), steps
         with torch.cuda.device(dev):

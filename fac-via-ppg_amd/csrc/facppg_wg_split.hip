@@ -25,14 +25,16 @@
 // Weight images: per A fragment of v_mfma_f32_32x32x16_bf16 (8 consecutive K entries per lane, one 16-byte load) the hi plane's
 // 64 lanes, then the lo plane's.
 //
-// Kernels: ks_pack_gate / ks_pack_res / ks_pack_end (create), ks_mel_pad, ks_begin (sigma*z, start conv of the last flow),
-// ks_wn_layer<LAST, NCB> (one fused WN layer per launch), ks_flow_end (affine inverse, W^-1, early z, next start conv or the
-// final interleave).
+// Kernels: ks_pack_gate / ks_pack_res / ks_pack_end (create), ks_mel_pad, ks_mel_cvt, ks_begin (sigma*z, start conv of the last
+// flow), ks_wn_layer<LAST, NCB, SEED> (one fused WN layer per launch), ks_cond_seed<BT> (the conditioning chunks of every layer
+// ahead of time), ks_flow_end (affine inverse, W^-1, early z, next start conv or the final interleave).
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <cstdlib>
 #include <cstring>
 #include <new>
+#include <type_traits>
 
 #include "facppg_wg_internal.h"
 
@@ -41,6 +43,7 @@ typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
 typedef float f32x2v __attribute__((ext_vector_type(2)));
 typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
 typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
+typedef float f32x4v __attribute__((ext_vector_type(4)));
 
 struct facppg_wg_split {
   facppg_wg_config cfg;
@@ -174,6 +177,10 @@ __global__ void ks_mel_pad(const float* __restrict__ mel, float* __restrict__ me
 //              summed in wave order and added to the running skip rows (first layer: + the folded end bias)
 // Every output column is computed the same way in every tile width (same chunk order, same MFMA order, same wave-order sum), so
 // an utterance gets the same bits in any batch and any tile width.
+// SEED launches (32-frame tiles, one utterance) run CONDITIONING-FIRST: the ncond conditioning chunks in their own order from zero
+// accumulators, then the tap chunks -- the order in which a tile may start from ks_cond_seed's accumulators instead of running the
+// conditioning chunks itself (tiles [0, seed_tiles) do; seeded or not, a column gets the same bits).  Their samples differ from
+// the tap-first launches' in the last bits (fp32 reassociation); the SEED = false instantiations are the code they were.
 // ------------------------------------------------------------------------------------------
 struct WnSplitArgs {
   const float* h_in;
@@ -187,11 +194,18 @@ struct WnSplitArgs {
   int T, P, Tr, Tqp, dil, first, nconv, ncond, kc;
 };
 
+// the arguments of a SEED launch: the layer's own, and where its seeds are
+struct WnSplitSeedArgs : WnSplitArgs {
+  const float4* seeds;       // this (flow, layer)'s [P][seed_nt][8 waves][2][4][64 lanes] accumulators (ks_cond_seed)
+  int seed_nt, seed_tiles;   // tiles per phase row of the seed buffer; tiles [0, seed_tiles) of the launch start from their seeds
+};
+
 template <int NCB>
 constexpr int wns_lds_bytes() { return 32 * NCB * (2 * ZP + 4 * SP) * 2; }
 
-template <bool LAST, int NCB>
-__global__ __launch_bounds__(512, 1) void ks_wn_layer(WnSplitArgs p) {
+template <bool LAST, int NCB, bool SEED = false>
+__global__ __launch_bounds__(512, 1) void ks_wn_layer(std::conditional_t<SEED, WnSplitSeedArgs, WnSplitArgs> p) {
+  static_assert(!SEED || NCB == 1, "seeds are kept per 32-frame tile");
   constexpr int TW = 32 * NCB;
   static_assert(8 * TW <= 512, "one staged 8-element vector per thread and chunk");
   extern __shared__ __align__(16) char smem[];
@@ -212,6 +226,15 @@ __global__ __launch_bounds__(512, 1) void ks_wn_layer(WnSplitArgs p) {
     qs[t] = f; php[t] = s - f * P;
   }
   const int nch = p.nconv + p.ncond;
+  // SEED: step c of the loop runs chunk kmap(c) -- the conditioning chunks, then the taps --, and a seeded tile starts at step
+  // ncond from ks_cond_seed's accumulators: the registers those first steps would have left
+  bool seeded = false;
+  if constexpr (SEED) seeded = (int)blockIdx.x < p.seed_tiles;
+  const int c_lo = seeded ? p.ncond : 0;
+  auto kmap = [&](int c) __attribute__((always_inline)) {
+    if constexpr (SEED) return c < p.ncond ? c + p.nconv : c - p.ncond;
+    else return c;
+  };
   const size_t hrow = (size_t)b * P;   // (b, phase) row base of h / xa, in units of Tqp frames
   const bool stager = tid < 8 * TW;
   const int scol = tid >> 3, skv = tid & 7;
@@ -265,15 +288,27 @@ __global__ __launch_bounds__(512, 1) void ks_wn_layer(WnSplitArgs p) {
       for (int r = 0; r < 16; ++r) acc[m][n][r] = 0.0f;
   float4 sr[2];
   u32x4 ar[4][2][2], an[4][2][2];
-  load_a(0, ar);
-  load_stage(0, sr);
+  load_a(kmap(c_lo), ar);
+  load_stage(kmap(c_lo), sr);
+  if constexpr (SEED) {
+    if (seeded) {
+      const float4* sp = p.seeds + ((size_t)ph * p.seed_nt + blockIdx.x) * 4096 + w * 512 + lane;
+#pragma unroll
+      for (int m = 0; m < 2; ++m)
+#pragma unroll
+        for (int g = 0; g < 4; ++g) {
+          const f32x4v v = __builtin_nontemporal_load((const f32x4v*)(sp + (m * 4 + g) * 64));   // read once
+          acc[m][0][4 * g + 0] = v.x; acc[m][0][4 * g + 1] = v.y; acc[m][0][4 * g + 2] = v.z; acc[m][0][4 * g + 3] = v.w;
+        }
+    }
+  }
   store_stage(0, sr);
   __syncthreads();
-  for (int c = 0; c < nch; ++c) {
-    const int cn = c + 1 < nch ? c + 1 : c;
+  for (int c = c_lo; c < nch; ++c) {
+    const int cn = kmap(c + 1 < nch ? c + 1 : c);
     load_a(cn, an);
     load_stage(cn, sr);
-    const unsigned short* sb = stg + (size_t)((c & 1) * 2) * TW * SP;
+    const unsigned short* sb = stg + (size_t)(((c - c_lo) & 1) * 2) * TW * SP;
 #pragma unroll
     for (int kk = 0; kk < 4; ++kk) {
       u32x4 bh[NCB], bl[NCB];
@@ -296,7 +331,7 @@ __global__ __launch_bounds__(512, 1) void ks_wn_layer(WnSplitArgs p) {
 #pragma unroll
         for (int m = 0; m < 2; ++m) acc[m][n] = mfma_bf(ar[kk][m][1], bh[n], acc[m][n]);
     }
-    if (c + 1 < nch) store_stage((c + 1) & 1, sr);
+    if (c + 1 < nch) store_stage((c + 1 - c_lo) & 1, sr);
     __syncthreads();
 #pragma unroll
     for (int kk = 0; kk < 4; ++kk)
@@ -415,6 +450,149 @@ __global__ __launch_bounds__(512, 1) void ks_wn_layer(WnSplitArgs p) {
     float* dst = p.skip + (((size_t)b * 8 + j) * P + ph) * p.Tr + q;
     *dst = p.first ? p.endb[j] + s : *dst + s;
   }
+}
+
+// ------------------------------------------------------------------------------------------
+// ks_cond_seed<BT>: the conditioning chunks of every (flow, layer, phase) gate GEMM for a block of BT 32-frame tiles of ONE
+// utterance, ahead of the layers (WN.forward's cond_layers, glow.py:154-175, on the upsampled mel, glow.py:253-259).
+// The staged window is ks_wn_layer's load_stage for its conditioning chunks (fp32 melp, zeros for kk >= kc and for frames past the
+// padded length), split ONCE by split8 into the hi / lo planes the layer kernel would stage; the A fragments are the same u32x4 of
+// wcond, and per K step and accumulator the three MFMAs come in the layer kernel's order from zero accumulators: the registers
+// parked in the seed buffer are those a SEED ks_wn_layer holds after its first ncond steps, bit for bit.  No bias (it stays at the
+// gate).  The window depends on the frames alone: it is staged once per block ([ncond][hi, lo][32 BT][SP] bf16) and stays in LDS
+// while the workgroup streams one 640 KiB (hop 256) weight image after the other past it -- 2.0 GB per pass.
+// A fragments: four K steps (one chunk) in registers, each K step's refilled for the next chunk as soon as its MFMAs have
+// issued -- no second buffer, so that BT = 3 (96 accumulator registers) fits the 256 registers of a 512-thread workgroup.
+// Work item = (group of lpw layers, phase, block), block-major so that a workgroup restages only when its block changes.
+// ------------------------------------------------------------------------------------------
+struct SeedSplitArgs {
+  const float* melp;                // [Tqp][80] zero-margined mel frames
+  float4* seeds;                    // [layers_total][P][seed_nt][8][2][4][64]
+  const u32x4* wcond[MAXF * 8];     // per (flow, layer): [P][4 ncond][8][2][hi, lo][64]
+  int lpw, P, Tr, seed_nt;
+  int tile0, tile1, nblk;           // tiles [tile0, tile1) in nblk blocks of BT
+  int ncond, kc;
+  int layer0, layer1, items;
+  const int* skip;                  // optional (device): *skip != 0 -> the launch does nothing
+  int* counter;                     // bounded launch: hands out the items past the first gridDim (zero at launch), or null: strided
+};
+
+constexpr int SEED_LDS_MAX = 160 * 1024 - 64;   // a CU's LDS less the kernel's own word
+constexpr int SEED_BT_MAX = 3;
+constexpr size_t seed_window_bytes(int ncond, int bt) { return (size_t)ncond * 2 * 32 * bt * SP * 2; }
+
+template <int BT>
+__global__ __launch_bounds__(512) void ks_cond_seed(SeedSplitArgs p) {
+  constexpr int TW = 32 * BT;
+  extern __shared__ __align__(16) char smem[];
+  unsigned short* win = (unsigned short*)smem;   // [ncond][2 planes][TW][SP]
+  __shared__ int next_item;
+  const int tid = threadIdx.x, w = tid >> 6, lane = tid & 63, lr = lane & 31, hf = lane >> 5;
+  if (p.skip && *p.skip) return;
+  const int nlg = (p.layer1 - p.layer0 + p.lpw - 1) / p.lpw, per = nlg * p.P, ncks = 4 * p.ncond;
+  int cur_blk = -1;
+  for (int lin = (int)blockIdx.x; lin < p.items;) {
+    const int blk = lin / per, rest = lin - blk * per, lg = rest / p.P, ph = rest - lg * p.P;
+    const int t0 = p.tile0 + blk * BT;
+    if (blk != cur_blk) {              // (uniform over the workgroup)
+      __syncthreads();
+      for (int v = tid; v < p.ncond * TW * 8; v += 512) {
+        const int c = v / (TW * 8), r = v - c * (TW * 8), col = r >> 3, kv = r & 7;
+        const int q = t0 * 32 + col, kk = 64 * c + 8 * kv;
+        float4 x0 = make_float4(0.0f, 0.0f, 0.0f, 0.0f), x1 = x0;
+        if (kk < p.kc && q < p.Tr) {
+          const int j = kk / NMEL, m = kk % NMEL;
+          const float* src = p.melp + ((size_t)HQ + q - j) * NMEL + m;
+          x0 = *(const float4*)src; x1 = *(const float4*)(src + 4);
+        }
+        u32x4 hi, lo;
+        split8(x0, x1, hi, lo);
+        unsigned short* d = win + ((size_t)(c * 2) * TW + col) * SP + 8 * kv;
+        *(u32x4*)d = hi;
+        *(u32x4*)(d + TW * SP) = lo;
+      }
+      __syncthreads();
+      cur_blk = blk;
+    }
+    const int l0 = p.layer0 + lg * p.lpw, l1 = min(l0 + p.lpw, p.layer1);
+    for (int l = l0; l < l1; ++l) {
+      // (((kk*8 + w)*2 + m)*2 + plane)*64 + lane of K step kk
+      const u32x4* img = p.wcond[l] + (size_t)ph * ncks * 2048 + w * 256 + lane;
+      f32x16 acc[2][BT];
+#pragma unroll
+      for (int m = 0; m < 2; ++m)
+#pragma unroll
+        for (int n = 0; n < BT; ++n)
+#pragma unroll
+          for (int r = 0; r < 16; ++r) acc[m][n][r] = 0.0f;
+      u32x4 ar[4][2][2];
+#pragma unroll
+      for (int kk = 0; kk < 4; ++kk)
+#pragma unroll
+        for (int m = 0; m < 2; ++m)
+#pragma unroll
+          for (int pl = 0; pl < 2; ++pl) ar[kk][m][pl] = __builtin_nontemporal_load(img + kk * 2048 + (m * 2 + pl) * 64);
+      for (int c = 0; c < p.ncond; ++c) {
+        const int cn = c + 1 < p.ncond ? c + 1 : c;
+        const unsigned short* sb = win + (size_t)(c * 2) * TW * SP;
+#pragma unroll
+        for (int kk = 0; kk < 4; ++kk) {
+          u32x4 bh[BT], bl[BT];
+#pragma unroll
+          for (int n = 0; n < BT; ++n) {
+            const unsigned short* bp = sb + (32 * n + lr) * SP + 16 * kk + 8 * hf;
+            bh[n] = *(const u32x4*)bp;
+            bl[n] = *(const u32x4*)(bp + TW * SP);
+          }
+#pragma unroll
+          for (int n = 0; n < BT; ++n)
+#pragma unroll
+            for (int m = 0; m < 2; ++m) acc[m][n] = mfma_bf(ar[kk][m][0], bh[n], acc[m][n]);
+#pragma unroll
+          for (int n = 0; n < BT; ++n)
+#pragma unroll
+            for (int m = 0; m < 2; ++m) acc[m][n] = mfma_bf(ar[kk][m][0], bl[n], acc[m][n]);
+#pragma unroll
+          for (int n = 0; n < BT; ++n)
+#pragma unroll
+            for (int m = 0; m < 2; ++m) acc[m][n] = mfma_bf(ar[kk][m][1], bh[n], acc[m][n]);
+          // this K step's fragments of the next chunk, into the registers just read
+#pragma unroll
+          for (int m = 0; m < 2; ++m)
+#pragma unroll
+            for (int pl = 0; pl < 2; ++pl) ar[kk][m][pl] = __builtin_nontemporal_load(img + (size_t)(4 * cn + kk) * 2048 + (m * 2 + pl) * 64);
+        }
+      }
+#pragma unroll
+      for (int n = 0; n < BT; ++n) {
+        if (t0 + n >= p.tile1) break;
+        float4* dst = p.seeds + (((size_t)l * p.P + ph) * p.seed_nt + t0 + n) * 4096 + w * 512 + lane;
+#pragma unroll
+        for (int m = 0; m < 2; ++m)
+#pragma unroll
+          for (int g = 0; g < 4; ++g)
+            __builtin_nontemporal_store(f32x4v{acc[m][n][4 * g + 0], acc[m][n][4 * g + 1], acc[m][n][4 * g + 2], acc[m][n][4 * g + 3]},
+                                        (f32x4v*)(dst + (m * 4 + g) * 64));   // read back milliseconds later: not through the L2
+      }
+    }
+    if (p.counter) {
+      __syncthreads();
+      if (tid == 0) next_item = (int)gridDim.x + atomicAdd(p.counter, 1);
+      __syncthreads();
+      lin = next_item;
+    } else {
+      lin += (int)gridDim.x;
+    }
+  }
+}
+
+// frames [f0, f0 + n) of an fp32 mel [80][ld] (the streaming postnet's output) -> the zero-margined fp32 [Tqp][80] layout
+__global__ void ks_mel_cvt(const float* __restrict__ mel, int ld, float* __restrict__ melp, int f0, int n, const int* __restrict__ skip) {
+  if (skip && *skip) return;
+  const int idx = blockIdx.x * blockDim.x + threadIdx.x;
+  if (idx >= n * NMEL) return;
+  const int m = idx / n, q = f0 + idx % n;
+  melp[((size_t)HQ + q) * NMEL + m] = mel[(size_t)m * ld + q];
 }
 
 // ------------------------------------------------------------------------------------------
@@ -637,6 +815,9 @@ extern "C" int facppg_wg_split_create(const facppg_wg_config* cfg, const float* 
   if (e == hipSuccess) e = hipStreamSynchronize(s);   // (the fp32 images are read by the packers above)
   if (e == hipSuccess) e = hipFuncSetAttribute((const void*)ks_wn_layer<false, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, wns_lds_bytes<2>());
   if (e == hipSuccess) e = hipFuncSetAttribute((const void*)ks_wn_layer<true, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, wns_lds_bytes<2>());
+  if (e == hipSuccess) e = hipFuncSetAttribute((const void*)ks_cond_seed<1>, hipFuncAttributeMaxDynamicSharedMemorySize, SEED_LDS_MAX);
+  if (e == hipSuccess) e = hipFuncSetAttribute((const void*)ks_cond_seed<2>, hipFuncAttributeMaxDynamicSharedMemorySize, SEED_LDS_MAX);
+  if (e == hipSuccess) e = hipFuncSetAttribute((const void*)ks_cond_seed<3>, hipFuncAttributeMaxDynamicSharedMemorySize, SEED_LDS_MAX);
   facppg_wg_destroy(f);
   if (e != hipSuccess) {
     set_error("facppg_wg_split_create: %s", hipGetErrorString(e));
@@ -658,13 +839,16 @@ extern "C" int facppg_wg_split_last_launch_shape(const facppg_wg_split* h, int* 
   return FACPPG_OK;
 }
 
-extern "C" int facppg_wg_split_infer(facppg_wg_split* h, const float* mel_dev, const int32_t* T_valid_dev, const float* z_dev,
-                                     uint64_t seed, float sigma, int B, int T, float* audio_dev, void* ws_, size_t ws_bytes,
-                                     void* stream_) {
-  FACPPG_REQUIRE(h && mel_dev && audio_dev && ws_, FACPPG_EINVAL, "NULL argument");
-  FACPPG_REQUIRE(B > 0 && T > 0, FACPPG_EINVAL, "B and T must be positive (got %d, %d)", B, T);
-  FACPPG_REQUIRE(B <= 65535, FACPPG_EINVAL, "B too large");
-  const size_t need = facppg_wg_split_workspace_bytes(h, B, T);
+// WaveGlow.infer on a split handle.  melp_ext != null (B = 1): the caller's zero-margined fp32 mel buffer laid out, like `seeds`,
+// for T_layout >= T frames; the layer launches are then the SEED ones (32-frame tiles, conditioning-first): tiles wholly inside
+// [0, seeded_frames) start from their seeds, the others run full K in the same launches.  flow_events[k] (may be null): the
+// launches of flow k wait for it on the stream.
+static int wgs_infer(facppg_wg_split* h, const float* mel_dev, const int32_t* T_valid_dev, const float* z_dev, uint64_t seed,
+                     float sigma, int B, int T, float* audio_dev, void* ws_, size_t ws_bytes, void* stream_,
+                     const float* melp_ext = nullptr, const float* seeds_dev = nullptr, int seeded_frames = 0, int T_layout = 0,
+                     void* const* flow_events = nullptr) {
+  if (!melp_ext) T_layout = T;
+  const size_t need = facppg_wg_split_workspace_bytes(h, B, T_layout);
   FACPPG_REQUIRE(ws_bytes >= need, FACPPG_EWORKSPACE, "workspace has %zu bytes, need %zu", ws_bytes, need);
   const facppg_wg_config& c = h->cfg;
   {
@@ -672,7 +856,8 @@ extern "C" int facppg_wg_split_infer(facppg_wg_split* h, const float* mel_dev, c
     for (int k = 0; k < c.n_flows; ++k) tot += h->early[k] ? c.n_early_size : 0;
     FACPPG_REQUIRE(tot == 8, FACPPG_EUNSUPPORTED, "noise channel count %d != n_group", tot);
   }
-  const WsSplit w = wss_layout(c, B, T);
+  WsSplit w = wss_layout(c, B, T_layout);   // rows (Tr, Tqp) of the layout; positions of the T frames that are there
+  w.L = T * w.P;
   FACPPG_REQUIRE((1 << (c.wn_layers - 1)) / w.P + 1 <= HQ, FACPPG_EUNSUPPORTED, "hop %d: the dilated taps reach past the %d-frame margins",
                  c.hop_length, HQ);
   FACPPG_REQUIRE((double)B * w.P * w.Tqp * C < 2.0e9, FACPPG_EUNSUPPORTED, "B*T = %d*%d frames is too long", B, T);
@@ -680,7 +865,7 @@ extern "C" int facppg_wg_split_infer(facppg_wg_split* h, const float* mel_dev, c
   char* ws = (char*)ws_;
   float* hbuf[2] = {(float*)(ws + w.h0), (float*)(ws + w.h1)};
   float* xa = (float*)(ws + w.xa);
-  float* melp = (float*)(ws + w.melp);
+  const float* melp = melp_ext ? melp_ext : (const float*)(ws + w.melp);
   float* skip = (float*)(ws + w.skip);
   float* aud[2] = {(float*)(ws + w.aud0), (float*)(ws + w.aud1)};
   const int nf = c.n_flows;
@@ -694,8 +879,9 @@ extern "C" int facppg_wg_split_infer(facppg_wg_split* h, const float* mel_dev, c
     FACPPG_REQUIRE(v == 32 || v == 64, FACPPG_EINVAL, "FACPPG_WG_SPLIT_TILE=%s: expected 32 or 64", env);
     tw = v;
   }
+  if (melp_ext) tw = 32;   // seeds are kept per 32-frame tile
   FACPPG_HIP_CHECK(hipMemsetAsync(ws + w.h0, 0, w.melp - w.h0, s));   // h0, h1, xa: margins and frames past each utterance
-  ks_mel_pad<<<dim3((w.Tqp * NMEL + 255) / 256, B), 256, 0, s>>>(mel_dev, melp, T_valid_dev, T, w.Tqp);
+  if (!melp_ext) ks_mel_pad<<<dim3((w.Tqp * NMEL + 255) / 256, B), 256, 0, s>>>(mel_dev, (float*)(ws + w.melp), T_valid_dev, T, w.Tqp);
   const float* z = z_dev;
   if (!z) {
     wg_launch_noise((float*)(ws + w.z), (size_t)B * 8 * w.L, seed, s);
@@ -723,19 +909,25 @@ extern "C" int facppg_wg_split_infer(facppg_wg_split* h, const float* mel_dev, c
     }
   }
   size_t z_off = (size_t)B * h->n_rem[nf - 1] * w.L;
-  WnSplitArgs a;
+  WnSplitSeedArgs a;   // (an unseeded launch takes its WnSplitArgs part)
   memset(&a, 0, sizeof(a));
   a.xa = xa; a.melp = melp; a.skip = skip; a.t_valid = T_valid_dev;
   a.T = T; a.P = w.P; a.Tr = w.Tr; a.Tqp = w.Tqp; a.kc = h->kc; a.ncond = h->kcp / 64;
+  a.seed_nt = w.Tr / 32; a.seed_tiles = melp_ext ? std::min(seeded_frames, round_up(T, 32)) / 32 : 0;
   for (int k = nf - 1; k >= 0; --k) {
+    if (flow_events && flow_events[k]) FACPPG_HIP_CHECK(hipStreamWaitEvent(s, (hipEvent_t)flow_events[k], 0));
     a.endb = h->endb[k];
     for (int i = 0; i < c.wn_layers; ++i) {
+      if (melp_ext) a.seeds = (const float4*)seeds_dev + (size_t)(k * c.wn_layers + i) * w.P * a.seed_nt * 4096;
       const bool last = i == c.wn_layers - 1;
       a.h_in = hbuf[hi]; a.h_out = hbuf[hi ^ 1];
       a.wconv = h->wconv[k][i]; a.wcond = h->wcond[k][i]; a.wres = h->wres[k][i]; a.wend = h->wend[k][i];
       a.b1 = h->b1[k][i]; a.b2 = h->b2[k][i];
       a.dil = 1 << i; a.first = i == 0; a.nconv = i == 0 ? 1 : 12;
-      if (tw == 64) {
+      if (melp_ext) {
+        if (last) ks_wn_layer<true, 1, true><<<lgrid, 512, wns_lds_bytes<1>(), s>>>(a);
+        else ks_wn_layer<false, 1, true><<<lgrid, 512, wns_lds_bytes<1>(), s>>>(a);
+      } else if (tw == 64) {
         if (last) ks_wn_layer<true, 2><<<lgrid, 512, wns_lds_bytes<2>(), s>>>(a);
         else ks_wn_layer<false, 2><<<lgrid, 512, wns_lds_bytes<2>(), s>>>(a);
       } else {
@@ -766,4 +958,99 @@ extern "C" int facppg_wg_split_infer(facppg_wg_split* h, const float* mel_dev, c
   }
   FACPPG_HIP_CHECK(hipGetLastError());
   return FACPPG_OK;
+}
+
+extern "C" int facppg_wg_split_infer(facppg_wg_split* h, const float* mel_dev, const int32_t* T_valid_dev, const float* z_dev,
+                                     uint64_t seed, float sigma, int B, int T, float* audio_dev, void* ws_, size_t ws_bytes,
+                                     void* stream_) {
+  FACPPG_REQUIRE(h && mel_dev && audio_dev && ws_, FACPPG_EINVAL, "NULL argument");
+  FACPPG_REQUIRE(B > 0 && T > 0, FACPPG_EINVAL, "B and T must be positive (got %d, %d)", B, T);
+  FACPPG_REQUIRE(B <= 65535, FACPPG_EINVAL, "B too large");
+  return wgs_infer(h, mel_dev, T_valid_dev, z_dev, seed, sigma, B, T, audio_dev, ws_, ws_bytes, stream_);
+}
+
+extern "C" int facppg_wg_split_seed_layout(const facppg_wg_split* h, int T, int* Tqp, int* margin, size_t* seed_bytes,
+                                           int* max_block_tiles) {
+  FACPPG_REQUIRE(h && T > 0 && Tqp && margin && seed_bytes && max_block_tiles, FACPPG_EINVAL, "NULL argument or T <= 0");
+  const WsSplit w = wss_layout(h->cfg, 1, T);
+  *Tqp = w.Tqp; *margin = HQ;
+  *seed_bytes = (size_t)h->cfg.n_flows * h->cfg.wn_layers * w.P * (w.Tr / 32) * 4096 * sizeof(float4);
+  int bt = 0;
+  while (bt < SEED_BT_MAX && seed_window_bytes(h->kcp / 64, bt + 1) <= (size_t)SEED_LDS_MAX) ++bt;
+  *max_block_tiles = bt;
+  return FACPPG_OK;
+}
+
+extern "C" int facppg_wg_split_mel_pad(const facppg_wg_split* h, const float* mel_dev, int T, int ld, int frame0, int nframes,
+                                       float* melp_dev, const int32_t* skip_dev, void* stream_) {
+  FACPPG_REQUIRE(h && mel_dev && melp_dev && T > 0, FACPPG_EINVAL, "NULL argument or T <= 0");
+  const WsSplit w = wss_layout(h->cfg, 1, T);
+  FACPPG_REQUIRE(frame0 >= 0 && nframes >= 0 && frame0 + nframes <= w.Tr && frame0 + nframes <= ld, FACPPG_EINVAL,
+                 "frames [%d, %d) do not lie inside the %d padded frames and the row length %d", frame0, frame0 + nframes, w.Tr, ld);
+  if (nframes == 0) return FACPPG_OK;
+  ks_mel_cvt<<<(nframes * NMEL + 255) / 256, 256, 0, (hipStream_t)stream_>>>(mel_dev, ld, melp_dev, frame0, nframes, skip_dev);
+  FACPPG_HIP_CHECK(hipGetLastError());
+  return FACPPG_OK;
+}
+
+extern "C" int facppg_wg_split_cond_seed(facppg_wg_split* h, const float* melp_dev, int T, int frame0, int nframes, int block_tiles,
+                                         int layers_per_workgroup, int flow0, int nflows, float* seeds_dev, size_t seed_bytes,
+                                         const int32_t* skip_dev, int max_workgroups, int32_t* counter_dev, void* stream_) {
+  FACPPG_REQUIRE(h && melp_dev && seeds_dev, FACPPG_EINVAL, "NULL argument");
+  FACPPG_REQUIRE(T > 0, FACPPG_EINVAL, "T must be positive (got %d)", T);
+  const facppg_wg_config& c = h->cfg;
+  const WsSplit w = wss_layout(c, 1, T);
+  size_t need = 0; int tqp = 0, mg = 0, bt_max = 0;
+  facppg_wg_split_seed_layout(h, T, &tqp, &mg, &need, &bt_max);
+  FACPPG_REQUIRE(seed_bytes >= need, FACPPG_EWORKSPACE, "seed buffer has %zu bytes, need %zu", seed_bytes, need);
+  FACPPG_REQUIRE(frame0 >= 0 && frame0 % 32 == 0 && nframes > 0 && frame0 + nframes <= w.Tr, FACPPG_EINVAL,
+                 "frames [%d, %d): the first must be a multiple of 32 and the range inside the %d padded frames", frame0, frame0 + nframes, w.Tr);
+  FACPPG_REQUIRE(layers_per_workgroup >= 1, FACPPG_EINVAL, "layers_per_workgroup >= 1");
+  FACPPG_REQUIRE(bt_max >= 1, FACPPG_EUNSUPPORTED, "hop %d: the conditioning window of one 32-frame tile (%zu bytes) does not fit the LDS",
+                 c.hop_length, seed_window_bytes(h->kcp / 64, 1));
+  FACPPG_REQUIRE(block_tiles >= 1 && block_tiles <= bt_max, FACPPG_EINVAL,
+                 "block_tiles = %d: the window of %zu bytes per tile must fit %d bytes of LDS and %d accumulator tiles the registers: "
+                 "the maximum is %d", block_tiles, seed_window_bytes(h->kcp / 64, 1), SEED_LDS_MAX, SEED_BT_MAX, bt_max);
+  if (nflows <= 0) { flow0 = 0; nflows = c.n_flows; }
+  FACPPG_REQUIRE(flow0 >= 0 && flow0 + nflows <= c.n_flows, FACPPG_EINVAL, "flows [%d, %d) of %d", flow0, flow0 + nflows, c.n_flows);
+  FACPPG_REQUIRE(c.n_flows * c.wn_layers <= MAXF * 8, FACPPG_EUNSUPPORTED, "too many layers");
+  SeedSplitArgs a;
+  memset(&a, 0, sizeof(a));
+  a.melp = melp_dev; a.seeds = (float4*)seeds_dev; a.skip = skip_dev;
+  for (int k = 0; k < c.n_flows; ++k)
+    for (int i = 0; i < c.wn_layers; ++i) a.wcond[k * c.wn_layers + i] = h->wcond[k][i];
+  a.lpw = layers_per_workgroup; a.P = w.P; a.Tr = w.Tr; a.seed_nt = w.Tr / 32;
+  const int ntiles = (nframes + 31) / 32;
+  a.tile0 = frame0 / 32; a.tile1 = a.tile0 + ntiles; a.nblk = (ntiles + block_tiles - 1) / block_tiles;
+  a.ncond = h->kcp / 64; a.kc = h->kc;
+  a.layer0 = flow0 * c.wn_layers; a.layer1 = (flow0 + nflows) * c.wn_layers;
+  a.items = (a.layer1 - a.layer0 + a.lpw - 1) / a.lpw * w.P * a.nblk;
+  size_t lds = seed_window_bytes(a.ncond, block_tiles);
+  // a BOUNDED launch (the caller shares the GPU with other streams) asks for a CU's whole LDS per workgroup, as
+  // facppg_wg_cond_seed does: one workgroup per CU and no other stream's small workgroups next to it
+  const int max_wgs = max_workgroups / 8 * 8;
+  const bool bounded = max_wgs > 0 && max_wgs < a.items;
+  if (max_workgroups > 0) lds = (size_t)SEED_LDS_MAX;
+  a.counter = bounded ? counter_dev : nullptr;
+  FACPPG_REQUIRE(!bounded || counter_dev, FACPPG_EINVAL, "a bounded launch needs counter_dev");
+  const unsigned grid = (unsigned)(bounded ? max_wgs : a.items);
+  hipStream_t s = (hipStream_t)stream_;
+  switch (block_tiles) {
+    case 1: ks_cond_seed<1><<<grid, 512, lds, s>>>(a); break;
+    case 2: ks_cond_seed<2><<<grid, 512, lds, s>>>(a); break;
+    default: ks_cond_seed<3><<<grid, 512, lds, s>>>(a); break;
+  }
+  FACPPG_HIP_CHECK(hipGetLastError());
+  return FACPPG_OK;
+}
+
+extern "C" int facppg_wg_split_infer_seeded(facppg_wg_split* h, const float* melp_dev, int T_layout, int T, const float* seeds_dev,
+                                            int seeded_frames, const float* z_dev, uint64_t seed, float sigma, float* audio_dev,
+                                            void* ws_, size_t ws_bytes, void* const* flow_events, void* stream_) {
+  FACPPG_REQUIRE(h && melp_dev && seeds_dev && audio_dev && ws_, FACPPG_EINVAL, "NULL argument");
+  FACPPG_REQUIRE(T > 0 && T_layout >= T, FACPPG_EINVAL, "need 0 < T <= T_layout (got %d, %d)", T, T_layout);
+  FACPPG_REQUIRE(seeded_frames >= 0 && seeded_frames % 32 == 0 && seeded_frames <= round_up(T, 32), FACPPG_EINVAL,
+                 "seeded_frames = %d: expected a multiple of 32 in [0, %d]", seeded_frames, round_up(T, 32));
+  return wgs_infer(h, nullptr, nullptr, z_dev, seed, sigma, 1, T, audio_dev, ws_, ws_bytes, stream_, melp_dev, seeds_dev, seeded_frames,
+                   T_layout, flow_events);
 }

@@ -160,6 +160,10 @@ def _declare(lib):
         "facppg_wg_split_workspace_bytes": (sz, [vp, c.c_int, c.c_int]),
         "facppg_wg_split_infer": (c.c_int, [vp, vp, vp, vp, u64, f32, c.c_int, c.c_int, vp, vp, sz, vp]),
         "facppg_wg_split_last_launch_shape": (c.c_int, [vp, c.POINTER(c.c_int), c.POINTER(c.c_int), c.POINTER(c.c_int)]),
+        "facppg_wg_split_seed_layout": (c.c_int, [vp, c.c_int, c.POINTER(c.c_int), c.POINTER(c.c_int), c.POINTER(sz), c.POINTER(c.c_int)]),
+        "facppg_wg_split_mel_pad": (c.c_int, [vp, vp, c.c_int, c.c_int, c.c_int, c.c_int, vp, vp, vp]),
+        "facppg_wg_split_cond_seed": (c.c_int, [vp, vp, c.c_int, c.c_int, c.c_int, c.c_int, c.c_int, c.c_int, c.c_int, vp, sz, vp, c.c_int, vp, vp]),
+        "facppg_wg_split_infer_seeded": (c.c_int, [vp, vp, c.c_int, c.c_int, vp, c.c_int, vp, c.c_uint64, f32, vp, vp, sz, vp, vp]),
         "facppg_stft_create": (c.c_int, [c.c_int, c.c_int, vp, vp, vp, vp, c.c_int, c.c_int, vp, c.POINTER(vp)]),
         "facppg_stft_destroy": (None, [vp]),
         "facppg_stft_workspace_bytes": (sz, [vp, c.c_int, c.c_int]),

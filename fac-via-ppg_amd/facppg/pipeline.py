@@ -18,7 +18,7 @@ class Synthesizer(object):
     (``{'model': ...}``, train_waveglow.py:56-64) once with weight norm removed for synthesis
     (utils.py:177-181) and once as pickled for the denoiser's bias estimate (generate_synthesis.py:58-61)."""
 
-    def __init__(self, ppg2mel_path, waveglow_path, hparams=None, denoiser_mode='zeros', vocoder_arithmetic=None):
+    def __init__(self, ppg2mel_path, waveglow_path, hparams=None, denoiser_mode='zeros', vocoder_arithmetic=None, vocoder_stream=None):
         from common.hparams import create_hparams_stage
         from common.utils import load_waveglow_model
         from script.train_ppg2mel import load_model
@@ -32,9 +32,12 @@ class Synthesizer(object):
         # the vocoder's arithmetic of every call (WaveGlow.infer's ``arithmetic``); the denoiser's bias spectrum above is formed on
         # the fp32 path either way
         self.vocoder_arithmetic = _checked_arithmetic(vocoder_arithmetic)
+        # synthesize()'s ``vocoder_stream`` of every one-utterance call (True: a "bf16x3" vocoder takes the streamed, conditioning-first path)
+        self.vocoder_stream = _checked_stream(vocoder_stream)
 
     def __call__(self, ppgs, sigma=0.6, strength=0.005, **kw):
         kw.setdefault("vocoder_arithmetic", self.vocoder_arithmetic)
+        kw.setdefault("vocoder_stream", self.vocoder_stream)
         return synthesize(ppgs, self.tacotron, self.waveglow, self.denoiser, sigma=sigma, strength=strength, **kw)
 
     def stream(self, jobs, sigma=0.6, strength=0.005, **kw):
@@ -86,7 +89,16 @@ class ConditioningStream(object):
     samples of the unstreamed pipeline, which runs a half vocoder conditioning-first for one utterance too
     (tests/test_gpu_stream_f16.py).
 
-    Host flow of one utterance: begin() (precision, layout, zeroed frame words) -> enqueue() (per planned block: _mel_block on
+    The split-bf16 arithmetic of an fp32 vocoder (synthesize(vocoder_arithmetic="bf16x3", vocoder_stream=True): opt-in per call) is
+    the third kind and streams like the fp16 one: every block's postnet columns are copied into the split path's fp32 [Tqp][80] mel
+    buffer behind the postnet (facppg_wg_split_mel_pad), the seed passes are ks_cond_seed's on the split handle (raw fp32 sums of the
+    split products, 2.0 GB of hi / lo images per pass, block_tiles clamped to what the LDS holds), the layer launches run
+    conditioning-first (facppg_wg_split_infer_seeded) and the tail tiles get their seeds from one more pass behind the decoder.  Bit
+    for bit the samples of the unstreamed opt-in call (mel_pad + infer_seeded with no seeded frame; tests/test_gpu_stream_bf16x3.py);
+    in the last bits NOT those of the plain vocoder_arithmetic="bf16x3" call, which sums the taps first and never comes here.  One
+    model pair may serve utterances of its precision's kind and of this one alternately: the buffers are re-laid-out per kind.
+
+    Host flow of one utterance: begin() (kind, layout, zeroed frame words) -> enqueue() (per planned block: _mel_block on
     the postnet stream, _seed_pass on the seed stream) -> finish() (_mel_block for the frames behind the last block) -> vocode()
     (tail_pass, possibly one more _seed_pass, WaveGlow.infer_seeded)."""
 
@@ -99,7 +111,9 @@ class ConditioningStream(object):
         self.profile = False       # True: hipEvents around every seed pass of the following utterances (pass_ms)
         self.lock = threading.Lock()   # held by synthesize() for the whole utterance (buffers, streams and plan are per model pair)
         # per utterance: set by begin() (dtype, half, cap), enqueue() (cuts, the events, n_launch), finish() (Tout, seeded, void_blocks)
-        self.dtype, self.half, self.cap, self.lag = None, False, 0, None
+        self.dtype, self.half, self.split, self.cap, self.lag = None, False, False, 0, None
+        self.melp16 = self.melp_split = None
+        self.max_block_tiles = 4
         self.dev = self.steps = self.Tin = self.taco_handle = self.wg_handle = None
         self.cuts, self.n_extra, self.n_launch = [], 0, 0
         self.last_final, self.finals, self.flow_events, self.pass_events = None, [], {}, []
@@ -116,7 +130,8 @@ class ConditioningStream(object):
     @staticmethod
     def usable(tacotron, waveglow):
         """The streamed path exists for the reference's shapes on the folded, phase-major vocoder kernels, all fp32 or all fp16 (the
-        reference's .half() recipe): bf16 and mixed modules run unstreamed (or are refused)."""
+        reference's .half() recipe): bf16 and mixed modules run unstreamed (or are refused).  An all-fp32 vocoder streams its own
+        arithmetic and, for the calls that opt in, the split-bf16 one (begin() is told which)."""
         return ConditioningStream._switched_on(tacotron, waveglow) and ConditioningStream.precision(waveglow) is not None
 
     @staticmethod
@@ -140,6 +155,12 @@ class ConditioningStream(object):
     # 400: 16.1 -> 15.2; profiles/r11_stream_f16_sweep.txt) -- its layer launches are 32-frame tiles streamed or not, so a seeded
     # launch is shorter at any length; 64 frames is the shortest utterance the sweep covers.
     MIN_FRAMES = {torch.float32: 128, torch.float16: 64}
+    # The split-bf16 kind (opt-in calls): like fp16, its layer launches are 32-frame tiles streamed or not, so a seeded launch is
+    # shorter at any length; the figure is the shortest length of the sweep from which streamed wins at every longer one
+    # (profiles/r16_stream_split_sweep.txt: 64 frames 7.08 -> 5.76 ms, 100: 7.95 -> 6.64, 130: 8.82 -> 7.50, 200: 10.97 -> 9.44,
+    # 400: 19.18 -> 17.07, 1000: 41.32 -> 36.97).
+    MIN_FRAMES_SPLIT = 64
+    SPLIT = "bf16x3"   # the kind's name: WaveGlow's ``arithmetic``, tail_pass()'s ``precision``
 
     SLACK = 64   # frames past the PPG's length the buffers are laid out for (an utterance that runs on past them is finished unstreamed)
 
@@ -175,23 +196,26 @@ class ConditioningStream(object):
             return t[:numel]
         # (the layout queries validate the models' packed-weight handles -- ~1000 tensors, 0.2 - 0.4 ms of host time in front of the
         #  encoder: asked once per (step limit, layout), not per utterance)
-        lk = (dev, steps, cap, self.half)
+        lk = (dev, steps, cap, self.half, self.split)
         if self.layout_key != lk:
-            self.layout = self.waveglow.seed_layout(cap, dev) + (L.facppg_taco_postnet_stream_workspace_bytes(self.tacotron._handle(dev), cap),)
+            lay = self.waveglow.seed_layout(cap, dev, arithmetic=self.SPLIT) if self.split else self.waveglow.seed_layout(cap, dev) + (4,)
+            self.layout = lay + (L.facppg_taco_postnet_stream_workspace_bytes(self.tacotron._handle(dev), cap),)
             self.layout_key = lk
-        self.tqp, self.margin, seed_bytes, post_ws_bytes = self.layout
+        self.tqp, self.margin, seed_bytes, self.max_block_tiles, post_ws_bytes = self.layout
         # {value, frame + 1} words + the void flags + the work counters + mel_post in the vocoder's zero-margined layout: ONE allocation,
         # zeroed by one launch before every decode
-        # (a half vocoder: + the same frames in ITS layout, fp16 [tqp][NF], converted block by block behind the postnet)
+        # (a half vocoder: + the same frames in ITS layout, fp16 [tqp][NF], converted block by block behind the postnet; the split
+        #  kind: + the same in fp32 [tqp][NF])
         nw = steps * self.NF + 512
         n32 = (self.NF * self.tqp + 1) // 2
-        n16 = (self.NF * self.tqp + 3) // 4 if self.half else 0
+        n16 = (self.NF * self.tqp + 3) // 4 if self.half else n32 if self.split else 0
         self.zeroed = grown("zeroed", nw + n32 + n16, torch.int64, zero=True)
         self.melp16 = self.zeroed[nw + n32:nw + n32 + n16].view(torch.float16)[:self.NF * self.tqp].view(self.tqp, self.NF) if self.half else None
+        self.melp_split = self.zeroed[nw + n32:nw + n32 + n16].view(torch.float32)[:self.NF * self.tqp].view(self.tqp, self.NF) if self.split else None
         self.words = self.zeroed[:nw]
         self.void = self.words[steps * self.NF:].view(torch.int32)[:512]                  # one per block
         self.counters = self.words[steps * self.NF:].view(torch.int32)[512:]              # one per bounded seed launch
-        self.melp = self.zeroed[nw:].view(torch.float32)[:self.NF * self.tqp].view(self.NF, self.tqp)
+        self.melp = self.zeroed[nw:nw + n32].view(torch.float32)[:self.NF * self.tqp].view(self.NF, self.tqp)
         self.mel = grown("mel", self.NF * steps, torch.float32, zero=True).view(self.NF, steps)   # collected frames, channel-major
         if "void_host" not in self.store:
             self.store["void_host"] = torch.zeros(512, dtype=torch.int32).pin_memory()
@@ -234,8 +258,9 @@ class ConditioningStream(object):
         return cuts
 
     # ---- called by Tacotron2.inference
-    def begin(self, tacotron, handle, dev, steps, Tin):
-        """Before the decoder launch, on its stream: zeroed frame words.  Returns them (None: not usable for this call)."""
+    def begin(self, tacotron, handle, dev, steps, Tin, arithmetic=None):
+        """Before the decoder launch, on its stream: zeroed frame words.  Returns them (None: not usable for this call).
+        arithmetic: the vocoder arithmetic of THIS utterance -- None: the module's own (fp32 / fp16 kind); "bf16x3": the split kind."""
         self.active = False
         # Short utterances do not gain: up to 128 frames the unstreamed vocoder runs 16-frame tiles, one per CU, and a layer launch
         # lasts as long as ONE tile either way (measured, tools/stream_T_sweep.sh: 64 frames 6.9 -> 8.1 ms, 100 frames 8.2 -> 9.0
@@ -244,7 +269,10 @@ class ConditioningStream(object):
         if self.dtype is None:
             return None
         self.half = self.dtype == torch.float16
-        if min(steps, Tin) < int(os.environ.get("FACPPG_STREAM_MIN_FRAMES", self.MIN_FRAMES[self.dtype])):
+        self.split = arithmetic == self.SPLIT
+        if self.split and self.dtype != torch.float32:       # (split operands are an fp32 module's: the vocoder stage refuses the rest)
+            return None
+        if min(steps, Tin) < int(os.environ.get("FACPPG_STREAM_MIN_FRAMES", self.MIN_FRAMES_SPLIT if self.split else self.MIN_FRAMES[self.dtype])):
             return None
         self.cap = min(steps, -(-(Tin + self.SLACK) // 32) * 32)
         try:
@@ -269,7 +297,7 @@ class ConditioningStream(object):
         the side stream."""
         dev = self.dev
         self.cuts = self.plan(self.steps, self.Tin)
-        self.wg_handle = self.waveglow._handle(dev)
+        self.wg_handle = self.waveglow._split_handle(dev) if self.split else self.waveglow._handle(dev)
         f_prev = 0
         lpw = max(1, int(os.environ.get("FACPPG_STREAM_LPW", "1")))
         # The seed passes take the CUs the decoder leaves except `spare` of them, ONE workgroup per CU that holds the CU's whole LDS
@@ -317,13 +345,21 @@ class ConditioningStream(object):
             _lib.check(L.facppg_taco_postnet_range(self.taco_handle, _lib.ptr(self.mel), self.steps, f0, f1, Tout,
                                                    self.melp.data_ptr() + 4 * self.margin, self.tqp, _lib.ptr(self.post_ws),
                                                    self.post_ws.numel(), self.cap, _lib.ptr(void), st))
-        if self.half:
+        if self.half or self.split:
             c0 = max(0, f0 - self.lag)
-            self.waveglow.mel_convert(self.melp[:, self.margin:], self.cap, c0, (f1 if Tout else f1 - self.lag) - c0, self.melp16, skip=void,
-                                      handle=self.wg_handle)
+            self.waveglow.mel_convert(self.melp[:, self.margin:], self.cap, c0, (f1 if Tout else f1 - self.lag) - c0,
+                                      self.melp_split if self.split else self.melp16, skip=void, handle=self.wg_handle, **self._kind())
+
+    def _kind(self):
+        """The keyword that sends a WaveGlow seeded method to this utterance's kernels."""
+        return {"arithmetic": self.SPLIT} if self.split else {}
+
+    def _vocoder_mel(self):
+        return self.melp_split if self.split else self.melp16 if self.half else self.melp
 
     def _seed_pass(self, frame0, nframes, block_tiles, layers_per_workgroup, max_workgroups, skip=None, timed=False):
-        """One k_cond_seed launch over frames [frame0, frame0 + nframes), every flow, on the current stream.  max_workgroups None:
+        """One k_cond_seed launch over frames [frame0, frame0 + nframes), every flow, on the current stream (block_tiles clamped to
+        what the kind's seed kernel takes).  max_workgroups None:
         an unbounded launch; otherwise (0 included: the bound may come from the environment) the launch takes the utterance's next
         zeroed work counter, and runs unbounded once the counters are used up.  timed: hipEvents around it for pass_ms()."""
         counter = None
@@ -337,9 +373,9 @@ class ConditioningStream(object):
             stream = torch.cuda.current_stream(self.dev)
             e0 = torch.cuda.Event(enable_timing=True)
             e0.record(stream)
-        self.waveglow.cond_seed(self.melp16 if self.half else self.melp, self.cap, frame0, nframes, self.seeds, block_tiles=block_tiles,
+        self.waveglow.cond_seed(self._vocoder_mel(), self.cap, frame0, nframes, self.seeds, block_tiles=min(block_tiles, self.max_block_tiles),
                                 layers_per_workgroup=layers_per_workgroup, skip=skip, handle=self.wg_handle,
-                                max_workgroups=max_workgroups or 0, counter=counter)
+                                max_workgroups=max_workgroups or 0, counter=counter, **self._kind())
         if timed:
             e1 = torch.cuda.Event(enable_timing=True)
             e1.record(stream)
@@ -397,11 +433,13 @@ class ConditioningStream(object):
         fp16: seeded and unseeded tiles of the fp16 launches are both 32 frames wide, so a launch with ONE unseeded tile lasts as long
         as an unseeded launch (every tile has a CU of its own at these lengths): one more pass, one workgroup per CU walking the
         work items from a counter -- the pass streams the images fastest that way (200 frames, two tail tiles: 8.8 ms against
-        9.1 ms end to end with the in-kernel tail, profiles/r11_stream_f16_ab.txt).  Same samples either way."""
+        9.1 ms end to end with the in-kernel tail, profiles/r11_stream_f16_ab.txt).  Same samples either way.
+        "bf16x3" (the split kind): fp16's rule for fp16's reason -- seeded and unseeded tiles are both 32 frames wide (the block
+        width is clamped to the kernel's by _seed_pass; both variants at 200 frames: profiles/r16_stream_split_ab.txt)."""
         s_all = -(-T // 32) * 32
         if s_all <= seeded:
             return None
-        if precision == torch.float16:
+        if precision == torch.float16 or precision == ConditioningStream.SPLIT:
             return None if tail == "mixed" else (seeded, s_all - seeded, min(4, (s_all - seeded) // 32), 1, True)
         mixed_wgs = P * (seeded // 32 + -(-(T - seeded) // 16))
         seeded_wgs = P * (s_all // 32)
@@ -413,14 +451,15 @@ class ConditioningStream(object):
         unseeded: tail_pass); fp32 audio (a half vocoder's is widened as the unstreamed path's is)."""
         n_cu = torch.cuda.get_device_properties(self.dev).multi_processor_count
         s_done = self.seeded
-        job = self.tail_pass(self.dtype, self.Tout, s_done, self.waveglow.upsample.stride[0] // 8, n_cu, os.environ.get("FACPPG_STREAM_TAIL"))
+        job = self.tail_pass(self.SPLIT if self.split else self.dtype, self.Tout, s_done, self.waveglow.upsample.stride[0] // 8, n_cu,
+                             os.environ.get("FACPPG_STREAM_TAIL"))
         if job is not None:
             frame0, nframes, block_tiles, lpw, bounded = job
-            self._seed_pass(frame0, nframes, block_tiles, lpw, n_cu if bounded else None)
+            self._seed_pass(frame0, nframes, block_tiles, lpw, n_cu if bounded else None, timed=self.profile)
             s_done = frame0 + nframes
         self.active = False
-        audio = self.waveglow.infer_seeded(self.melp16 if self.half else self.melp, self.Tout, self.seeds, s_done, sigma=sigma, z=z, seed=seed,
-                                           handle=self.wg_handle, T_layout=self.cap, flow_events=self.flow_events)
+        audio = self.waveglow.infer_seeded(self._vocoder_mel(), self.Tout, self.seeds, s_done, sigma=sigma, z=z, seed=seed,
+                                           handle=self.wg_handle, T_layout=self.cap, flow_events=self.flow_events, **self._kind())
         return audio.float() if self.half else audio
 
 
@@ -467,7 +506,7 @@ def pad_ppgs(ppgs, device=None):
 
 
 def _acoustic(ppgs, tacotron, seed, dropout_masks, utterance_seeds, step_limits, timer=None, while_decoding=None, consumer=None,
-              decoder_workgroups=None):
+              decoder_workgroups=None, consumer_arithmetic=None):
     """PPG upload + Tacotron2.inference on the current stream -> (mel_post [B, 80, Tout], [Tout_i]).  Blocks the host once,
     for the decoder's output lengths."""
     dev = next(tacotron.parameters()).device
@@ -477,7 +516,8 @@ def _acoustic(ppgs, tacotron, seed, dropout_masks, utterance_seeds, step_limits,
     out = tacotron.inference(x, lengths=lens if len(lens) > 1 else None, dropout_masks=dropout_masks,
                              seed=seed, utterance_seeds=utterance_seeds, step_limits=step_limits,
                              while_decoding=while_decoding, frame_consumer=consumer if len(lens) == 1 else None,
-                             decoder_workgroups=decoder_workgroups, **({"timer": timer} if timer is not None else {}))
+                             decoder_workgroups=decoder_workgroups, **({"timer": timer} if timer is not None else {}),
+                             **({"frame_consumer_arithmetic": consumer_arithmetic} if consumer_arithmetic is not None and consumer is not None else {}))
     mel_post, tout = out[1], [int(v) for v in out.out_lengths]
     if consumer is not None and consumer.active:      # (the vocoder reads the stream's own mel buffer: no copy on the latency path)
         return mel_post, tout
@@ -493,9 +533,20 @@ def _checked_arithmetic(arithmetic):
     return None if arithmetic == "fp32" else arithmetic
 
 
-def _vocode(mel_post, tout, waveglow, denoiser, sigma, strength, seed, z, utterance_seeds, timer=None, consumer=None, arithmetic=None):
+def _checked_stream(vocoder_stream):
+    """The ``vocoder_stream`` of a call: None or True; anything else is refused here, before any model runs."""
+    if vocoder_stream is not None and vocoder_stream is not True:
+        from facppg.lib import FacppgError
+        raise FacppgError("vocoder_stream=%r: expected None or True" % (vocoder_stream,))
+    return vocoder_stream
+
+
+def _vocode(mel_post, tout, waveglow, denoiser, sigma, strength, seed, z, utterance_seeds, timer=None, consumer=None, arithmetic=None,
+            split_first=False):
     """WaveGlow.infer + Denoiser on the current stream -> audio [B, Tout_max * hop] on the device; no host waits beyond the
-    small uploads (lengths, seeds).  arithmetic: WaveGlow.infer's ("bf16x3": never streamed, ``consumer`` is None)."""
+    small uploads (lengths, seeds).  arithmetic: WaveGlow.infer's ("bf16x3": streamed only for the calls that opted in).
+    split_first: one utterance of an opt-in "bf16x3" call -- the conditioning-first split path, from the stream's seeds or, when
+    the stream did not run, from none (the same samples)."""
     hop = waveglow.upsample.stride[0]
     multi = len(tout) > 1
     wg_seeds = None if utterance_seeds is None else [int(v) + 1 for v in utterance_seeds]
@@ -508,6 +559,13 @@ def _vocode(mel_post, tout, waveglow, denoiser, sigma, strength, seed, z, uttera
         if wg_seeds is not None:
             z = waveglow.draw_noise(wg_seeds, tout[0], mel_post.device)
         audio = consumer.vocode(sigma, z=z, seed=seed)
+    elif split_first:
+        if wg_seeds is not None:
+            z = waveglow.draw_noise(wg_seeds, tout[0], mel_post.device)
+        waveglow._require_split_module("infer_seeded")
+        h = waveglow._checked_split_handle(mel_post.device)
+        melp = waveglow.mel_pad(mel_post[:, :, :tout[0]], handle=h, arithmetic=arithmetic)
+        audio = waveglow.infer_seeded(melp, tout[0], None, 0, sigma=sigma, z=z, seed=seed, handle=h, arithmetic=arithmetic)
     else:
         # one utterance through a half vocoder: the K order of the streamed path (conditioning first), so that the samples do not
         # depend on whether this utterance was streamed (too short, FACPPG_STREAM=0, outgrew the layout, stream busy)
@@ -527,7 +585,7 @@ def _vocode(mel_post, tout, waveglow, denoiser, sigma, strength, seed, z, uttera
 
 
 def synthesize(ppgs, tacotron, waveglow, denoiser=None, sigma=0.6, strength=0.005, seed=None, dropout_masks=None, z=None,
-               return_device=False, utterance_seeds=None, step_limits=None, timer=None, vocoder_arithmetic=None):
+               return_device=False, utterance_seeds=None, step_limits=None, timer=None, vocoder_arithmetic=None, vocoder_stream=None):
     """Returns (list of float32 waveforms [N_i], list of mel lengths).  Models must be on the GPU.
 
     One utterance (the latency path, the metric's "batch = 1"): the postnet and the conditioning part of the vocoder's gate GEMMs
@@ -536,15 +594,23 @@ def synthesize(ppgs, tacotron, waveglow, denoiser=None, sigma=0.6, strength=0.00
     so the result for an utterance is the same whatever batch, batch size or GPU it is synthesised in.
     step_limits: per-utterance max_decoder_steps (e.g. its PPG length).
     vocoder_arithmetic: WaveGlow.infer's ``arithmetic`` (None / "fp32": the module's own path; "bf16x3": split-bf16 operands on the
-    bf16 MFMA, fp32 samples out).  A "bf16x3" call always takes the unstreamed path: ConditioningStream is not used."""
+    bf16 MFMA, fp32 samples out).  A plain "bf16x3" call always takes the unstreamed path: ConditioningStream is not used.
+    vocoder_stream: None = the above in every respect; True with vocoder_arithmetic="bf16x3" and ONE utterance = the split
+    arithmetic in the conditioning-first K order, its conditioning work streamed under the decoder whenever the stream is usable
+    (long enough, FACPPG_STREAM not 0, not busy, inside its layout, memory for the seeds) and the same call unseeded when it is
+    not: the samples never depend on whether or how far the utterance was streamed; they differ from the plain "bf16x3" call's in
+    the last bits (fp32 reassociation, the same accuracy).  True with any other arithmetic changes nothing (those stream by their
+    own rules), and a batch of several utterances ignores the keyword and runs as without it -- as a .half() vocoder is
+    conditioning-first for one utterance only.  Any other value is refused before a model runs."""
     arithmetic = _checked_arithmetic(vocoder_arithmetic)
+    split_first = _checked_stream(vocoder_stream) is True and arithmetic == ConditioningStream.SPLIT and len(ppgs) == 1
     if timer is not None:
         timer.__init__()
     hop = waveglow.upsample.stride[0]
     with torch.no_grad():
         dev = next(waveglow.parameters()).device
         consumer = None
-        if len(ppgs) == 1 and arithmetic is None and ConditioningStream.usable(tacotron, waveglow):
+        if len(ppgs) == 1 and (arithmetic is None or split_first) and ConditioningStream.usable(tacotron, waveglow):
             consumer = waveglow.__dict__.get("_facppg_cond_stream")
             if consumer is None or consumer.tacotron is not tacotron:
                 consumer = waveglow.__dict__["_facppg_cond_stream"] = ConditioningStream(tacotron, waveglow)
@@ -557,8 +623,9 @@ def synthesize(ppgs, tacotron, waveglow, denoiser=None, sigma=0.6, strength=0.00
                                        # host work under the decoder's milliseconds: the vocoder's weight check (the stream does its own)
                                        while_decoding=lambda: None if (consumer is not None and consumer.active) else
                                        (waveglow.prepare(dev, arithmetic) if arithmetic is not None else waveglow.prepare(dev)),
-                                       consumer=consumer)
-            audio = _vocode(mel_post, tout, waveglow, denoiser, sigma, strength, seed, z, utterance_seeds, timer, consumer, arithmetic)
+                                       consumer=consumer, consumer_arithmetic=arithmetic if split_first else None)
+            audio = _vocode(mel_post, tout, waveglow, denoiser, sigma, strength, seed, z, utterance_seeds, timer, consumer, arithmetic,
+                            split_first)
         finally:
             if consumer is not None:
                 consumer.lock.release()

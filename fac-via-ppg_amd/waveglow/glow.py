@@ -931,7 +931,7 @@ class WaveGlow(torch.nn.Module):
     def last_launch_shape(self, arithmetic=None):
         """(frames per tile, waves per workgroup, workgroups per launch) of the WN-layer kernels of the most recent
         infer() -- which instantiation of the fused layer kernel ran (facppg_wg_last_launch_shape); arithmetic="bf16x3": of the
-        most recent infer(arithmetic="bf16x3") (facppg_wg_split_last_launch_shape)."""
+        most recent infer(arithmetic="bf16x3") or infer_seeded(arithmetic="bf16x3") (facppg_wg_split_last_launch_shape)."""
         split = self._check_arithmetic(arithmetic)
         h = self.__dict__.get("_facppg_split_handle" if split else "_facppg_handle")
         if h is None:
@@ -1001,12 +1001,16 @@ class WaveGlow(torch.nn.Module):
         self.__dict__["_facppg_split_handle"] = (out, device, _lib.WeightIdentity(self))
         return out
 
+    def _checked_split_handle(self, dev):
+        """The split handle for ``dev``: the one prepare(dev, "bf16x3") just validated (the token is consumed), or validated now."""
+        pre = self.__dict__.pop("_facppg_prepared", None)
+        cur = self.__dict__.get("_facppg_split_handle")
+        return pre[0] if (pre is not None and pre[1] == dev and cur is not None and cur[0] is pre[0]) else self._split_handle(dev)
+
     def _infer_split(self, spect, sigma, z, lengths, seed, utterance_seeds):
         """infer(arithmetic="bf16x3"): one launch sequence of facppg_wg_split_infer, the arguments normalised by _infer_args."""
         dev = spect.device
-        pre = self.__dict__.pop("_facppg_prepared", None)
-        cur = self.__dict__.get("_facppg_split_handle")
-        h = pre[0] if (pre is not None and pre[1] == dev and cur is not None and cur[0] is pre[0]) else self._split_handle(dev)
+        h = self._checked_split_handle(dev)
         spect = spect.contiguous()
         B, _, T = spect.shape
         hop = self.upsample.stride[0]
@@ -1321,17 +1325,60 @@ class WaveGlow(torch.nn.Module):
         _lib.check(layout(h, int(T), c.byref(tqp), c.byref(mg), c.byref(nb)))
         return tqp.value, mg.value, nb.value
 
-    def seed_layout(self, T, device):
+    # ---- the same on split-bf16 operands (arithmetic="bf16x3"): the split handle and the facppg_wg_split_* entry points
+    def _require_split_module(self, who):
+        if self._precision() != torch.float32:
+            raise _lib.FacppgError("WaveGlow.%s: arithmetic='bf16x3' splits fp32 operands: an all-fp32 module (a .half() module "
+                                   "runs the fp16 kernels)" % who)
+
+    def _resolve_split(self, who, dev, handle=None):
+        """The split handle the seeded methods run on: ``handle`` -- the module's current split handle, anything else is refused --
+        or, with None, the module's split handle for ``dev`` (validated or built now).  All-fp32 modules only."""
+        if handle is None:
+            self._require_split_module(who)
+            return self._split_handle(dev)
+        cur = self.__dict__.get("_facppg_split_handle")
+        if cur is None or cur[0] is not handle:
+            raise _lib.FacppgError("WaveGlow.%s: the handle passed in is not this module's current split-bf16 one (its weights "
+                                   "changed since)" % who)
+        return handle
+
+    def _split_seed_layout(self, h, T):
+        c = _lib.ctypes
+        tqp, mg, nb, bt = c.c_int(), c.c_int(), c.c_size_t(), c.c_int()
+        _lib.check(_lib.load().facppg_wg_split_seed_layout(h, int(T), c.byref(tqp), c.byref(mg), c.byref(nb), c.byref(bt)))
+        return tqp.value, mg.value, nb.value, bt.value
+
+    @staticmethod
+    def _check_split_mel_buffer(who, melp):
+        if melp.dtype != torch.float32:
+            raise _lib.FacppgError("%s: arithmetic='bf16x3' reads an fp32 mel buffer [Tqp, n_mel], this one is %s" % (who, melp.dtype))
+
+    def seed_layout(self, T, device, arithmetic=None):
         """(Tqp, margin, seed_bytes) for an utterance of T frames: the zero-margined mel buffer is [n_mel, Tqp] with frame q at
-        column margin + q; the seed buffer has seed_bytes bytes (facppg_wg_seed_layout)."""
+        column margin + q; the seed buffer has seed_bytes bytes (facppg_wg_seed_layout).  arithmetic="bf16x3": (Tqp, margin,
+        seed_bytes, max_block_tiles) of the split path -- the mel buffer is fp32 [Tqp, n_mel], frame q at ROW margin + q, and
+        cond_seed takes block_tiles up to max_block_tiles (facppg_wg_split_seed_layout)."""
+        if self._check_arithmetic(arithmetic):
+            return self._split_seed_layout(self._resolve_split("seed_layout", device), T)
         h, _, (layout, _, _) = self._resolve(device)
         return self._seed_layout(h, layout, T)
 
-    def mel_pad(self, mel, handle=None):
+    def mel_pad(self, mel, handle=None, arithmetic=None):
         """mel [1, n_mel, T] -> the zero-margined [n_mel, Tqp] buffer cond_seed / infer_seeded read; of a .half() module: an fp32
-        (or half) mel -> the fp16 [Tqp, n_mel] buffer, rounded to nearest even."""
+        (or half) mel -> the fp16 [Tqp, n_mel] buffer, rounded to nearest even.  arithmetic="bf16x3": an fp32 mel -> the fp32
+        [Tqp, n_mel] buffer of the split path."""
+        split = self._check_arithmetic(arithmetic)
         dev = mel.device
         T = mel.shape[2]
+        if split:
+            if mel.dtype != torch.float32:
+                raise _lib.FacppgError("WaveGlow.mel_pad: arithmetic='bf16x3' takes an fp32 mel (got %s)" % mel.dtype)
+            _lib.require_cuda(mel, "WaveGlow.mel_pad: mel")
+            h = self._resolve_split("mel_pad", dev, handle)
+            out = torch.zeros(self._split_seed_layout(h, T)[0], mel.shape[1], dtype=torch.float32, device=dev)
+            self.mel_convert(mel[0].contiguous(), T, 0, T, out, handle=h, arithmetic=arithmetic)
+            return out
         h, dt, (layout, _, _) = self._resolve(dev, handle)
         tqp = self._seed_layout(h, layout, T)[0]
         if dt == torch.float16:
@@ -1344,10 +1391,21 @@ class WaveGlow(torch.nn.Module):
             _lib.check(_lib.load().facppg_wg_mel_pad(h, _lib.ptr(m), T, m.stride(0), _lib.ptr(out), _lib.current_stream(dev)))
         return out
 
-    def mel_convert(self, mel, T, frame0, nframes, melp, skip=None, handle=None):
+    def mel_convert(self, mel, T, frame0, nframes, melp, skip=None, handle=None, arithmetic=None):
         """Frames [frame0, frame0 + nframes) of the fp32 ``mel`` [n_mel, >= frame0 + nframes] (row stride mel.stride(0)) into the
-        fp16 zero-margined ``melp`` [Tqp, n_mel] laid out for T frames (k16_mel_cvt), on the current stream.  .half() modules."""
+        fp16 zero-margined ``melp`` [Tqp, n_mel] laid out for T frames (k16_mel_cvt), on the current stream.  .half() modules.
+        arithmetic="bf16x3" (all-fp32 modules): into the split path's fp32 ``melp`` [Tqp, n_mel] (ks_mel_cvt)."""
+        split = self._check_arithmetic(arithmetic)
         dev = melp.device
+        if split:
+            if mel.dtype != torch.float32 or mel.stride(1) != 1:
+                raise _lib.FacppgError("mel_convert: fp32 rows in (got %s)" % mel.dtype)
+            self._check_split_mel_buffer("mel_convert", melp)
+            h = self._resolve_split("mel_convert", dev, handle)
+            with torch.cuda.device(dev):
+                _lib.check(_lib.load().facppg_wg_split_mel_pad(h, _lib.ptr(mel), int(T), mel.stride(0), int(frame0), int(nframes),
+                                                               _lib.ptr(melp), _lib.ptr(skip), _lib.current_stream(dev)))
+            return
         if mel.dtype != torch.float32 or melp.dtype != torch.float16 or mel.stride(1) != 1:
             raise _lib.FacppgError("mel_convert: fp32 rows in, the fp16 mel buffer out")
         with torch.cuda.device(dev):
@@ -1356,16 +1414,23 @@ class WaveGlow(torch.nn.Module):
                                                          _lib.current_stream(dev)))
 
     def cond_seed(self, melp, T, frame0, nframes, seeds, block_tiles=1, layers_per_workgroup=4, skip=None, handle=None, flows=None,
-                  max_workgroups=0, counter=None):
+                  max_workgroups=0, counter=None, arithmetic=None):
         """Form the gate accumulators' seeds (bias + conditioning sums, k_cond_seed) of frames [frame0, frame0 + nframes) of the
         utterance whose zero-margined mel frames are ``melp``, for every flow (or flows = (first, count)), layer and phase, on the
         current stream.  max_workgroups > 0 bounds the launch (its workgroups then take the work items from ``counter``, a zeroed
         int32 on the device): the CUs it does not fill stay free for whoever else needs one right away.  A .half() module takes
-        its fp16 mel buffer (mel_pad / mel_convert) and forms the raw conditioning sums, no bias (k16_cond_seed)."""
+        its fp16 mel buffer (mel_pad / mel_convert) and forms the raw conditioning sums, no bias (k16_cond_seed).
+        arithmetic="bf16x3" (all-fp32 modules): the split path's fp32 mel buffer, the raw sums of the split products
+        (ks_cond_seed); block_tiles at most seed_layout's max_block_tiles."""
+        split = self._check_arithmetic(arithmetic)
         dev = melp.device
         f0, nf = flows if flows is not None else (0, 0)
-        h, dt, (_, seed_fn, _) = self._resolve(dev, handle)
-        self._check_mel_buffer("cond_seed", melp, dt)
+        if split:
+            self._check_split_mel_buffer("cond_seed", melp)
+            h, seed_fn = self._resolve_split("cond_seed", dev, handle), _lib.load().facppg_wg_split_cond_seed
+        else:
+            h, dt, (_, seed_fn, _) = self._resolve(dev, handle)
+            self._check_mel_buffer("cond_seed", melp, dt)
         with torch.cuda.device(dev):
             _lib.check(seed_fn(h, _lib.ptr(melp), int(T), int(frame0),
                        int(nframes), int(block_tiles), int(layers_per_workgroup), int(f0), int(nf), _lib.ptr(seeds),
@@ -1377,17 +1442,35 @@ class WaveGlow(torch.nn.Module):
         if melp.dtype != dt:
             raise _lib.FacppgError("%s: the module is %s, its mel buffer is %s" % (who, "fp16" if dt == torch.float16 else "fp32", melp.dtype))
 
-    def infer_seeded(self, melp, T, seeds, seeded_frames, sigma=1.0, z=None, seed=None, handle=None, T_layout=None, flow_events=None):
+    def infer_seeded(self, melp, T, seeds, seeded_frames, sigma=1.0, z=None, seed=None, handle=None, T_layout=None, flow_events=None,
+                     arithmetic=None):
         """WaveGlow.infer of ONE utterance (glow.py:252-293) whose layers start from ``seeds``: audio [1, T*hop].  Same samples
         as infer() on the same mel frames, bit for bit.  T_layout >= T: the frame count ``melp`` and ``seeds`` were laid out for.
         flow_events: {flow: torch.cuda.Event} the launches of that flow wait for (its seeds are still being formed elsewhere).
-        A .half() module (fp16 ``melp``): half audio, the samples of infer(mel.half(), cond_first=True); seeded_frames may be 0."""
+        A .half() module (fp16 ``melp``): half audio, the samples of infer(mel.half(), cond_first=True); seeded_frames may be 0.
+        arithmetic="bf16x3" (all-fp32 modules, the split path's fp32 ``melp``): fp32 audio on split-bf16 operands in the
+        conditioning-first K order -- the same bits whichever tiles were seeded (seeded_frames may be 0, ``seeds`` then None), in
+        the last bits not those of infer(arithmetic="bf16x3"), which sums the taps first."""
+        split = self._check_arithmetic(arithmetic)
         T_layout = T if T_layout is None else int(T_layout)
         dev = melp.device
-        h, dt, (_, _, infer_fn) = self._resolve(dev, handle)
-        self._check_mel_buffer("infer_seeded", melp, dt)
+        if split:
+            self._check_split_mel_buffer("infer_seeded", melp)
+            h, dt, infer_fn = self._resolve_split("infer_seeded", dev, handle), torch.float32, _lib.load().facppg_wg_split_infer_seeded
+            if seeds is None and int(seeded_frames) == 0:
+                seeds = melp                       # (never read: no tile starts from a seed)
+        else:
+            h, dt, (_, _, infer_fn) = self._resolve(dev, handle)
+            self._check_mel_buffer("infer_seeded", melp, dt)
         zt, _, seed, _ = self._infer_args(1, T, dt, z, None, seed, None, dev)
-        ws = self._infer_workspace(1, T_layout, dev, 0, h)
+        if split:
+            nbytes = _lib.load().facppg_wg_split_workspace_bytes(h, 1, T_layout)
+            wss = self.__dict__.setdefault("_facppg_ws", {})
+            ws = wss.get("bf16x3")
+            if ws is None or ws.numel() < nbytes or ws.device != dev:
+                ws = wss["bf16x3"] = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+        else:
+            ws = self._infer_workspace(1, T_layout, dev, 0, h)
         audio = torch.empty(1, T * self.upsample.stride[0], dtype=dt, device=dev)
         evs = None
         if flow_events:

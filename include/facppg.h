@@ -426,6 +426,36 @@ int facppg_wg_split_infer(facppg_wg_split* h, const float* mel_dev, const int32_
                           float* audio_dev, void* workspace_dev, size_t workspace_bytes, void* stream);
 int facppg_wg_split_last_launch_shape(const facppg_wg_split* h, int* tile_frames, int* waves, int* n_tiles);
 
+/* ---- Seeded inference of ONE utterance on a split handle: WN.forward's cond_layers (glow.py:154-175) on the upsampled mel
+ * (glow.py:253-259) formed ahead of the layers, as facppg_wg_*_f16 above do for an fp16 handle, with fp32 melp, fp32 injected z
+ * and fp32 audio.  facppg_wg_split_infer sums the taps first and the conditioning chunks last; a seed can only stand for chunks
+ * that are summed first from zero accumulators, and fp32 accumulation is not associative.  So the seeded path has a K order of
+ * its own -- conditioning first --, and its samples differ from facppg_wg_split_infer's in the last bits (same accuracy: the
+ * three terms per K step and accumulator keep their order).  facppg_wg_split_infer itself is unchanged.
+ * facppg_wg_split_seed_layout (glow.py:253-259): as facppg_wg_seed_layout_f16 -- the mel buffer is melp [Tqp][n_mel] in fp32
+ *   (frame q at row *margin + q, margins and missing frames zero), the seeds are raw fp32 gate accumulators (no bias) in the layer
+ *   kernel's register order, 64 KiB per (flow, layer, phase, 32-frame tile) -- and *max_block_tiles, the largest block_tiles
+ *   facppg_wg_split_cond_seed takes for this handle (the split window of a block must fit a CU's LDS: 3 at hop 256, 1 at hop 160).
+ * facppg_wg_split_mel_pad (glow.py:253-259, the frames the upsampler reads): frames [frame0, frame0 + nframes) of the fp32
+ *   mel_dev [n_mel][ld] -> melp_dev; nothing else of melp_dev is written (the caller zeroes it once).  *skip_dev != 0 (may be
+ *   NULL): does nothing.
+ * facppg_wg_split_cond_seed (glow.py:154-175, cond_layers): the arguments of facppg_wg_cond_seed_f16; a block_tiles above
+ *   *max_block_tiles is refused, the message names the maximum.
+ * facppg_wg_split_infer_seeded (glow.py:252-293): the arguments of facppg_wg_infer_seeded_f16; workspace
+ *   facppg_wg_split_workspace_bytes(h, 1, T_layout).  The launches use 32-frame tiles: tiles wholly inside [0, seeded_frames) (a
+ *   multiple of 32, at most T rounded up to 32) start from their seeds, the others run unseeded, conditioning-first, in the same
+ *   launches -- a column gets the same bits either way.  seeded_frames = 0 is the unstreamed call with these bits.  Its launch
+ *   shape is what facppg_wg_split_last_launch_shape then reports. */
+int facppg_wg_split_seed_layout(const facppg_wg_split* h, int T, int* Tqp, int* margin, size_t* seed_bytes, int* max_block_tiles);
+int facppg_wg_split_mel_pad(const facppg_wg_split* h, const float* mel_dev, int T, int ld, int frame0, int nframes,
+                            float* melp_dev, const int32_t* skip_dev, void* stream);
+int facppg_wg_split_cond_seed(facppg_wg_split* h, const float* melp_dev, int T, int frame0, int nframes, int block_tiles,
+                              int layers_per_workgroup, int flow0, int nflows, float* seeds_dev, size_t seed_bytes,
+                              const int32_t* skip_dev, int max_workgroups, int32_t* counter_dev, void* stream);
+int facppg_wg_split_infer_seeded(facppg_wg_split* h, const float* melp_dev, int T_layout, int T, const float* seeds_dev,
+                                 int seeded_frames, const float* z_dev, uint64_t seed, float sigma, float* audio_dev,
+                                 void* workspace_dev, size_t workspace_bytes, void* const* flow_events, void* stream);
+
 /* ------------------------------------------------------------------------------------
  * STFT / mel analysis / denoiser (src/common/stft.py, src/common/layers.py,
  * src/waveglow/denoiser.py)
