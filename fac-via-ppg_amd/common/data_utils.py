@@ -7,12 +7,23 @@ precomputed PPG ([Tin, n_symbols] float array, 10 ms frame shift, rows = posteri
 given path itself is a ``.npy`` file or a sibling ``<wav>.ppg.npy`` exists next to the wav.
 
 ``ppg_acoustics_collate`` is the reference's mini-batch collation (data_utils.py:281-334), what ``Tacotron2.parse_batch``
-takes.  ``PPGMelLoader`` (data_utils.py:62-278) is out of scope: it extracts its PPGs with Kaldi.
+takes.
+
+``get_ppg_batch`` is ``get_ppg`` for a list of paths: the precomputed-file rule per path, and ONE pass of the batch front
+end (ppg.compute_ppg_batch: the utterances laid end to end through the MFCC, CMN / splice / LDA and TDNN kernels) for the
+paths that have no precomputed file.  ``PPGMelLoader`` (data_utils.py:163-278) is the reference's (PPG, mel) data set on top
+of it, what ``script.train_ppg2mel.finetune`` trains from; F0 features (``is_append_f0``) are not built.
 """
 import os
+import pickle
+import random
 
 import numpy as np
 import torch
+import torch.utils.data
+from scipy.io import wavfile
+
+from common.utils import load_filepaths
 
 
 def ppg_candidates(wav_path):
@@ -38,6 +49,147 @@ def get_ppg(wav_path, deps=None, is_fmllr=False):
     raise NotImplementedError(
         "PPG extraction from audio needs the Kaldi nnet3 acoustic model (data/am/final.raw), which the reference does not ship; "
         "provide a precomputed PPG as %s (the model's input features are available: ppg.compute_feat_for_nnet)" % " or ".join(candidates))
+
+
+def _precomputed(wav_path):
+    for c in ppg_candidates(wav_path):
+        if os.path.isfile(c):
+            return True
+    return False
+
+
+def get_ppg_batch(wav_paths, deps=None, is_full_ppg=True):
+    """``get_ppg`` for a list of paths -> list of [Tin, n_symbols] float32 arrays, in the order given.  A path with a
+    precomputed PPG file is read as ``get_ppg`` reads it; the others go through the batch front end together
+    (ppg.compute_ppg_batch, one pass over all of them); a path with neither a file nor a model raises ``get_ppg``'s error.
+    ``is_full_ppg=False`` returns monophone PPGs: computed ones come reduced out of the acoustic model's output kernel,
+    precomputed senone PPGs go through ppg.reduce_ppg_dim."""
+    wav_paths = list(wav_paths)
+    out = [None] * len(wav_paths)
+    todo = []
+    for i, path in enumerate(wav_paths):
+        if _precomputed(path) or deps is None or getattr(deps, "nnet", None) is None or not os.path.isfile(path):
+            out[i] = get_ppg(path, deps)                 # the file, or get_ppg's error
+        else:
+            todo.append(i)
+    trans = getattr(deps, "monophone_trans", None)
+    if not is_full_ppg:
+        if trans is None:
+            raise ValueError("get_ppg_batch: monophone PPGs need deps.monophone_trans (data/feats/reduce_dim.mat)")
+        for i, p in enumerate(out):
+            if p is not None and p.shape[1] == trans.shape[1]:
+                from ppg import reduce_ppg_dim
+                out[i] = reduce_ppg_dim(p, trans).cpu().numpy()
+    if todo:
+        from common import feat
+        from ppg import compute_ppg_batch
+        ppgs = compute_ppg_batch([feat.read_wav_kaldi(wav_paths[i]) for i in todo], deps, is_full_ppg=is_full_ppg, shift=10)
+        for i, p in zip(todo, ppgs):
+            out[i] = p.cpu().numpy()
+    return out
+
+
+class PPGMelLoader(torch.utils.data.Dataset):
+    """Loads [ppg, mel] pairs: the reference's data_utils.py:163-278.
+
+    data_utterance_paths   a text file with one wav path per line (``load_filepaths``); the list is shuffled under
+                           ``random.seed(hparams.seed)`` as the reference does, and the stored order is the shuffled one
+    hparams                max_wav_value, sampling_rate, is_full_ppg, is_append_f0, is_cache_feats, load_feats_from_disk,
+                           feats_cache_path, ppg_subsampling_factor, seed and the STFT's parameters
+    ppg_deps               None builds ``DependenciesPPG()`` as the reference does
+    batch_utterances       utterances extracted per pass of the batch front end (``get_ppg_batch``) and of the ragged
+                           ``TacotronSTFT.mel_spectrogram``; within a pass they are sorted by length (the padding of the
+                           mel batch stays small); the features do not depend on it beyond fp32 round-off
+
+    The PPG side is the senone PPG (``is_full_ppg``) or the monophone PPG, reduced inside the acoustic model's output
+    kernel; the acoustic side is the log-mel of ``audio / max_wav_value``, [T, n_mel].  ``is_append_f0`` raises: the
+    reference reads ``utt.f0``, and nothing on this path computes an F0 track."""
+
+    def __init__(self, data_utterance_paths, hparams, ppg_deps=None, batch_utterances=32):
+        self.data_utterance_paths = load_filepaths(data_utterance_paths)
+        self.max_wav_value = hparams.max_wav_value
+        self.sampling_rate = hparams.sampling_rate
+        self.is_full_ppg = hparams.is_full_ppg
+        self.is_append_f0 = hparams.is_append_f0
+        self.is_cache_feats = hparams.is_cache_feats
+        self.load_feats_from_disk = hparams.load_feats_from_disk
+        self.feats_cache_path = hparams.feats_cache_path
+        self.ppg_subsampling_factor = hparams.ppg_subsampling_factor
+        self.batch_utterances = int(batch_utterances)
+        if self.is_cache_feats and self.load_feats_from_disk:
+            raise ValueError('If you are loading feats from the disk, do not rewrite them back!')
+        if self.is_append_f0:
+            raise NotImplementedError("PPGMelLoader: is_append_f0 is not built -- the reference appends utt.f0 "
+                                      "(data_utils.py:142-160, 248-256), and no F0 extraction exists on this path")
+        if self.batch_utterances < 1:
+            raise ValueError("PPGMelLoader: batch_utterances must be at least 1")
+        if ppg_deps is None:
+            from ppg import DependenciesPPG
+            ppg_deps = DependenciesPPG()
+        self.ppg_deps = ppg_deps
+
+        from common import layers
+        self.stft = layers.TacotronSTFT(hparams.filter_length, hparams.hop_length, hparams.win_length, hparams.n_acoustic_feat_dims,
+                                        hparams.sampling_rate, hparams.mel_fmin, hparams.mel_fmax)
+        random.seed(hparams.seed)
+        random.shuffle(self.data_utterance_paths)
+
+        self.ppg_sequences = []
+        self.acoustic_sequences = []
+        if self.load_feats_from_disk:
+            print('Loading data from %s.' % self.feats_cache_path)
+            with open(self.feats_cache_path, 'rb') as f:
+                data = pickle.load(f)
+            self.ppg_sequences = data[0]
+            self.acoustic_sequences = data[1]
+        else:
+            for at in range(0, len(self.data_utterance_paths), self.batch_utterances):
+                ppgs, mels = self.extract_batch_feats(self.data_utterance_paths[at:at + self.batch_utterances], self.is_full_ppg)
+                self.ppg_sequences += [p.astype(np.float32) for p in ppgs]
+                self.acoustic_sequences += mels
+        if self.is_cache_feats:
+            print('Caching data to %s.' % self.feats_cache_path)
+            with open(self.feats_cache_path, 'wb') as f:
+                pickle.dump([self.ppg_sequences, self.acoustic_sequences], f)
+
+    def extract_batch_feats(self, paths, is_full_ppg=False):
+        """extract_utterance_feats (data_utils.py:215-258) for a chunk of utterances: (PPGs, mels) in the order of ``paths``;
+        PPG [Tin, n_symbols] numpy, mel [N // hop + 1, n_mel] CPU tensor."""
+        audio = []
+        for path in paths:
+            fs, wav = wavfile.read(path)
+            if fs != self.stft.sampling_rate:
+                raise ValueError("{} SR doesn't match target {} SR".format(fs, self.stft.sampling_rate))
+            audio.append((wav[:, 0] if wav.ndim == 2 else wav).astype(np.float32))
+        order = sorted(range(len(paths)), key=lambda i: len(audio[i]))
+        got = get_ppg_batch([paths[i] for i in order], self.ppg_deps, is_full_ppg=is_full_ppg)
+        hop = self.stft.stft_fn.hop_length
+        padded = np.zeros((len(order), len(audio[order[-1]])), np.float32)
+        for row, i in enumerate(order):
+            padded[row, :len(audio[i])] = audio[i] / self.max_wav_value
+        lengths = [len(audio[i]) for i in order]
+        mel = self.stft.mel_spectrogram(torch.from_numpy(padded).cuda(), lengths)          # [B, n_mel, max N // hop + 1]
+        ppgs, mels = [None] * len(paths), [None] * len(paths)
+        for row, i in enumerate(order):
+            ppgs[i] = got[row]
+            mels[i] = mel[row, :, :lengths[row] // hop + 1].transpose(0, 1).contiguous().cpu()
+        return ppgs, mels
+
+    def extract_utterance_feats(self, data_utterance_path, is_full_ppg=False):
+        """data_utils.py:215-258: [ppg, mel] of one utterance."""
+        ppgs, mels = self.extract_batch_feats([data_utterance_path], is_full_ppg)
+        return [ppgs[0], mels[0]]
+
+    def __getitem__(self, index):
+        """data_utils.py:260-275: (T*D1 PPG sequence, T*D2 mels) as float32 tensors."""
+        if self.ppg_subsampling_factor == 1:
+            curr_ppg = self.ppg_sequences[index]
+        else:
+            curr_ppg = self.ppg_sequences[index][0::self.ppg_subsampling_factor, :]
+        return torch.from_numpy(curr_ppg), self.acoustic_sequences[index]
+
+    def __len__(self):
+        return len(self.ppg_sequences)
 
 
 def ppg_acoustics_collate(batch):

@@ -5,6 +5,8 @@ libfacppg_hip instead of pykaldi.  Kaldi objects become plain tensors: a "Matrix
   MfccOptions, compute_mfcc_feats            Kaldi MFCC with the reference's options (facppg_mfcc_*)
   apply_cepstral_mean_norm, splice_frames, apply_feat_transform          (facppg_cmn_splice_transform)
   read_sparse_mat                            Kaldi sparse matrix -> dense float32 GPU tensor
+  compute_mfcc_feats_batch, cmn_splice_transform_batch   the same chain for a list of utterances in one pass
+                                             (facppg_mfcc_compute_batch, facppg_cmn_splice_transform_batch)
 
 Dither is not applied (Kaldi's default adds random +-1 LSB noise; this path is deterministic); inputs above 16 kHz are
 downsampled with Kaldi's LinearResample when allow_downsample is set (facppg_resample), as the reference does."""
@@ -158,6 +160,28 @@ class Mfcc(object):
         except Exception:
             pass
 
+    def _at_model_rate(self, wave, samp_freq, out=None):
+        """wave [N] at samp_freq -> the samples at the features' rate, downsampled through facppg_resample when the input
+        rate is higher (feature-common-inl.h ComputeFeatures); written into ``out`` when given (a slice of a batch's buffer)."""
+        L = _lib.load()
+        dev = wave.device
+        target = self.opts.frame_opts.samp_freq
+        if float(samp_freq) == float(target):
+            return wave if out is None else out.copy_(wave)
+        # a higher input rate is downsampled when allow_downsample, anything else is an error
+        if float(samp_freq) < float(target) or not self.opts.frame_opts.allow_downsample:
+            raise _lib.FacppgError("Mfcc: waveform sampled at %g Hz, features need %g Hz (set frame_opts.allow_downsample for higher rates)"
+                                   % (samp_freq, target))
+        n_out = L.facppg_resample_num_samples(wave.numel(), int(samp_freq), int(target))
+        res = torch.empty(n_out, device=dev) if out is None else out
+        with torch.cuda.device(dev):
+            _lib.check(L.facppg_resample(_lib.ptr(wave), wave.numel(), int(samp_freq), int(target), _lib.ptr(res), _lib.current_stream(dev)))
+        return res
+
+    def num_samples_at_model_rate(self, n, samp_freq):
+        target = self.opts.frame_opts.samp_freq
+        return n if float(samp_freq) == float(target) else _lib.load().facppg_resample_num_samples(n, int(samp_freq), int(target))
+
     def compute_features(self, wave, samp_freq, vtln_warp=1.0):
         """wave: [N] samples (GPU tensor, int16 range) -> [T, num_ceps] (GPU)."""
         _lib.require_cuda(wave, "Mfcc.compute_features: wave")
@@ -165,18 +189,7 @@ class Mfcc(object):
             raise _lib.FacppgError("VTLN warping is not built (the reference always passes 1.0, feat.py:95)")
         L = _lib.load()
         dev = wave.device
-        wave = wave.float().contiguous().reshape(-1)
-        target = self.opts.frame_opts.samp_freq
-        if float(samp_freq) != float(target):
-            # feature-common-inl.h ComputeFeatures: a higher input rate is downsampled when allow_downsample, anything else is an error
-            if float(samp_freq) < float(target) or not self.opts.frame_opts.allow_downsample:
-                raise _lib.FacppgError("Mfcc: waveform sampled at %g Hz, features need %g Hz (set frame_opts.allow_downsample for higher rates)"
-                                       % (samp_freq, target))
-            n_out = L.facppg_resample_num_samples(wave.numel(), int(samp_freq), int(target))
-            res = torch.empty(n_out, device=dev)
-            with torch.cuda.device(dev):
-                _lib.check(L.facppg_resample(_lib.ptr(wave), wave.numel(), int(samp_freq), int(target), _lib.ptr(res), _lib.current_stream(dev)))
-            wave = res
+        wave = self._at_model_rate(wave.float().contiguous().reshape(-1), samp_freq)
         h = self._get(dev)
         n = wave.numel()
         T = L.facppg_mfcc_num_frames(h, n)
@@ -186,6 +199,42 @@ class Mfcc(object):
             _lib.check(L.facppg_mfcc_compute(h, _lib.ptr(wave), n, 1 if self.opts.use_energy else 0, _lib.ptr(out), _lib.ptr(ws), ws.numel(),
                                              _lib.current_stream(dev)))
         return out
+
+
+    def compute_features_batch(self, waves, samp_freqs):
+        """waves: B tensors [N_b] (GPU, int16 range) sampled at samp_freqs[b] -> (mfcc [sum T, num_ceps], frame counts [B]).
+        Each utterance is downsampled on its own where needed, straight into its place in one buffer; framing, spectrum and
+        cepstra then run once over all frames (facppg_mfcc_compute_batch).  Every row equals compute_features' bit for bit."""
+        if not len(waves):
+            raise ValueError("compute_features_batch: no utterance")
+        for w in waves:
+            _lib.require_cuda(w, "Mfcc.compute_features_batch: wave")
+        L = _lib.load()
+        dev = waves[0].device
+        h = self._get(dev)
+        waves = [w.float().contiguous().reshape(-1) for w in waves]
+        counts = [self.num_samples_at_model_rate(w.numel(), fs) for w, fs in zip(waves, samp_freqs)]
+        frames = [L.facppg_mfcc_num_frames(h, n) for n in counts]
+        for w, fs, T in zip(waves, samp_freqs, frames):
+            if T <= 0:
+                self.compute_features(w, fs)          # too short for one frame: the single call's refusal, word for word
+        s_off, f_off = _lib.host_offsets(counts), _lib.host_offsets(frames)
+        flat = torch.empty(s_off[-1], device=dev)
+        for b, (w, fs) in enumerate(zip(waves, samp_freqs)):
+            self._at_model_rate(w, fs, out=flat[s_off[b]:s_off[b + 1]])
+        s_dev, f_dev = _lib.upload(list(s_off), torch.int32, dev), _lib.upload(list(f_off), torch.int32, dev)
+        out = torch.empty(f_off[-1], self.opts.num_ceps, device=dev)
+        ws = torch.empty(L.facppg_mfcc_batch_workspace_bytes(h, f_off[-1]), dtype=torch.uint8, device=dev)
+        with torch.cuda.device(dev):
+            _lib.check(L.facppg_mfcc_compute_batch(h, _lib.ptr(flat), _lib.ptr(s_dev), s_off, _lib.ptr(f_dev), f_off, len(waves),
+                                                   1 if self.opts.use_energy else 0, _lib.ptr(out), _lib.ptr(ws), ws.numel(),
+                                                   _lib.current_stream(dev)))
+        return out, frames
+
+
+def compute_mfcc_feats_batch(wavs, mfcc_opts):
+    """compute_mfcc_feats for a list of WaveData: (mfcc [sum T, D] of the first channels laid end to end, frame counts)."""
+    return Mfcc(mfcc_opts).compute_features_batch([w.data()[0] for w in wavs], [w.samp_freq for w in wavs])
 
 
 def compute_mfcc_feats(wav, mfcc_opts):
@@ -230,6 +279,33 @@ def apply_feat_transform(feats, transform):
 def cmn_splice_transform(feats, left_context, right_context, transform):
     """The three steps of compute_ppg.py:124-132 in one pass."""
     return _cst(feats, True, int(left_context), int(right_context), torch.as_tensor(transform))
+
+
+def cmn_splice_transform_batch(feats, frames, left_context, right_context, transform, do_cmn=True):
+    """cmn_splice_transform per utterance in one pass: feats [sum T, D] (utterances laid end to end), frames = their frame
+    counts -> [sum T, M] (or the spliced width when transform is None).  Mean, splice and clamp stay inside each utterance."""
+    _lib.require_cuda(feats, "feature matrix")
+    L = _lib.load()
+    dev = feats.device
+    feats = feats.float().contiguous()
+    left, right = int(left_context), int(right_context)
+    f_off = _lib.host_offsets(frames)
+    T, D = feats.shape
+    if f_off[-1] != T:
+        raise ValueError("cmn_splice_transform_batch: the frame counts add up to %d, the matrix has %d rows" % (f_off[-1], T))
+    W = (left + right + 1) * D
+    tr = None if transform is None else torch.as_tensor(transform).to(dev).float().contiguous()
+    if tr is not None and tr.shape[1] not in (W, W + 1):
+        logging.error("Transform matrix has bad dimension %dx%d versus feat dim %d" % (tr.shape[0], tr.shape[1], W))   # feat.py:154-155
+        raise _lib.FacppgError("Transform matrix has bad dimension %dx%d versus feat dim %d" % (tr.shape[0], tr.shape[1], W))
+    out = torch.empty(T, W if tr is None else tr.shape[0], device=dev)
+    mean = torch.empty(len(frames), D, device=dev)
+    f_dev = _lib.upload(list(f_off), torch.int32, dev)
+    with torch.cuda.device(dev):
+        _lib.check(L.facppg_cmn_splice_transform_batch(_lib.ptr(feats), _lib.ptr(f_dev), f_off, len(frames), D, 1 if do_cmn else 0, left, right,
+                                                       _lib.ptr(tr), 0 if tr is None else tr.shape[0], 0 if tr is None else tr.shape[1],
+                                                       _lib.ptr(out), _lib.ptr(mean), _lib.current_stream(dev)))
+    return out
 
 
 def read_sparse_mat(sparse_mat_dir):

@@ -35,6 +35,26 @@ constexpr int kWave = 64;  // CDNA wavefront
 
 __host__ __device__ inline int round_up(int x, int m) { return (x + m - 1) / m * m; }
 
+// Frame / sample offsets of a batch of utterances laid end to end (host copy): B + 1 values, off[0] = 0, strictly increasing
+// (every utterance holds at least one element).
+inline int check_offsets(const int32_t* off, int B, const char* what) {
+  FACPPG_REQUIRE(off && B > 0, FACPPG_EINVAL, "%s: NULL offsets or no utterance", what);
+  FACPPG_REQUIRE(off[0] == 0, FACPPG_EINVAL, "%s: offsets must start at 0 (got %d)", what, off[0]);
+  for (int b = 0; b < B; ++b)
+    FACPPG_REQUIRE(off[b + 1] > off[b], FACPPG_EINVAL, "%s: offsets must increase (utterance %d: %d -> %d)", what, b, off[b], off[b + 1]);
+  return FACPPG_OK;
+}
+
+// largest b in [0, B) with off[b] <= g  (off strictly increasing, off[0] <= g)
+__device__ __forceinline__ int seg_of(const int* __restrict__ off, int B, int g) {
+  int lo = 0, hi = B;
+  while (hi - lo > 1) {
+    const int mid = (lo + hi) >> 1;
+    if (off[mid] <= g) lo = mid; else hi = mid;
+  }
+  return lo;
+}
+
 // One exact-fp32 MFMA: D[32x32] += A[32x2] * B[2x32]; lane l holds A[l&31][l>>5], B[l>>5][l&31].
 __device__ __forceinline__ f32x16 mfma32x32x2(float a, float b, f32x16 c) {
   return __builtin_amdgcn_mfma_f32_32x32x2f32(a, b, c, 0, 0, 0);

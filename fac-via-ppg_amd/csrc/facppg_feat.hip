@@ -25,23 +25,38 @@ namespace {
 
 // frames[k][t] = wav[reflect(first(t) + k)], first(t) = t*shift + shift/2 - len/2  (feature-window.cc: snip_edges = false);
 // energy[t] = log(max(sum_k (x_k - mean)^2, floor))  (raw_energy, after DC removal) for use_energy
-__global__ void k_mfcc_frames(const float* __restrict__ wav, int N, int T, int len, int shift, float* __restrict__ frames,
-                              float* __restrict__ energy, int Tld) {
-  const int t = blockIdx.x * blockDim.x + threadIdx.x;
-  if (t >= T) return;
+__device__ __forceinline__ void mfcc_frame(const float* __restrict__ wav, int N, int t, int len, int shift, float* __restrict__ frames,
+                                           float* __restrict__ energy, int Tld, int col) {
   const int first = t * shift + shift / 2 - len / 2;
   float s = 0.f, s2 = 0.f;
   for (int k = 0; k < len; ++k) {
     int i = first + k;
     while (i < 0 || i >= N) i = i < 0 ? -i - 1 : 2 * N - 1 - i;
     const float v = wav[i];
-    frames[(size_t)k * Tld + t] = v;
+    frames[(size_t)k * Tld + col] = v;
     s += v; s2 = fmaf(v, v, s2);
   }
   if (energy) {
     const float e = s2 - s * s / (float)len;
-    energy[t] = logf(fmaxf(e, 1.1920929e-7f));   // max(energy, FLT_EPSILON), feature-window.cc ProcessWindow
+    energy[col] = logf(fmaxf(e, 1.1920929e-7f));   // max(energy, FLT_EPSILON), feature-window.cc ProcessWindow
   }
+}
+
+__global__ void k_mfcc_frames(const float* __restrict__ wav, int N, int T, int len, int shift, float* __restrict__ frames,
+                              float* __restrict__ energy, int Tld) {
+  const int t = blockIdx.x * blockDim.x + threadIdx.x;
+  if (t >= T) return;
+  mfcc_frame(wav, N, t, len, shift, frames, energy, Tld, t);
+}
+
+// batch form: frame g of the batch is frame g - foff[b] of utterance b, cut from that utterance's own samples
+// wav[soff[b] .. soff[b+1]) with the reflection at ITS ends; column g of the one frame matrix
+__global__ void k_mfcc_frames_batch(const float* __restrict__ wav, const int* __restrict__ soff, const int* __restrict__ foff, int B, int len,
+                                    int shift, float* __restrict__ frames, float* __restrict__ energy, int Tld) {
+  const int g = blockIdx.x * blockDim.x + threadIdx.x;
+  if (g >= foff[B]) return;
+  const int b = seg_of(foff, B, g);
+  mfcc_frame(wav + soff[b], soff[b + 1] - soff[b], g - foff[b], len, shift, frames, energy, Tld, g);
 }
 
 // spec [2*nbins][Tld] (real rows, then imaginary rows) -> mfcc [T][n_ceps]; one wavefront per frame
@@ -75,8 +90,7 @@ __global__ __launch_bounds__(256) void k_mfcc_tail(const float* __restrict__ spe
 }
 
 // column means of feats [T][D] -> mean[D] (fixed order: one workgroup, strided partial sums then a tree)
-__global__ __launch_bounds__(256) void k_col_mean(const float* __restrict__ x, int T, int D, float* __restrict__ mean) {
-  __shared__ float red[256];
+__device__ __forceinline__ void col_mean(const float* __restrict__ x, int T, int D, float* __restrict__ mean, float* red) {
   for (int d = 0; d < D; ++d) {
     float v = 0.f;
     for (int t = threadIdx.x; t < T; t += 256) v += x[(size_t)t * D + d];
@@ -91,11 +105,24 @@ __global__ __launch_bounds__(256) void k_col_mean(const float* __restrict__ x, i
   }
 }
 
+__global__ __launch_bounds__(256) void k_col_mean(const float* __restrict__ x, int T, int D, float* __restrict__ mean) {
+  __shared__ float red[256];
+  col_mean(x, T, D, mean, red);
+}
+
+// batch form: workgroup b takes the mean of utterance b's own frames foff[b] .. foff[b+1]-1 -> mean[b][D]
+__global__ __launch_bounds__(256) void k_col_mean_batch(const float* __restrict__ x, const int* __restrict__ foff, int D, float* __restrict__ mean) {
+  __shared__ float red[256];
+  const int b = blockIdx.x;
+  col_mean(x + (size_t)foff[b] * D, foff[b + 1] - foff[b], D, mean + (size_t)b * D, red);
+}
+
 // out[t][m] = off[m] + sum_{j=-left..right} sum_d A[m][(j+left)*D + d] * (x[clamp(t+j)][d] - mean[d])   (transform given)
 // out[t][(j+left)*D + d] = x[clamp(t+j)][d] - mean[d]                                                    (transform null: splice only)
-__global__ void k_cmn_splice_transform(const float* __restrict__ x, int T, int D, const float* __restrict__ mean, int left, int right,
-                                       const float* __restrict__ A, int M, int cols, float* __restrict__ out) {
-  const int t = blockIdx.x, W = (left + right + 1) * D;
+__device__ __forceinline__ void cmn_splice_transform_frame(const float* __restrict__ x, int T, int t, int D, const float* __restrict__ mean,
+                                                           int left, int right, const float* __restrict__ A, int M, int cols,
+                                                           float* __restrict__ out) {
+  const int W = (left + right + 1) * D;
   if (!A) {
     for (int i = threadIdx.x; i < W; i += blockDim.x) {
       const int j = i / D - left, d = i % D, tt = min(max(t + j, 0), T - 1);
@@ -111,6 +138,21 @@ __global__ void k_cmn_splice_transform(const float* __restrict__ x, int T, int D
     }
     out[(size_t)t * M + m] = v;
   }
+}
+
+__global__ void k_cmn_splice_transform(const float* __restrict__ x, int T, int D, const float* __restrict__ mean, int left, int right,
+                                       const float* __restrict__ A, int M, int cols, float* __restrict__ out) {
+  cmn_splice_transform_frame(x, T, blockIdx.x, D, mean, left, right, A, M, cols, out);
+}
+
+// batch form: workgroup g is frame g - foff[b] of utterance b; the splice clamps to that utterance's own first / last frame
+// and subtracts its own mean[b][D]
+__global__ void k_cmn_splice_transform_batch(const float* __restrict__ x, const int* __restrict__ foff, int B, int D,
+                                             const float* __restrict__ mean, int left, int right, const float* __restrict__ A, int M,
+                                             int cols, float* __restrict__ out) {
+  const int g = blockIdx.x, b = seg_of(foff, B, g), W = A ? M : (left + right + 1) * D;
+  cmn_splice_transform_frame(x + (size_t)foff[b] * D, foff[b + 1] - foff[b], g - foff[b], D, mean ? mean + (size_t)b * D : nullptr, left, right, A,
+                             M, cols, out + (size_t)foff[b] * W);
 }
 
 // Kaldi LinearResample (feat/resample.cc) as used by DownsampleWaveForm (allow_downsample): windowed-sinc low-pass at
@@ -225,6 +267,46 @@ extern "C" int facppg_mfcc_compute(facppg_mfcc* h, const float* wav_dev, int n_s
   return FACPPG_OK;
 }
 
+extern "C" size_t facppg_mfcc_batch_workspace_bytes(const facppg_mfcc* h, int total_frames) {
+  if (!h || total_frames <= 0) return 0;
+  const size_t Tld = round_up(total_frames, 64);
+  return ((size_t)h->frame_length + 2 * h->nbins + 1) * Tld * 4;
+}
+
+extern "C" int facppg_mfcc_compute_batch(facppg_mfcc* h, const float* wav_dev, const int32_t* sample_offsets_dev,
+                                         const int32_t* sample_offsets_host, const int32_t* frame_offsets_dev,
+                                         const int32_t* frame_offsets_host, int B, int use_energy, float* mfcc_dev, void* ws_dev,
+                                         size_t ws_bytes, void* stream_) {
+  if (int rc = check_offsets(sample_offsets_host, B, "facppg_mfcc_compute_batch (samples)")) return rc;
+  FACPPG_REQUIRE(h && wav_dev && sample_offsets_dev && frame_offsets_dev && frame_offsets_host && mfcc_dev && ws_dev, FACPPG_EINVAL,
+                 "NULL argument");
+  FACPPG_REQUIRE(frame_offsets_host[0] == 0, FACPPG_EINVAL, "facppg_mfcc_compute_batch (frames): offsets must start at 0 (got %d)",
+                 frame_offsets_host[0]);
+  for (int b = 0; b < B; ++b) {
+    const int n = sample_offsets_host[b + 1] - sample_offsets_host[b], T = facppg_mfcc_num_frames(h, n);
+    FACPPG_REQUIRE(T > 0, FACPPG_EINVAL, "no frames in %d samples", n);      // (facppg_mfcc_compute's refusal)
+    FACPPG_REQUIRE(frame_offsets_host[b + 1] - frame_offsets_host[b] == T, FACPPG_EINVAL,
+                   "utterance %d: %d samples are %d frames, the frame offsets say %d", b, n, T, frame_offsets_host[b + 1] - frame_offsets_host[b]);
+  }
+  const int T = frame_offsets_host[B];
+  FACPPG_REQUIRE(ws_bytes >= facppg_mfcc_batch_workspace_bytes(h, T), FACPPG_EWORKSPACE, "workspace has %zu bytes, need %zu", ws_bytes,
+                 facppg_mfcc_batch_workspace_bytes(h, T));
+  hipStream_t s = (hipStream_t)stream_;
+  const int Tld = round_up(T, 64);
+  float* frames = (float*)ws_dev;
+  float* spec = frames + (size_t)h->frame_length * Tld;
+  float* energy = spec + (size_t)2 * h->nbins * Tld;
+  k_mfcc_frames_batch<<<(T + 255) / 256, 256, 0, s>>>(wav_dev, sample_offsets_dev, frame_offsets_dev, B, h->frame_length, h->frame_shift, frames,
+                                                      use_energy ? energy : nullptr, Tld);
+  GemmArgs g;
+  g.A = h->basis; g.M = 2 * h->nbins; g.Cin = h->frame_length; g.X = frames; g.ldx = Tld; g.N = T; g.C = spec; g.ldc = Tld; g.B = 1;
+  if (int rc = gemm_launch(g, s)) return rc;
+  k_mfcc_tail<<<(T + 3) / 4, 256, (size_t)4 * (h->nbins + h->n_mel) * 4, s>>>(spec, Tld, T, h->nbins, h->mel, h->n_mel, h->dct, h->n_ceps,
+                                                                                use_energy ? energy : nullptr, mfcc_dev);
+  FACPPG_HIP_CHECK(hipGetLastError());
+  return FACPPG_OK;
+}
+
 extern "C" int facppg_cmn_splice_transform(const float* feats_dev, int T, int D, int do_cmn, int left, int right, const float* transform_dev,
                                            int M, int cols, float* out_dev, float* mean_ws_dev, void* stream_) {
   FACPPG_REQUIRE(feats_dev && out_dev && (mean_ws_dev || !do_cmn), FACPPG_EINVAL, "NULL argument");
@@ -235,6 +317,23 @@ extern "C" int facppg_cmn_splice_transform(const float* feats_dev, int T, int D,
   hipStream_t s = (hipStream_t)stream_;
   if (do_cmn) k_col_mean<<<1, 256, 0, s>>>(feats_dev, T, D, mean_ws_dev);
   k_cmn_splice_transform<<<T, 64, 0, s>>>(feats_dev, T, D, do_cmn ? mean_ws_dev : nullptr, left, right, transform_dev, M, cols, out_dev);
+  FACPPG_HIP_CHECK(hipGetLastError());
+  return FACPPG_OK;
+}
+
+extern "C" int facppg_cmn_splice_transform_batch(const float* feats_dev, const int32_t* frame_offsets_dev, const int32_t* frame_offsets_host,
+                                                 int B, int D, int do_cmn, int left, int right, const float* transform_dev, int M, int cols,
+                                                 float* out_dev, float* mean_ws_dev, void* stream_) {
+  if (int rc = check_offsets(frame_offsets_host, B, "facppg_cmn_splice_transform_batch")) return rc;
+  FACPPG_REQUIRE(feats_dev && frame_offsets_dev && out_dev && (mean_ws_dev || !do_cmn), FACPPG_EINVAL, "NULL argument");
+  FACPPG_REQUIRE(D > 0 && left >= 0 && right >= 0, FACPPG_EINVAL, "bad T/D/context");
+  const int W = (left + right + 1) * D;
+  if (transform_dev)
+    FACPPG_REQUIRE(M > 0 && (cols == W || cols == W + 1), FACPPG_EINVAL, "Transform matrix has bad dimension %dx%d versus feat dim %d", M, cols, W);
+  hipStream_t s = (hipStream_t)stream_;
+  if (do_cmn) k_col_mean_batch<<<B, 256, 0, s>>>(feats_dev, frame_offsets_dev, D, mean_ws_dev);
+  k_cmn_splice_transform_batch<<<frame_offsets_host[B], 64, 0, s>>>(feats_dev, frame_offsets_dev, B, D, do_cmn ? mean_ws_dev : nullptr, left, right,
+                                                                    transform_dev, M, cols, out_dev);
   FACPPG_HIP_CHECK(hipGetLastError());
   return FACPPG_OK;
 }

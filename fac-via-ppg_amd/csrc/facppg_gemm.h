@@ -20,6 +20,11 @@ namespace facppg {
 enum GemmAct { ACT_NONE = 0, ACT_RELU = 1, ACT_TANH = 2, ACT_LOG_CLAMP = 3 /* log(max(v, 1e-5)) */ };
 
 inline int gemm_kpad(int K) { return round_up(K, 64); }
+// K splits of a product whose caller lends a partial-sum buffer (gemm_launch): a function of K ALONE, 1 = not split
+inline int gemm_split_k(int K) {
+  const int nch = gemm_kpad(K) / 64;
+  return nch < 8 ? 1 : nch / 4 < 16 ? nch / 4 : 16;
+}
 // + 3 k-groups: k_gemm prefetches up to 3 groups past the last row block (never used)
 inline size_t packed_a_float4s(int M, int K) { return (size_t)(round_up(M, 32) / 32) * (gemm_kpad(K) / 8 + 1) * 64 + 3 * 64; }
 

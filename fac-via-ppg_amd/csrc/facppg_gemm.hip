@@ -306,9 +306,8 @@ int gemm_launch(const GemmArgs& a, hipStream_t s) {
   // long serial K loop each.  The split factor depends on K ALONE -- not on the batch or the padded
   // length -- so an utterance is summed in the same order whatever batch it rides in (padded batches equal
   // independent runs bit for bit); large products pay a little extra partial-sum traffic for that.
-  const int nch = ka.KG / 8;
-  if (a.splitk_ws && nch >= 8) {
-    const int sk = nch / 4 < 16 ? nch / 4 : 16;
+  const int sk = gemm_split_k(a.Cin * a.taps);
+  if (a.splitk_ws && sk > 1) {
     const size_t need = (size_t)sk * a.B * a.M * a.N * sizeof(float);
     FACPPG_REQUIRE(need <= a.splitk_ws_bytes, FACPPG_EWORKSPACE, "gemm_launch: split-K buffer has %zu bytes, needs %zu",
                    a.splitk_ws_bytes, need);

@@ -67,6 +67,125 @@ __global__ void k_tdnn_output(const float* __restrict__ y, int M, int Tp, int T,
   }
 }
 
+// ---- batch form: B utterances laid end to end, one column space -------------------------------------------------------
+// Utterance b owns the columns cs[b] .. cs[b+1]-1, cs[b+1] - cs[b] = round_up(L + T_b + R, 4) (the rounding keeps every
+// segment's start on a 16-byte boundary of its row), laid out inside exactly as the single-utterance form lays out its
+// Tp columns.  k_gemm reads columns n + tap*dil across a join, but only into columns outside every valid frame's
+// dependency cone: by the telescoping shifts above, frame t of utterance b at the last layer depends on the segment's own
+// columns t .. t + L + R alone.
+
+// cs[b] = sum_{i < b} round_up(L + T_i + R, 4), b = 0..B  (B is small against the column count: each thread sums its own prefix)
+__global__ void k_tdnn_colstart(const int* __restrict__ off, int B, int LR, int* __restrict__ cs) {
+  const int b = blockIdx.x * blockDim.x + threadIdx.x;
+  if (b > B) return;
+  int c = 0;
+  for (int i = 0; i < b; ++i) c += (LR + off[i + 1] - off[i] + 3) & ~3;
+  cs[b] = c;
+}
+
+// ragged k_tdnn_input: x0[c][cs[b] + j] = feats[off[b] + clamp(j - L, 0, T_b - 1)][c] for every column j of segment b
+__global__ void k_tdnn_input_batch(const float* __restrict__ feats, const int* __restrict__ off, const int* __restrict__ cs, int B,
+                                   float* __restrict__ x0, int D, int L, int N) {
+  const int n = blockIdx.x * blockDim.x + threadIdx.x, c = blockIdx.y;
+  if (n >= N) return;
+  const int b = seg_of(cs, B, n), T = off[b + 1] - off[b];
+  const int t = min(max(n - cs[b] - L, 0), T - 1);
+  x0[(size_t)c * N + n] = feats[(size_t)(off[b] + t) * D + c];
+}
+
+// ragged k_tdnn_output: frame g of the batch (utterance b, frame g - off[b]) sits in column cs[b] + g - off[b]; same
+// arithmetic per frame, in the same order, as k_tdnn_output
+__global__ void k_tdnn_output_batch(const float* __restrict__ y, const int* __restrict__ off, const int* __restrict__ cs, int B, int M,
+                                    int N, int final_op, float* __restrict__ out) {
+  const int g = blockIdx.x * blockDim.x + threadIdx.x;
+  if (g >= off[B]) return;
+  const int b = seg_of(off, B, g), t = cs[b] + g - off[b];
+  float mx = -INFINITY, sum = 0.0f;
+  if (final_op != 0) {
+    for (int m = 0; m < M; ++m) mx = fmaxf(mx, y[(size_t)m * N + t]);
+    for (int m = 0; m < M; ++m) sum += expf(y[(size_t)m * N + t] - mx);
+  }
+  const float lse = logf(sum);
+  for (int m = 0; m < M; ++m) {
+    const float v = y[(size_t)m * N + t];
+    out[(size_t)g * M + m] = final_op == 0 ? v : final_op == 1 ? expf(v - mx) / sum : v - mx - lse;
+  }
+}
+
+// Softmax fused with reduce_ppg_dim (compute_ppg.py:73-94): out[g][d] = sum_m softmax(y[:, col(g)])[m] * Rt[m][d], without
+// the [frames][M] posterior matrix in between.  One workgroup = MONO_FT consecutive frames of the batch.
+//  - logits are read as (frame f = tid % 16, channel row r = tid / 16): 16 neighbouring columns per channel row;
+//  - max and sum of exp: per thread over its channel rows, then over the 4 rows of a wave by lane exchange and over the 4
+//    waves through LDS;
+//  - exp(y - max) goes through LDS in chunks of MONO_CH channels x 16 frames; thread (d = tid % 64, part = tid / 64) keeps
+//    the 16 frames' sums of column d in registers and walks the chunk's channels part, part + 4, ..: one (coalesced) read of
+//    Rt per 16 multiply-adds, the posteriors broadcast from LDS;
+//  - the division by the sum of exp is applied once per output.
+constexpr int MONO_FT = 16, MONO_CH = 256;
+__global__ __launch_bounds__(256) void k_tdnn_mono(const float* __restrict__ y, const int* __restrict__ off, const int* __restrict__ cs,
+                                                   int B, int M, int N, const float* __restrict__ Rt, int Md, float* __restrict__ out) {
+  __shared__ __attribute__((aligned(16))) float pe[MONO_CH * MONO_FT];   // later: the 4 parts' sums [4][16][64]
+  __shared__ float red[4][MONO_FT], mxs[MONO_FT], sums[MONO_FT];
+  __shared__ int col[MONO_FT];
+  const int tid = threadIdx.x, f = tid & 15, r = tid >> 4, d = tid & 63, part = tid >> 6;
+  const int g0 = blockIdx.x * MONO_FT, G = off[B];
+  if (tid < MONO_FT) {
+    const int g = min(g0 + tid, G - 1);      // a frame past the end repeats the last one (never stored)
+    const int b = seg_of(off, B, g);
+    col[tid] = cs[b] + g - off[b];
+  }
+  __syncthreads();
+  const float* yc = y + col[f];
+  float mx = -INFINITY;
+  for (int m = r; m < M; m += 16) mx = fmaxf(mx, yc[(size_t)m * N]);
+  mx = fmaxf(mx, __shfl_xor(mx, 16));
+  mx = fmaxf(mx, __shfl_xor(mx, 32));
+  if ((tid & 63) < 16) red[part][f] = mx;
+  __syncthreads();
+  if (tid < MONO_FT) mxs[tid] = fmaxf(fmaxf(red[0][tid], red[1][tid]), fmaxf(red[2][tid], red[3][tid]));
+  __syncthreads();
+  mx = mxs[f];
+  float se = 0.0f, acc[MONO_FT];
+#pragma unroll
+  for (int i = 0; i < MONO_FT; ++i) acc[i] = 0.0f;
+  for (int c0 = 0; c0 < M; c0 += MONO_CH) {
+#pragma unroll 4
+    for (int i = 0; i < MONO_CH / 16; ++i) {
+      const int m = c0 + r + 16 * i;
+      const float e = m < M ? expf(yc[(size_t)m * N] - mx) : 0.0f;
+      pe[(r + 16 * i) * MONO_FT + f] = e;
+      se += e;
+    }
+    __syncthreads();
+    const int kend = min(MONO_CH, M - c0);
+    if (d < Md)
+      for (int kk = part; kk < kend; kk += 4) {
+        const float w = Rt[(size_t)(c0 + kk) * Md + d];
+        const float4* p4 = (const float4*)(pe + kk * MONO_FT);
+#pragma unroll
+        for (int q = 0; q < MONO_FT / 4; ++q) {
+          const float4 p = p4[q];
+          acc[4 * q] = fmaf(p.x, w, acc[4 * q]); acc[4 * q + 1] = fmaf(p.y, w, acc[4 * q + 1]);
+          acc[4 * q + 2] = fmaf(p.z, w, acc[4 * q + 2]); acc[4 * q + 3] = fmaf(p.w, w, acc[4 * q + 3]);
+        }
+      }
+    __syncthreads();
+  }
+  se += __shfl_xor(se, 16);
+  se += __shfl_xor(se, 32);
+  if ((tid & 63) < 16) red[part][f] = se;
+#pragma unroll
+  for (int i = 0; i < MONO_FT; ++i) pe[(part * MONO_FT + i) * 64 + d] = acc[i];
+  __syncthreads();
+  if (tid < MONO_FT) sums[tid] = (red[0][tid] + red[1][tid]) + (red[2][tid] + red[3][tid]);
+  __syncthreads();
+  for (int i = part; i < MONO_FT; i += 4) {
+    const int g = g0 + i;
+    if (g < G && d < Md)
+      out[(size_t)g * Md + d] = ((pe[i * 64 + d] + pe[(MONO_FT + i) * 64 + d]) + (pe[(2 * MONO_FT + i) * 64 + d] + pe[(3 * MONO_FT + i) * 64 + d])) / sums[i];
+  }
+}
+
 struct TdnnWs { size_t x[2], splitk, splitk_bytes, total; int Tp; };
 TdnnWs tdnn_ws(const facppg_tdnn* h, int T) {
   TdnnWs w;
@@ -79,6 +198,58 @@ TdnnWs tdnn_ws(const facppg_tdnn* h, int T) {
   w.splitk = take(w.splitk_bytes);
   w.total = off;
   return w;
+}
+
+struct TdnnBatchWs { size_t x[2], splitk, splitk_bytes, cs, total; long N; };
+TdnnBatchWs tdnn_batch_ws(const facppg_tdnn* h, const int32_t* off, int B) {
+  TdnnBatchWs w;
+  w.N = 0;
+  for (int b = 0; b < B; ++b) w.N += round_up(h->left + h->right + off[b + 1] - off[b], 4);
+  size_t o = 0;
+  auto take = [&](size_t bytes) { size_t r = o; o += (bytes + 255) / 256 * 256; return r; };
+  w.x[0] = take((size_t)h->max_dim * w.N * 4);
+  w.x[1] = take((size_t)h->max_dim * w.N * 4);
+  size_t parts = 0;      // the largest layer's partial sums (the single form's 16 * max_dim bound costs GBs at a corpus's N)
+  for (const facppg_tdnn_layer& l : h->layers) {
+    const int sk = gemm_split_k(l.in_dim * l.taps);
+    if (sk > 1 && (size_t)sk * l.out_dim > parts) parts = (size_t)sk * l.out_dim;
+  }
+  w.splitk_bytes = parts * w.N * 4;
+  w.splitk = take(w.splitk_bytes);
+  w.cs = take((size_t)(B + 1) * 4);
+  w.total = o;
+  return w;
+}
+
+// the layers of the batch form up to the last layer's output [out_dim][N]; *y_out = that buffer
+int tdnn_batch_layers(facppg_tdnn* h, const float* feats_dev, const int32_t* off_dev, const int32_t* off_host, int B, void* ws_,
+                      size_t ws_bytes, hipStream_t s, const float** y_out, const int** cs_out, int* N_out) {
+  FACPPG_REQUIRE(h && feats_dev && off_dev && ws_, FACPPG_EINVAL, "NULL argument");
+  const TdnnBatchWs w = tdnn_batch_ws(h, off_host, B);
+  FACPPG_REQUIRE(w.N * (long)h->max_dim < (1l << 31), FACPPG_EUNSUPPORTED, "batch of %ld columns x %d channels exceeds 2^31 elements: split it", w.N,
+                 h->max_dim);
+  FACPPG_REQUIRE(ws_bytes >= w.total, FACPPG_EWORKSPACE, "workspace has %zu bytes, need %zu", ws_bytes, w.total);
+  char* ws = (char*)ws_;
+  float* x[2] = {(float*)(ws + w.x[0]), (float*)(ws + w.x[1])};
+  int* cs = (int*)(ws + w.cs);
+  const int N = (int)w.N;
+  k_tdnn_colstart<<<(B + 256) / 256, 256, 0, s>>>(off_dev, B, h->left + h->right, cs);
+  k_tdnn_input_batch<<<dim3((N + 255) / 256, h->in_dim), 256, 0, s>>>(feats_dev, off_dev, cs, B, x[0], h->in_dim, h->left, N);
+  int cur = 0;
+  for (int i = 0; i < h->n_layers; ++i) {
+    const facppg_tdnn_layer& l = h->layers[i];
+    GemmArgs g;
+    g.A = h->A[i]; g.M = l.out_dim; g.Cin = l.in_dim; g.taps = l.taps; g.dil = l.dil; g.pad = 0;
+    g.X = x[cur]; g.ldx = N; g.N = N; g.bias = h->bias[i]; g.act = l.relu ? ACT_RELU : ACT_NONE;
+    g.C = x[cur ^ 1]; g.ldc = N; g.B = 1;
+    g.splitk_ws = (float*)(ws + w.splitk); g.splitk_ws_bytes = w.splitk_bytes;
+    const int rc = gemm_launch(g, s);
+    if (rc != FACPPG_OK) return rc;
+    cur ^= 1;
+    if (l.renorm_target_rms > 0.0f) k_tdnn_renorm<<<(N + 255) / 256, 256, 0, s>>>(x[cur], l.out_dim, N, l.renorm_target_rms);
+  }
+  *y_out = x[cur]; *cs_out = cs; *N_out = N;
+  return FACPPG_OK;
 }
 
 }  // namespace
@@ -204,6 +375,39 @@ extern "C" int facppg_tdnn_forward(facppg_tdnn* h, const float* feats_dev, int T
     if (l.renorm_target_rms > 0.0f) k_tdnn_renorm<<<(Tp + 255) / 256, 256, 0, s>>>(x[cur], l.out_dim, Tp, l.renorm_target_rms);
   }
   k_tdnn_output<<<(T + 63) / 64, 64, 0, s>>>(x[cur], h->out_dim, Tp, T, h->final_op, out_dev);
+  FACPPG_HIP_CHECK(hipGetLastError());
+  return FACPPG_OK;
+}
+
+extern "C" size_t facppg_tdnn_batch_workspace_bytes(const facppg_tdnn* h, const int32_t* offsets_host, int B) {
+  if (!h || check_offsets(offsets_host, B, "facppg_tdnn_batch_workspace_bytes")) return 0;
+  return tdnn_batch_ws(h, offsets_host, B).total;
+}
+
+extern "C" int facppg_tdnn_forward_batch(facppg_tdnn* h, const float* feats_dev, const int32_t* offsets_dev, const int32_t* offsets_host,
+                                         int B, float* out_dev, void* ws_, size_t ws_bytes, void* stream_) {
+  if (int rc = check_offsets(offsets_host, B, "facppg_tdnn_forward_batch")) return rc;
+  FACPPG_REQUIRE(out_dev, FACPPG_EINVAL, "NULL argument");
+  hipStream_t s = (hipStream_t)stream_;
+  const float* y; const int* cs; int N;
+  if (int rc = tdnn_batch_layers(h, feats_dev, offsets_dev, offsets_host, B, ws_, ws_bytes, s, &y, &cs, &N)) return rc;
+  k_tdnn_output_batch<<<(offsets_host[B] + 63) / 64, 64, 0, s>>>(y, offsets_dev, cs, B, h->out_dim, N, h->final_op, out_dev);
+  FACPPG_HIP_CHECK(hipGetLastError());
+  return FACPPG_OK;
+}
+
+extern "C" int facppg_tdnn_forward_batch_reduced(facppg_tdnn* h, const float* feats_dev, const int32_t* offsets_dev,
+                                                 const int32_t* offsets_host, int B, const float* transform_t_dev, int M, float* out_dev,
+                                                 void* ws_, size_t ws_bytes, void* stream_) {
+  if (int rc = check_offsets(offsets_host, B, "facppg_tdnn_forward_batch_reduced")) return rc;
+  FACPPG_REQUIRE(h && out_dev && transform_t_dev, FACPPG_EINVAL, "NULL argument");
+  FACPPG_REQUIRE(M > 0 && M <= 64, FACPPG_EINVAL, "bad M (1 <= M <= 64, got %d)", M);
+  FACPPG_REQUIRE(h->final_op == 1, FACPPG_EUNSUPPORTED, "the fused reduction needs a model whose output is a softmax (final_op 1, got %d)",
+                 h->final_op);
+  hipStream_t s = (hipStream_t)stream_;
+  const float* y; const int* cs; int N;
+  if (int rc = tdnn_batch_layers(h, feats_dev, offsets_dev, offsets_host, B, ws_, ws_bytes, s, &y, &cs, &N)) return rc;
+  k_tdnn_mono<<<(offsets_host[B] + MONO_FT - 1) / MONO_FT, 256, 0, s>>>(y, offsets_dev, cs, B, h->out_dim, N, transform_t_dev, M, out_dev);
   FACPPG_HIP_CHECK(hipGetLastError());
   return FACPPG_OK;
 }

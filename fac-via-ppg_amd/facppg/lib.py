@@ -205,6 +205,9 @@ def _declare(lib):
         "facppg_mfcc_workspace_bytes": (sz, [vp, c.c_int]),
         "facppg_mfcc_compute": (c.c_int, [vp, vp, c.c_int, c.c_int, vp, vp, sz, vp]),
         "facppg_cmn_splice_transform": (c.c_int, [vp, c.c_int, c.c_int, c.c_int, c.c_int, c.c_int, vp, c.c_int, c.c_int, vp, vp, vp]),
+        "facppg_mfcc_batch_workspace_bytes": (sz, [vp, c.c_int]),
+        "facppg_mfcc_compute_batch": (c.c_int, [vp, vp, vp, vp, vp, vp, c.c_int, c.c_int, vp, vp, sz, vp]),
+        "facppg_cmn_splice_transform_batch": (c.c_int, [vp, vp, vp, c.c_int, c.c_int, c.c_int, c.c_int, c.c_int, vp, c.c_int, c.c_int, vp, vp, vp]),
         "facppg_resample_num_samples": (c.c_int, [c.c_int, c.c_int, c.c_int]),
         "facppg_resample": (c.c_int, [vp, c.c_int, c.c_int, c.c_int, vp, vp]),
         "facppg_reduce_ppg": (c.c_int, [vp, vp, c.c_int, c.c_int, c.c_int, vp, vp]),
@@ -216,6 +219,9 @@ def _declare(lib):
         "facppg_tdnn_context": (c.c_int, [vp, c.POINTER(c.c_int), c.POINTER(c.c_int)]),
         "facppg_tdnn_workspace_bytes": (sz, [vp, c.c_int]),
         "facppg_tdnn_forward": (c.c_int, [vp, vp, c.c_int, vp, vp, sz, vp]),
+        "facppg_tdnn_batch_workspace_bytes": (sz, [vp, vp, c.c_int]),
+        "facppg_tdnn_forward_batch": (c.c_int, [vp, vp, vp, vp, c.c_int, vp, vp, sz, vp]),
+        "facppg_tdnn_forward_batch_reduced": (c.c_int, [vp, vp, vp, vp, c.c_int, vp, c.c_int, vp, vp, sz, vp]),
         "facppg_attention_window_mask": (c.c_int, [vp, c.c_int, c.c_int, c.c_int, c.c_int, vp, vp]),
     }
     for name, (res, args) in sigs.items():
@@ -263,6 +269,19 @@ def upload(values, dtype, device):
     from pageable memory waits for the stream to reach it (with a WaveGlow.infer in front, > 100 ms during which nothing
     else gets enqueued); from a pinned staging tensor it is just another queued command."""
     return torch.tensor(values, dtype=dtype).pin_memory().to(device, non_blocking=True)
+
+
+def host_offsets(lengths):
+    """Lengths of a batch of utterances laid end to end -> their B + 1 offsets as a C int32 array (the host copy the batch
+    entry points take); ``offsets_array(values)`` wraps offsets that are already cumulative."""
+    off = [0]
+    for n in lengths:
+        off.append(off[-1] + int(n))
+    return offsets_array(off)
+
+
+def offsets_array(offsets):
+    return (ctypes.c_int32 * len(offsets))(*[int(v) for v in offsets])
 
 
 def current_stream(device):

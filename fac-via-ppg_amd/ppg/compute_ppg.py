@@ -9,6 +9,10 @@
                            features [T, 40] -> senone posteriors [T, K] (compute_ppg.py:42-70).  The model is read by
                            common.decode.read_nnet3_model / common.nnet3 -- PARITY UNPINNED: the reference ships neither
                            the model (data/am/final.raw) nor anything Kaldi computed from it
+  compute_feat_for_nnet_batch, compute_full_ppg_batch, compute_ppg_batch
+                           the same chain for a LIST of utterances in one pass: the utterances are laid end to end, every
+                           TDNN layer is one GEMM over all of them (facppg_tdnn_forward_batch), and the monophone
+                           reduction is fused into the output kernel (facppg_tdnn_forward_batch_reduced)
 
 Matrices are float32 GPU tensors; file paths default to ``<repo data dir>/...`` like the reference's module constants and
 can be overridden (FACPPG_DATA_DIR, or the constructor arguments)."""
@@ -83,6 +87,78 @@ def compute_full_ppg(nnet, feats):
     return out
 
 
+def _require_model(nnet, what):
+    if nnet is None:
+        raise _lib.FacppgError("%s: no acoustic model -- the reference does not ship data/am/final.raw; pass a model read "
+                               "with common.decode.read_nnet3_model, or use precomputed PPGs (common.data_utils.get_ppg)" % what)
+
+
+def _tdnn_handle(nnet, dev, what):
+    _require_model(nnet, what)
+    h = getattr(nnet, "_facppg_tdnn", None)
+    if h is None or h.dev != dev:
+        h = nnet._facppg_tdnn = _TdnnHandle(nnet, dev)
+    return h
+
+
+def _full_ppg_flat(nnet, feats, frames, transform=None):
+    """feats [sum T, D] (GPU, the utterances laid end to end) x frame counts -> [sum T, K] posteriors, or with ``transform``
+    ([d, K], read_sparse_mat) the [sum T, d] monophone PPGs from the fused output kernel."""
+    L = _lib.load()
+    dev = feats.device
+    h = _tdnn_handle(nnet, dev, "compute_full_ppg_batch")
+    T, D = feats.shape
+    if D != h.in_dim:
+        raise _lib.FacppgError("compute_full_ppg_batch: features have %d dims, the model's input node has %d" % (D, h.in_dim))
+    off = _lib.host_offsets(frames)
+    if off[-1] != T:
+        raise ValueError("compute_full_ppg_batch: the frame counts add up to %d, the matrix has %d rows" % (off[-1], T))
+    B = len(frames)
+    nbytes = L.facppg_tdnn_batch_workspace_bytes(h.handle, off, B)
+    if nbytes == 0:
+        _lib.check(-1)
+    off_dev = _lib.upload(list(off), torch.int32, dev)
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    with torch.cuda.device(dev):
+        if transform is None:
+            out = torch.empty(T, h.out_dim, device=dev)
+            _lib.check(L.facppg_tdnn_forward_batch(h.handle, _lib.ptr(feats), _lib.ptr(off_dev), off, B, _lib.ptr(out), _lib.ptr(ws), ws.numel(),
+                                                   _lib.current_stream(dev)))
+        else:
+            tr_t = torch.as_tensor(transform).to(dev).float().t().contiguous()            # [K, d]
+            if tr_t.shape[0] != h.out_dim:
+                raise _lib.FacppgError("reduce_ppg_dim: PPG has %d dims, the transform expects %d" % (h.out_dim, tr_t.shape[0]))
+            out = torch.empty(T, tr_t.shape[1], device=dev)
+            _lib.check(L.facppg_tdnn_forward_batch_reduced(h.handle, _lib.ptr(feats), _lib.ptr(off_dev), off, B, _lib.ptr(tr_t), tr_t.shape[1],
+                                                           _lib.ptr(out), _lib.ptr(ws), ws.numel(), _lib.current_stream(dev)))
+    return out
+
+
+def _split(flat, frames):
+    """[sum T, K] -> the B utterances' [T_b, K] (views of the one buffer)."""
+    out, at = [], 0
+    for n in frames:
+        out.append(flat[at:at + n])
+        at += n
+    return out
+
+
+def compute_full_ppg_batch(nnet, feats_list, transform=None):
+    """compute_full_ppg (compute_ppg.py:42-70) for a list of feature matrices [T_b, D] (GPU tensors or numpy) in ONE pass ->
+    list of [T_b, K] GPU tensors.  With ``transform`` (the pdf -> monophone matrix [d, K]) the list holds the [T_b, d]
+    monophone PPGs instead, reduced inside the output kernel (the model's output must be a softmax)."""
+    _require_model(nnet, "compute_full_ppg_batch")
+    if not len(feats_list):
+        raise ValueError("compute_full_ppg_batch: no utterance")
+    mats = []
+    for f in feats_list:
+        f = torch.as_tensor(f)
+        mats.append((f if f.is_cuda else f.cuda()).float())
+    frames = [int(m.shape[0]) for m in mats]
+    flat = mats[0].contiguous() if len(mats) == 1 else torch.cat(mats, 0)
+    return _split(_full_ppg_flat(nnet, flat, frames, transform), frames)
+
+
 def reduce_ppg_dim(ppgs, transform):
     """ppgs [T, D] (GPU tensor or numpy) x transform [d, D] (dense; read_sparse_mat) -> [T, d] on the GPU."""
     L = _lib.load()
@@ -117,6 +193,45 @@ def compute_feat_for_nnet_internal(wav, lda, **kwargs):
     mfcc_opts.frame_opts.snip_edges = options["is_snip_edges"]
     mfccs = feat.compute_mfcc_feats(wav, mfcc_opts)
     return feat.cmn_splice_transform(mfccs, options["left_context"], options["right_context"], lda)
+
+
+def _feat_for_nnet_flat(wavs, lda, **kwargs):
+    options = {"is_use_energy": False, "is_downsample": True, "frame_shift": 10, "is_snip_edges": False, "left_context": 3,
+               "right_context": 3}
+    for key, val in kwargs.items():
+        if key in options:
+            options[key] = val
+        else:
+            logging.error("Option %s not allowed!" % (key))
+    mfcc_opts = feat.MfccOptions()
+    mfcc_opts.use_energy = options["is_use_energy"]
+    mfcc_opts.frame_opts.allow_downsample = options["is_downsample"]
+    mfcc_opts.frame_opts.frame_shift_ms = options["frame_shift"]
+    mfcc_opts.frame_opts.snip_edges = options["is_snip_edges"]
+    mfccs, frames = feat.compute_mfcc_feats_batch(wavs, mfcc_opts)
+    return feat.cmn_splice_transform_batch(mfccs, frames, options["left_context"], options["right_context"], lda), frames
+
+
+def compute_feat_for_nnet_batch(wavs, lda, **options):
+    """compute_feat_for_nnet_internal (compute_ppg.py:97-134, same options and defaults) for a list of WaveData in one pass
+    -> list of [T_b, 40] GPU tensors, each equal to the single call's bit for bit."""
+    flat, frames = _feat_for_nnet_flat(wavs, lda, **options)
+    return _split(flat, frames)
+
+
+def compute_ppg_batch(wavs, deps, is_full_ppg=True, shift=10):
+    """compute_full_ppg_wrapper / compute_monophone_ppg (compute_ppg.py:161-202) for a list of WaveData in one pass: wav ->
+    features -> acoustic model -> list of GPU tensors [T_b, K]: the senone posteriors, or with ``is_full_ppg=False`` the
+    monophone PPGs through ``deps.monophone_trans``."""
+    _require_model(deps.nnet, "compute_ppg_batch")
+    flat, frames = _feat_for_nnet_flat(wavs, deps.lda, frame_shift=shift)
+    if is_full_ppg:
+        return _split(_full_ppg_flat(deps.nnet, flat, frames), frames)
+    if deps.monophone_trans is None:
+        raise _lib.FacppgError("compute_ppg_batch: monophone PPGs need the pdf -> monophone matrix (data/feats/reduce_dim.mat)")
+    if nnet3.plan_layers(deps.nnet)[1] != "softmax":      # the fused kernel reduces posteriors: other outputs go the long way
+        return [reduce_ppg_dim(p, deps.monophone_trans) for p in _split(_full_ppg_flat(deps.nnet, flat, frames), frames)]
+    return _split(_full_ppg_flat(deps.nnet, flat, frames, deps.monophone_trans), frames)
 
 
 def compute_feat_for_nnet(wav_path, lda_path):

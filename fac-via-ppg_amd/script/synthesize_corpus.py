@@ -9,6 +9,10 @@ BASELINE.json's north_star.  Utterances are independent, so each rank synthesise
   python -m torch.distributed.run --nnodes=1 --nproc-per-node 8 --master-addr 127.0.0.1 \
       -m script.synthesize_corpus --ppg2mel_model taco.pt --waveglow_model wg.pt \
       --ppg_list ppgs.txt --output_dir out/ --batch_size 64
+
+With ``--wav_list`` instead of ``--ppg_list`` the corpus is a list of teacher wavs (the reference's purpose: wav in,
+converted wav out, generate_synthesis.py:60-98): each rank extracts the PPGs of its own shard through the batch front end
+(common.data_utils.get_ppg_batch, ``--batch_size`` utterances per pass) and then synthesises as above.
 """
 import argparse
 import os
@@ -28,7 +32,13 @@ def parse(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument('--ppg2mel_model', required=True)
     ap.add_argument('--waveglow_model', required=True)
-    ap.add_argument('--ppg_list', required=True, help='text file, one precomputed PPG .npy path per line')
+    src = ap.add_mutually_exclusive_group(required=True)
+    src.add_argument('--ppg_list', help='text file, one precomputed PPG .npy path per line')
+    src.add_argument('--wav_list', help='text file, one teacher wav per line: the PPGs are extracted here (acoustic model: --nnet_path '
+                                        'and the files of --feats_dir; senone or monophone PPGs by the hparam is_full_ppg)')
+    ap.add_argument('--nnet_path', default=None, help='nnet3 acoustic model for --wav_list (default: data/am/final.raw)')
+    ap.add_argument('--feats_dir', default=None, help='directory of final.mat, reduce_dim.mat and splice_opts for --wav_list '
+                                                      '(default: data/feats)')
     ap.add_argument('--output_dir', required=True)
     ap.add_argument('--batch_size', type=int, default=64,
                     help='utterances per synthesis batch; the latency-bound decoder costs the same for 16 or 96 utterances, so larger '
@@ -67,6 +77,34 @@ def parse_hparams(text):
         default = getattr(base, name)
         kw[name] = (value.lower() in ('1', 'true')) if isinstance(default, bool) else type(default)(value)
     return create_hparams_stage(**kw)
+
+
+def wav_ppg_lengths(paths):
+    """PPG frames each teacher wav will yield (10 ms shift at 16 kHz, Kaldi snip_edges = false), from the wav headers alone:
+    what the shards are balanced by before any PPG exists."""
+    from facppg import lib as _lib
+    L = _lib.load()
+    lengths = []
+    for p in paths:
+        fs, wav = wavfile.read(p, mmap=True)
+        n = wav.shape[0] if fs == FS else L.facppg_resample_num_samples(wav.shape[0], int(fs), FS)
+        lengths.append((n + FS // 200) // (FS // 100))
+    return lengths
+
+
+def extract_shard_ppgs(paths, mine, lengths, args, hparams):
+    """{global id: PPG} of this rank's utterances, extracted ``args.batch_size`` at a time in batches of similar length."""
+    from common.data_utils import get_ppg_batch
+    from ppg import compute_ppg
+    feats_dir = args.feats_dir or os.path.dirname(compute_ppg.LDA_PATH)
+    deps = compute_ppg.DependenciesPPG(nnet_path=args.nnet_path or compute_ppg.NNET_PATH, lda_path=os.path.join(feats_dir, "final.mat"),
+                                       reduce_dim_path=os.path.join(feats_dir, "reduce_dim.mat"),
+                                       splice_opts_path=os.path.join(feats_dir, "splice_opts"))
+    ppgs = {}
+    for batch in shard.batches(mine, lengths, args.batch_size):
+        for i, p in zip(batch, get_ppg_batch([paths[i] for i in batch], deps, is_full_ppg=hparams.is_full_ppg)):
+            ppgs[i] = p
+    return ppgs
 
 
 def synthesize_shard(synthesizer, ppgs, lengths, rank, world, args):
@@ -122,12 +160,18 @@ def main(argv=None, synthesizer=None):
         else:
             dist.init_process_group(args.dist_backend, rank=rank, world_size=world)
     try:
-        paths = load_filepaths(args.ppg_list)
-        ppgs = [np.load(p, mmap_mode="r") for p in paths]
-        lengths = [p.shape[0] for p in ppgs]
+        hparams = parse_hparams(args.hparams)
+        if args.wav_list:
+            paths = load_filepaths(args.wav_list)
+            lengths = wav_ppg_lengths(paths)
+            ppgs = extract_shard_ppgs(paths, shard.partition(lengths, world)[rank], lengths, args, hparams)
+        else:
+            paths = load_filepaths(args.ppg_list)
+            ppgs = [np.load(p, mmap_mode="r") for p in paths]
+            lengths = [p.shape[0] for p in ppgs]
         if synthesizer is None:
             from facppg.pipeline import Synthesizer
-            synthesizer = Synthesizer(args.ppg2mel_model, args.waveglow_model, hparams=parse_hparams(args.hparams),
+            synthesizer = Synthesizer(args.ppg2mel_model, args.waveglow_model, hparams=hparams,
                                       vocoder_arithmetic=args.vocoder_arithmetic)
         wavs, ids = synthesize_shard(synthesizer, ppgs, lengths, rank, world, args)
         gathered = collect(wavs, ids, world)

@@ -765,6 +765,26 @@ int facppg_resample(const float* wav_dev, int n_in, int fs_in, int fs_out, float
 int facppg_cmn_splice_transform(const float* feats_dev, int T, int D, int do_cmn, int left, int right,
                                 const float* transform_dev, int M, int cols, float* out_dev,
                                 float* mean_ws_dev, void* stream);
+/* The two front-end steps above for a BATCH of utterances laid end to end (the per-utterance loops of
+ * PPGMelLoader.__init__ / get_ppg, data_utils.py:55-59, 204-209, over compute_feat_for_nnet_internal, compute_ppg.py:97-134):
+ * wav_dev holds the B waveforms one after the other (all at the model's rate: facppg_resample stays per utterance),
+ * sample_offsets[B + 1] and frame_offsets[B + 1] (off[0] = 0, increasing; T_b = facppg_mfcc_num_frames of utterance b's
+ * sample count) both on the device and on the host.  Per frame the arithmetic is that of the single-utterance entry
+ * points in the same order, so an utterance gets the same bits in any batch: frames reflect at the utterance's own ends
+ * (Kaldi snip_edges = false), the cepstral mean is taken over its own frames, the splice clamps to its own first / last
+ * frame.  facppg_mfcc_compute_batch (replaces Mfcc.compute_features, feat.py:98, per utterance): -> mfcc_dev
+ * [sum T][n_ceps].  A sample count the single call refuses is refused with the same message. */
+size_t facppg_mfcc_batch_workspace_bytes(const facppg_mfcc* h, int total_frames);
+int facppg_mfcc_compute_batch(facppg_mfcc* h, const float* wav_dev, const int32_t* sample_offsets_dev,
+                              const int32_t* sample_offsets_host, const int32_t* frame_offsets_dev,
+                              const int32_t* frame_offsets_host, int B, int use_energy, float* mfcc_dev,
+                              void* workspace_dev, size_t workspace_bytes, void* stream);
+/* facppg_cmn_splice_transform_batch (replaces apply_cepstral_mean_norm, splice_frames and apply_feat_transform,
+ * feat.py:103-156, per utterance): feats_dev [sum T][D] -> out_dev [sum T][M]; mean_ws_dev: B * D floats of scratch. */
+int facppg_cmn_splice_transform_batch(const float* feats_dev, const int32_t* frame_offsets_dev,
+                                      const int32_t* frame_offsets_host, int B, int D, int do_cmn, int left,
+                                      int right, const float* transform_dev, int M, int cols, float* out_dev,
+                                      float* mean_ws_dev, void* stream);
 /* Replaces reduce_ppg_dim (compute_ppg.py:73-94): out[t][m] = sum_k ppg[t][k] * transform_t[k][m]
  * (transform_t = the densified pdf -> monophone matrix, TRANSPOSED: [K][M], M <= 64). */
 int facppg_reduce_ppg(const float* ppg_dev, const float* transform_t_dev, int T, int K, int M,
@@ -809,6 +829,24 @@ size_t facppg_tdnn_workspace_bytes(const facppg_tdnn* h, int T);
  * the utterance's ends are the first / last frame repeated (DecodableNnetSimple's edge handling). */
 int facppg_tdnn_forward(facppg_tdnn* h, const float* feats_dev, int T, float* out_dev, void* workspace_dev,
                         size_t ws_bytes, void* stream);
+
+/* compute_full_ppg (compute_ppg.py:42-70) for a BATCH of utterances in one pass: feats_dev holds the utterances'
+ * [T_b][in_dim] rows laid end to end, offsets[B + 1] their frame offsets (off[0] = 0, increasing), on the device and on
+ * the host; out_dev [sum T][out_dim].  The utterances share one column space (each segment [left | T_b | right] with its
+ * own edge frames repeated, starting on a 4-column boundary), every layer is ONE GEMM over all of it, and no valid frame
+ * depends on a column of another utterance.  Softmax and renorm are the single call's arithmetic per frame; through the
+ * GEMM layers the sums are k_gemm's, whose order does not depend on the column count. */
+size_t facppg_tdnn_batch_workspace_bytes(const facppg_tdnn* h, const int32_t* offsets_host, int B);
+int facppg_tdnn_forward_batch(facppg_tdnn* h, const float* feats_dev, const int32_t* offsets_dev,
+                              const int32_t* offsets_host, int B, float* out_dev, void* workspace_dev,
+                              size_t ws_bytes, void* stream);
+/* The same, followed by reduce_ppg_dim (compute_ppg.py:73-94) in the output kernel: out_dev [sum T][M] =
+ * softmax(logits) . transform_t ([out_dim][M], M <= 64, as facppg_reduce_ppg takes it) -- the monophone PPGs of
+ * compute_monophone_ppg (compute_ppg.py:161-181) without the [sum T][out_dim] posteriors in memory.  The model's
+ * output must be a softmax (final_op 1), else FACPPG_EUNSUPPORTED.  Same workspace. */
+int facppg_tdnn_forward_batch_reduced(facppg_tdnn* h, const float* feats_dev, const int32_t* offsets_dev,
+                                      const int32_t* offsets_host, int B, const float* transform_t_dev, int M,
+                                      float* out_dev, void* workspace_dev, size_t ws_bytes, void* stream);
 
 #ifdef __cplusplus
 }
