@@ -1393,8 +1393,8 @@ class WaveGlow(torch.nn.Module):
 
     def mel_convert(self, mel, T, frame0, nframes, melp, skip=None, handle=None, arithmetic=None):
         """Frames [frame0, frame0 + nframes) of the fp32 ``mel`` [n_mel, >= frame0 + nframes] (row stride mel.stride(0)) into the
-        fp16 zero-margined ``melp`` [Tqp, n_mel] laid out for T frames (k16_mel_cvt), on the current stream.  .half() modules.
-        arithmetic="bf16x3" (all-fp32 modules): into the split path's fp32 ``melp`` [Tqp, n_mel] (ks_mel_cvt)."""
+        fp16 zero-margined ``melp`` [Tqp, n_mel] laid out for T frames (k_cc_mel_cvt), on the current stream.  .half() modules.
+        arithmetic="bf16x3" (all-fp32 modules): into the split path's fp32 ``melp`` [Tqp, n_mel] (the same kernel, for fp32)."""
         split = self._check_arithmetic(arithmetic)
         dev = melp.device
         if split:
