@@ -10,6 +10,7 @@ libfacppg_hip instead of pykaldi.  Kaldi objects become plain tensors: a "Matrix
 
 Dither is not applied (Kaldi's default adds random +-1 LSB noise; this path is deterministic); inputs above 16 kHz are
 downsampled with Kaldi's LinearResample when allow_downsample is set (facppg_resample), as the reference does."""
+import copy
 import logging
 
 import numpy as np
@@ -232,9 +233,26 @@ class Mfcc(object):
         return out, frames
 
 
-def compute_mfcc_feats_batch(wavs, mfcc_opts):
-    """compute_mfcc_feats for a list of WaveData: (mfcc [sum T, D] of the first channels laid end to end, frame counts)."""
-    return Mfcc(mfcc_opts).compute_features_batch([w.data()[0] for w in wavs], [w.samp_freq for w in wavs])
+_KEPT_MFCC = {}
+
+
+def _kept_mfcc(opts):
+    """One Mfcc per set of option values, kept with its device tables: building one costs the host a float64 DFT basis, an
+    upload, and -- when it is dropped -- a hipFree, which waits for the device.  The key is the option VALUES and the kept
+    Mfcc holds a copy of them, so options changed afterwards find or make another entry; entries live as long as the process
+    (``_KEPT_MFCC.clear()`` releases them)."""
+    key = tuple(sorted(vars(opts.frame_opts).items())) + tuple(sorted(vars(opts.mel_opts).items())) + \
+        (opts.num_ceps, opts.use_energy, opts.cepstral_lifter)
+    if key not in _KEPT_MFCC:
+        _KEPT_MFCC[key] = Mfcc(copy.deepcopy(opts))
+    return _KEPT_MFCC[key]
+
+
+def compute_mfcc_feats_batch(wavs, mfcc_opts, keep_tables=False):
+    """compute_mfcc_feats for a list of WaveData: (mfcc [sum T, D] of the first channels laid end to end, frame counts).
+    keep_tables: compute with the Mfcc kept for these option values (same values; no table upload or hipFree in the call)."""
+    mfcc = _kept_mfcc(mfcc_opts) if keep_tables else Mfcc(mfcc_opts)
+    return mfcc.compute_features_batch([w.data()[0] for w in wavs], [w.samp_freq for w in wavs])
 
 
 def compute_mfcc_feats(wav, mfcc_opts):

@@ -38,7 +38,10 @@ __global__ void k_frames(const float* __restrict__ x, float* __restrict__ X, con
   int j = f * hop + k - fl / 2;
   if (j < 0) j = -j;
   if (j >= Nb) j = 2 * (Nb - 1) - j;
-  X[((size_t)b * fl + k) * F + f] = x[(size_t)b * N + j];
+  // an utterance of a ragged batch with Nb <= fl/2 samples (one or two frames of audio; the reference's reflect padding refuses it)
+  // reflects past its other end: the index stays inside the utterance instead of reading its neighbour, or in front of the buffer
+  j = min(max(j, 0), Nb - 1);
+  X[((size_t)b * fl + k) * F + f] = Nb > 0 ? x[(size_t)b * N + j] : 0.0f;      // (an empty utterance has one frame of silence)
 }
 
 // S[b][2*cutoff][F] (re rows then im rows) -> magnitude, phase   (stft.py:99-105)

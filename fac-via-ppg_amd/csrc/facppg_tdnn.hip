@@ -21,7 +21,7 @@
 using namespace facppg;
 
 struct facppg_tdnn {
-  int device = 0;
+  int device = 0, n_cu = 256;
   int n_layers = 0, final_op = 0, in_dim = 0, out_dim = 0, left = 0, right = 0, max_dim = 0;
   std::vector<facppg_tdnn_layer> layers;
   std::vector<float4*> A;
@@ -121,18 +121,25 @@ __global__ void k_tdnn_output_batch(const float* __restrict__ y, const int* __re
 //    the 16 frames' sums of column d in registers and walks the chunk's channels part, part + 4, ..: one (coalesced) read of
 //    Rt per 16 multiply-adds, the posteriors broadcast from LDS;
 //  - the division by the sum of exp is applied once per output.
+// PADDED = false stores out [sum T][Md] (frame g's row); PADDED = true stores the same values into out [B][Md][Tmax], the layout
+// the encoder reads (frame t of utterance b at out[b][d][t]; the columns T_b .. Tmax-1 are k_tdnn_zero_padding's):
+// the 16 frames of the tile then lie along the lanes, so that the stores of a channel row are neighbours.
 constexpr int MONO_FT = 16, MONO_CH = 256;
+template <bool PADDED>
 __global__ __launch_bounds__(256) void k_tdnn_mono(const float* __restrict__ y, const int* __restrict__ off, const int* __restrict__ cs,
-                                                   int B, int M, int N, const float* __restrict__ Rt, int Md, float* __restrict__ out) {
+                                                   int B, int M, int N, const float* __restrict__ Rt, int Md, float* __restrict__ out,
+                                                   int Tmax) {
   __shared__ __attribute__((aligned(16))) float pe[MONO_CH * MONO_FT];   // later: the 4 parts' sums [4][16][64]
   __shared__ float red[4][MONO_FT], mxs[MONO_FT], sums[MONO_FT];
   __shared__ int col[MONO_FT];
+  __shared__ size_t dst[MONO_FT];      // PADDED: offset of out[b][0][t] for the tile's frames
   const int tid = threadIdx.x, f = tid & 15, r = tid >> 4, d = tid & 63, part = tid >> 6;
   const int g0 = blockIdx.x * MONO_FT, G = off[B];
   if (tid < MONO_FT) {
     const int g = min(g0 + tid, G - 1);      // a frame past the end repeats the last one (never stored)
     const int b = seg_of(off, B, g);
     col[tid] = cs[b] + g - off[b];
+    if (PADDED) dst[tid] = (size_t)b * Md * Tmax + (g - off[b]);
   }
   __syncthreads();
   const float* yc = y + col[f];
@@ -175,15 +182,84 @@ __global__ __launch_bounds__(256) void k_tdnn_mono(const float* __restrict__ y, 
   se += __shfl_xor(se, 32);
   if ((tid & 63) < 16) red[part][f] = se;
 #pragma unroll
-  for (int i = 0; i < MONO_FT; ++i) pe[(part * MONO_FT + i) * 64 + d] = acc[i];
+  for (int i = 0; i < MONO_FT; ++i) pe[(part * MONO_FT + i) * 64 + (PADDED ? (d + 4 * i) & 63 : d)] = acc[i];
   __syncthreads();
   if (tid < MONO_FT) sums[tid] = (red[0][tid] + red[1][tid]) + (red[2][tid] + red[3][tid]);
   __syncthreads();
+  if (PADDED) {      // (frame f, channels r, r + 16, ..): the same expression per output, stored along the frames
+    // the sums of frame i sit rotated by 4 i within their row of 64: the 64 lanes (16 frames x 4 neighbouring channels) read 64 banks
+    if (g0 + f < G)
+      for (int dd = r; dd < Md; dd += 16) {
+        const int c = (dd + 4 * f) & 63;
+        out[dst[f] + (size_t)dd * Tmax] =
+            ((pe[f * 64 + c] + pe[(MONO_FT + f) * 64 + c]) + (pe[(2 * MONO_FT + f) * 64 + c] + pe[(3 * MONO_FT + f) * 64 + c])) / sums[f];
+      }
+    return;
+  }
   for (int i = part; i < MONO_FT; i += 4) {
     const int g = g0 + i;
     if (g < G && d < Md)
       out[(size_t)g * Md + d] = ((pe[i * 64 + d] + pe[(MONO_FT + i) * 64 + d]) + (pe[(2 * MONO_FT + i) * 64 + d] + pe[(3 * MONO_FT + i) * 64 + d])) / sums[i];
   }
+}
+
+// out [B][Md][Tmax]: the columns T_b .. Tmax-1 of every channel row, which k_tdnn_mono<true> does not visit, are set to 0
+__global__ void k_tdnn_zero_padding(const int* __restrict__ off, int Md, int Tmax, float* __restrict__ out) {
+  const int b = blockIdx.z, d = blockIdx.y, t = blockIdx.x * blockDim.x + threadIdx.x;
+  if (t < Tmax && t >= off[b + 1] - off[b]) out[((size_t)b * Md + d) * Tmax + t] = 0.0f;
+}
+
+// Softmax over the M channel rows of a column, written as out [B][M][Tmax] -- the layout the encoder reads (ppg_dev, channel-major
+// with the frames contiguous), which is also the layout of the logits: no transpose.  One workgroup = POST_FT consecutive frames
+// of ONE utterance (blockIdx.x, blockIdx.y) x the channel rows k0 .. k0 + kper - 1 it stores (blockIdx.z).
+//  - threads are (frame f = tid % 16, channel row r = tid / 16): the 16 lanes of a channel row read 16 neighbouring logits and
+//    store 16 neighbouring posteriors (scalar accesses: a segment starts on a multiple of 4 columns, an output row anywhere);
+//  - max and sum of exp over ALL M rows in every workgroup, whatever rows it stores (the logits of a tile are 16 x M floats out
+//    of the L2; splitting the stores over blockIdx.z is what fills the CUs when a batch has a few hundred columns): per thread
+//    over its rows r, r + 16, .. in order, then over the 4 rows of a wave by lane exchange, then over the 4 waves through LDS,
+//    pairwise -- k_tdnn_mono's order.  No atomics; a frame's posteriors depend on its own column alone, not on B, Tmax, the
+//    segment's start or kper;
+//  - the value is k_tdnn_output's expf(v - max) / sum;
+//  - frames T_b .. Tmax-1 of an utterance are stored as 0: every element of out is written.
+constexpr int POST_FT = 16;
+__global__ __launch_bounds__(256) void k_tdnn_post_padded(const float* __restrict__ y, const int* __restrict__ off, const int* __restrict__ cs,
+                                                          int M, int N, int Tmax, int kper, float* __restrict__ out) {
+  __shared__ float red[4][POST_FT], stat[POST_FT];
+  const int tid = threadIdx.x, f = tid & 15, r = tid >> 4, wave = tid >> 6;
+  const int b = blockIdx.y, t0 = blockIdx.x * POST_FT, t = t0 + f, T = off[b + 1] - off[b];
+  const int k0 = blockIdx.z * kper, k1 = min(M, k0 + kper);
+  float* ob = out + (size_t)b * M * Tmax + t;
+  if (t0 >= T) {      // (uniform over the workgroup) a tile of padding
+    if (t < Tmax)
+      for (int k = k0 + r; k < k1; k += 16) ob[(size_t)k * Tmax] = 0.0f;
+    return;
+  }
+  const float* yc = y + cs[b] + min(t, T - 1);      // a frame past the utterance's end repeats its last one (stored as 0)
+  float mx = -INFINITY;
+#pragma unroll 8
+  for (int m = r; m < M; m += 16) mx = fmaxf(mx, yc[(size_t)m * N]);
+  mx = fmaxf(mx, __shfl_xor(mx, 16));
+  mx = fmaxf(mx, __shfl_xor(mx, 32));
+  if ((tid & 63) < 16) red[wave][f] = mx;
+  __syncthreads();
+  if (tid < POST_FT) stat[tid] = fmaxf(fmaxf(red[0][tid], red[1][tid]), fmaxf(red[2][tid], red[3][tid]));
+  __syncthreads();
+  mx = stat[f];
+  float se = 0.0f;
+#pragma unroll 8
+  for (int m = r; m < M; m += 16) se += expf(yc[(size_t)m * N] - mx);
+  se += __shfl_xor(se, 16);
+  se += __shfl_xor(se, 32);
+  __syncthreads();      // (every thread has read stat[] as the max)
+  if ((tid & 63) < 16) red[wave][f] = se;
+  __syncthreads();
+  if (tid < POST_FT) stat[tid] = (red[0][tid] + red[1][tid]) + (red[2][tid] + red[3][tid]);
+  __syncthreads();
+  const float sum = stat[f];
+  if (t >= Tmax) return;
+  const bool valid = t < T;
+#pragma unroll 4
+  for (int k = k0 + r; k < k1; k += 16) ob[(size_t)k * Tmax] = valid ? expf(yc[(size_t)k * N] - mx) / sum : 0.0f;
 }
 
 struct TdnnWs { size_t x[2], splitk, splitk_bytes, total; int Tp; };
@@ -275,6 +351,7 @@ extern "C" int facppg_tdnn_create(const facppg_tdnn_layer* layers, int n_layers,
   facppg_tdnn* h = new (std::nothrow) facppg_tdnn;
   FACPPG_REQUIRE(h, FACPPG_EHIP, "out of host memory");
   h->device = device; h->n_layers = n_layers; h->final_op = final_op;
+  if (hipDeviceGetAttribute(&h->n_cu, hipDeviceAttributeMultiprocessorCount, device) != hipSuccess || h->n_cu < 1) h->n_cu = 256;
   h->layers.assign(layers, layers + n_layers);
   h->in_dim = layers[0].in_dim; h->out_dim = layers[n_layers - 1].out_dim; h->max_dim = h->in_dim;
   size_t a_f4 = 0, b_f = 0;
@@ -407,7 +484,46 @@ extern "C" int facppg_tdnn_forward_batch_reduced(facppg_tdnn* h, const float* fe
   hipStream_t s = (hipStream_t)stream_;
   const float* y; const int* cs; int N;
   if (int rc = tdnn_batch_layers(h, feats_dev, offsets_dev, offsets_host, B, ws_, ws_bytes, s, &y, &cs, &N)) return rc;
-  k_tdnn_mono<<<(offsets_host[B] + MONO_FT - 1) / MONO_FT, 256, 0, s>>>(y, offsets_dev, cs, B, h->out_dim, N, transform_t_dev, M, out_dev);
+  k_tdnn_mono<false><<<(offsets_host[B] + MONO_FT - 1) / MONO_FT, 256, 0, s>>>(y, offsets_dev, cs, B, h->out_dim, N, transform_t_dev, M, out_dev, 0);
+  FACPPG_HIP_CHECK(hipGetLastError());
+  return FACPPG_OK;
+}
+
+extern "C" int facppg_tdnn_forward_batch_padded(facppg_tdnn* h, const float* feats_dev, const int32_t* offsets_dev,
+                                                const int32_t* offsets_host, int B, const float* transform_t_dev, int M, int Tmax,
+                                                float* out_dev, void* ws_, size_t ws_bytes, void* stream_) {
+  FACPPG_REQUIRE(B >= 1, FACPPG_EINVAL, "facppg_tdnn_forward_batch_padded: B must be at least 1 (got %d)", B);
+  if (int rc = check_offsets(offsets_host, B, "facppg_tdnn_forward_batch_padded")) return rc;
+  FACPPG_REQUIRE(h && feats_dev && offsets_dev && out_dev && ws_, FACPPG_EINVAL, "facppg_tdnn_forward_batch_padded: NULL argument");
+  FACPPG_REQUIRE(!transform_t_dev || (M > 0 && M <= 64), FACPPG_EINVAL, "facppg_tdnn_forward_batch_padded: bad M (1 <= M <= 64, got %d)", M);
+  FACPPG_REQUIRE(h->final_op == 1, FACPPG_EUNSUPPORTED,
+                 "facppg_tdnn_forward_batch_padded: the padded layout holds posteriors: the model's output must be a softmax (final_op 1, got %d)",
+                 h->final_op);
+  int Tlong = 0, Tshort = Tmax;
+  for (int b = 0; b < B; ++b) {
+    const int T = offsets_host[b + 1] - offsets_host[b];
+    Tlong = T > Tlong ? T : Tlong;
+    Tshort = T < Tshort ? T : Tshort;
+  }
+  FACPPG_REQUIRE(Tmax >= Tlong, FACPPG_EINVAL, "facppg_tdnn_forward_batch_padded: Tmax %d is shorter than the longest utterance (%d frames)", Tmax,
+                 Tlong);
+  FACPPG_REQUIRE(B <= 65535, FACPPG_EUNSUPPORTED, "facppg_tdnn_forward_batch_padded: at most 65535 utterances per call (got %d)", B);
+  hipStream_t s = (hipStream_t)stream_;
+  const float* y; const int* cs; int N;
+  if (int rc = tdnn_batch_layers(h, feats_dev, offsets_dev, offsets_host, B, ws_, ws_bytes, s, &y, &cs, &N)) return rc;
+  if (transform_t_dev) {
+    // k_tdnn_mono walks the valid frames only: the padding, where a batch has any, is zeroed next to it
+    if (Tshort < Tmax) k_tdnn_zero_padding<<<dim3((Tmax + 255) / 256, M, B), 256, 0, s>>>(offsets_dev, M, Tmax, out_dev);
+    k_tdnn_mono<true><<<(offsets_host[B] + MONO_FT - 1) / MONO_FT, 256, 0, s>>>(y, offsets_dev, cs, B, h->out_dim, N, transform_t_dev, M, out_dev, Tmax);
+  } else {
+    // channel rows per workgroup: whole tiles of 16 rows, split until the launch has about two workgroups per CU (at most 16 ways:
+    // every split repeats the tile's max / sum passes; the values do not depend on the split)
+    const int tiles = (Tmax + POST_FT - 1) / POST_FT;
+    long want = 2l * h->n_cu / ((long)tiles * B);
+    const int split = (int)(want < 1 ? 1 : want > 16 ? 16 : want);
+    const int kper = round_up((h->out_dim + split - 1) / split, 16);
+    k_tdnn_post_padded<<<dim3(tiles, B, (h->out_dim + kper - 1) / kper), 256, 0, s>>>(y, offsets_dev, cs, h->out_dim, N, Tmax, kper, out_dev);
+  }
   FACPPG_HIP_CHECK(hipGetLastError());
   return FACPPG_OK;
 }

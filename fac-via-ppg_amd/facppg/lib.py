@@ -222,6 +222,7 @@ def _declare(lib):
         "facppg_tdnn_batch_workspace_bytes": (sz, [vp, vp, c.c_int]),
         "facppg_tdnn_forward_batch": (c.c_int, [vp, vp, vp, vp, c.c_int, vp, vp, sz, vp]),
         "facppg_tdnn_forward_batch_reduced": (c.c_int, [vp, vp, vp, vp, c.c_int, vp, c.c_int, vp, vp, sz, vp]),
+        "facppg_tdnn_forward_batch_padded": (c.c_int, [vp, vp, vp, vp, c.c_int, vp, c.c_int, c.c_int, vp, vp, sz, vp]),
         "facppg_attention_window_mask": (c.c_int, [vp, c.c_int, c.c_int, c.c_int, c.c_int, vp, vp]),
     }
     for name, (res, args) in sigs.items():

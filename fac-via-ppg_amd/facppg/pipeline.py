@@ -41,9 +41,37 @@ class Synthesizer(object):
         return synthesize(ppgs, self.tacotron, self.waveglow, self.denoiser, sigma=sigma, strength=strength, **kw)
 
     def stream(self, jobs, sigma=0.6, strength=0.005, **kw):
-        """synthesize_stream over this synthesizer's models: batch i+1's acoustic model under batch i's vocoder."""
+        """synthesize_stream over this synthesizer's models: batch i+1's acoustic model under batch i's vocoder.  Jobs that carry
+        ``wavs`` need ``ppg_deps`` (a ppg.DependenciesPPG)."""
         kw.setdefault("vocoder_arithmetic", self.vocoder_arithmetic)
         return synthesize_stream(jobs, self.tacotron, self.waveglow, self.denoiser, sigma=sigma, strength=strength, **kw)
+
+    def _deps(self, ppg_deps):
+        """The PPG dependencies of a call that starts from audio: the caller's, else ppg.DependenciesPPG() read once."""
+        if ppg_deps is not None:
+            return ppg_deps
+        if getattr(self, "ppg_deps", None) is None:
+            from ppg import DependenciesPPG
+            self.ppg_deps = DependenciesPPG()
+        return self.ppg_deps
+
+    def convert(self, wavs, ppg_deps=None, sigma=0.6, strength=0.005, ppgs=None, **kw):
+        """synthesize_wavs over this synthesizer's models: teacher wavs (list of WaveData) -> (waveforms, mel lengths); the PPGs
+        go from the front end to the encoder on the device.  ppg_deps: a ppg.DependenciesPPG (None: the default files, which
+        are read only for a well-formed list of wavs)."""
+        _checked_wav_list(wavs, ppgs, "Synthesizer.convert")
+        kw.setdefault("vocoder_arithmetic", self.vocoder_arithmetic)
+        kw.setdefault("vocoder_stream", self.vocoder_stream)
+        return synthesize_wavs(wavs, self._deps(ppg_deps), self.tacotron, self.waveglow, self.denoiser, sigma=sigma, strength=strength, **kw)
+
+    def convert_file(self, utterance_path, wav_path, fs, sigma=0.6, strength=0.005, ppg_deps=None):
+        """synthesize_file from the teacher wav itself: ``utterance_path`` (a wav) -> ``wav_path`` (float32 [N, 1] at ``fs``,
+        generate_synthesis.py:86-98), the PPGs extracted here and kept on the device."""
+        from common.feat import read_wav_kaldi
+        from scipy.io import wavfile
+        wavs, tout = self.convert([read_wav_kaldi(utterance_path)], ppg_deps, sigma=sigma, strength=strength)
+        wavfile.write(wav_path, fs, wavs[0].astype(np.float32)[:, None])
+        return tout[0]
 
     @staticmethod
     def has_utterance(utterance_path):
@@ -506,13 +534,17 @@ def pad_ppgs(ppgs, device=None):
 
 
 def _acoustic(ppgs, tacotron, seed, dropout_masks, utterance_seeds, step_limits, timer=None, while_decoding=None, consumer=None,
-              decoder_workgroups=None, consumer_arithmetic=None):
+              decoder_workgroups=None, consumer_arithmetic=None, prepared=None):
     """PPG upload + Tacotron2.inference on the current stream -> (mel_post [B, 80, Tout], [Tout_i]).  Blocks the host once,
-    for the decoder's output lengths."""
+    for the decoder's output lengths.  prepared: (x [B, D, Tmax] on the device, lengths) in place of ``ppgs`` -- the front end's
+    own output (ppg.compute_ppg_padded): nothing to upload."""
     dev = next(tacotron.parameters()).device
-    x, lens = pad_ppgs(ppgs, device=dev)
-    if timer is not None:
-        timer.mark("ppg_upload")
+    if prepared is not None:
+        x, lens = prepared
+    else:
+        x, lens = pad_ppgs(ppgs, device=dev)
+        if timer is not None:
+            timer.mark("ppg_upload")
     out = tacotron.inference(x, lengths=lens if len(lens) > 1 else None, dropout_masks=dropout_masks,
                              seed=seed, utterance_seeds=utterance_seeds, step_limits=step_limits,
                              while_decoding=while_decoding, frame_consumer=consumer if len(lens) == 1 else None,
@@ -603,14 +635,24 @@ def synthesize(ppgs, tacotron, waveglow, denoiser=None, sigma=0.6, strength=0.00
     own rules), and a batch of several utterances ignores the keyword and runs as without it -- as a .half() vocoder is
     conditioning-first for one utterance only.  Any other value is refused before a model runs."""
     arithmetic = _checked_arithmetic(vocoder_arithmetic)
-    split_first = _checked_stream(vocoder_stream) is True and arithmetic == ConditioningStream.SPLIT and len(ppgs) == 1
+    _checked_stream(vocoder_stream)
     if timer is not None:
         timer.__init__()
+    return _synthesize(ppgs, None, tacotron, waveglow, denoiser, sigma, strength, seed, dropout_masks, z, return_device, utterance_seeds,
+                       step_limits, timer, arithmetic, vocoder_stream)
+
+
+def _synthesize(ppgs, prepared, tacotron, waveglow, denoiser, sigma, strength, seed, dropout_masks, z, return_device, utterance_seeds,
+                step_limits, timer, arithmetic, vocoder_stream):
+    """synthesize() behind its argument checks, over host PPGs or over a batch the front end left on the device (``prepared``, see
+    _acoustic): the same stages under the same rules either way."""
+    n = len(ppgs) if prepared is None else len(prepared[1])
+    split_first = vocoder_stream is True and arithmetic == ConditioningStream.SPLIT and n == 1
     hop = waveglow.upsample.stride[0]
     with torch.no_grad():
         dev = next(waveglow.parameters()).device
         consumer = None
-        if len(ppgs) == 1 and (arithmetic is None or split_first) and ConditioningStream.usable(tacotron, waveglow):
+        if n == 1 and (arithmetic is None or split_first) and ConditioningStream.usable(tacotron, waveglow):
             consumer = waveglow.__dict__.get("_facppg_cond_stream")
             if consumer is None or consumer.tacotron is not tacotron:
                 consumer = waveglow.__dict__["_facppg_cond_stream"] = ConditioningStream(tacotron, waveglow)
@@ -623,7 +665,7 @@ def synthesize(ppgs, tacotron, waveglow, denoiser=None, sigma=0.6, strength=0.00
                                        # host work under the decoder's milliseconds: the vocoder's weight check (the stream does its own)
                                        while_decoding=lambda: None if (consumer is not None and consumer.active) else
                                        (waveglow.prepare(dev, arithmetic) if arithmetic is not None else waveglow.prepare(dev)),
-                                       consumer=consumer, consumer_arithmetic=arithmetic if split_first else None)
+                                       consumer=consumer, consumer_arithmetic=arithmetic if split_first else None, prepared=prepared)
             audio = _vocode(mel_post, tout, waveglow, denoiser, sigma, strength, seed, z, utterance_seeds, timer, consumer, arithmetic,
                             split_first)
         finally:
@@ -633,6 +675,64 @@ def synthesize(ppgs, tacotron, waveglow, denoiser=None, sigma=0.6, strength=0.00
         return [audio[b, :tout[b] * hop] for b in range(len(tout))], tout
     host = audio.cpu().numpy()
     return [host[b, :tout[b] * hop].copy() for b in range(len(tout))], tout
+
+
+def _checked_wav_list(wavs, ppgs, what):
+    """``wavs`` is a non-empty list, and no ``ppgs`` came with it."""
+    from facppg.lib import FacppgError
+    if ppgs is not None:
+        raise FacppgError("%s: both ppgs and wavs given -- an utterance comes from one of them" % what)
+    if wavs is None or isinstance(wavs, (str, bytes)) or not hasattr(wavs, "__len__") or len(wavs) == 0:
+        raise FacppgError("%s: wavs must be a non-empty list of WaveData (common.feat.read_wav_kaldi)" % what)
+
+
+def _checked_wavs(wavs, deps, tacotron, is_full_ppg, what, ppgs=None):
+    """The argument checks of a call that starts from audio, all on the host and before any device work: ``wavs`` a non-empty list
+    (and no ``ppgs`` next to it), an acoustic model in ``deps`` whose posteriors -- senone or monophone -- have the width the
+    PPG -> mel model was built for.  Returns is_full_ppg (None: whichever width fits the model's n_symbols)."""
+    from facppg.lib import FacppgError
+    from ppg.compute_ppg import _require_model, padded_ppg_dim
+    _checked_wav_list(wavs, ppgs, what)
+    if deps is None:
+        raise FacppgError("%s: no PPG dependencies (ppg.DependenciesPPG) -- wavs need the acoustic model" % what)
+    _require_model(getattr(deps, "nnet", None), what)
+    n_symbols = tacotron._hp["n_symbols"]
+    if is_full_ppg is None:
+        is_full_ppg = padded_ppg_dim(deps, True) == n_symbols or getattr(deps, "monophone_trans", None) is None
+    D = padded_ppg_dim(deps, bool(is_full_ppg))
+    if D != n_symbols:
+        raise FacppgError("%s: the %s PPGs of these dependencies have %d symbols, the PPG -> mel model was built for %d"
+                          % (what, "senone" if is_full_ppg else "monophone", D, n_symbols))
+    return bool(is_full_ppg)
+
+
+def synthesize_wavs(wavs, deps, tacotron, waveglow, denoiser=None, is_full_ppg=None, sigma=0.6, strength=0.005, seed=None,
+                    dropout_masks=None, z=None, return_device=False, utterance_seeds=None, step_limits=None, timer=None,
+                    vocoder_arithmetic=None, vocoder_stream=None, ppgs=None):
+    """synthesize() from teacher audio (the reference's purpose, generate_synthesis.py:86-98): wavs, a list of WaveData on the GPU
+    (common.feat.read_wav_kaldi), go through the batch front end (ppg.compute_ppg_padded: features, acoustic model of ``deps``,
+    a ppg.DependenciesPPG) and their posteriors reach the encoder where the front end left them -- on the device, in the padded
+    channel-major batch it reads; no PPG visits the host.  Every keyword of synthesize() means what it means there, the result
+    is synthesize()'s, and one utterance takes the streamed batch-1 paths under the same rules.
+
+    is_full_ppg: senone posteriors (True) or monophone PPGs through deps.monophone_trans (False); None picks the one whose width
+    is the model's n_symbols.  A width that differs from n_symbols is refused before anything is launched, and so is a call that
+    names ``ppgs`` as well: an utterance comes from one of the two.
+    The monophone PPGs are compute_ppg_batch's bit for bit, so the samples are those of synthesize() over its host copies; the
+    senone posteriors sum their softmax in another order than the row-major output kernels (the same bounds against the
+    oracle), so there the samples are those of synthesize() over host copies of compute_ppg_padded's own values."""
+    from ppg.compute_ppg import compute_ppg_padded
+    is_full_ppg = _checked_wavs(wavs, deps, tacotron, is_full_ppg, "synthesize_wavs", ppgs)
+    arithmetic = _checked_arithmetic(vocoder_arithmetic)
+    _checked_stream(vocoder_stream)
+    if timer is not None:
+        timer.__init__()
+    with torch.no_grad():
+        prepared = compute_ppg_padded(wavs, deps, is_full_ppg=is_full_ppg)
+    if timer is not None:
+        timer.mark("front_end")
+    return _synthesize(None, prepared, tacotron, waveglow, denoiser, sigma, strength, seed, dropout_masks, z, return_device, utterance_seeds,
+                       step_limits, timer, arithmetic, vocoder_stream)
 
 
 _ACOUSTIC_STREAMS = {}
@@ -646,10 +746,18 @@ def _acoustic_stream(device):
 
 
 def synthesize_stream(jobs, tacotron, waveglow, denoiser=None, sigma=0.6, strength=0.005, return_device=True, overlap=True,
-                      acoustic_workgroups=32, vocoder_arithmetic=None):
+                      acoustic_workgroups=32, vocoder_arithmetic=None, ppg_deps=None, is_full_ppg=None):
     """A sequence of batches, software-pipelined: generator of (waveforms, mel lengths), one per job, in order.
 
     jobs: iterable of dicts with ``ppgs`` and optionally ``seed``, ``utterance_seeds``, ``step_limits`` (as synthesize()).
+    A job may carry ``wavs`` (a list of WaveData, as synthesize_wavs() takes it) in place of ``ppgs``: its front end (features,
+    acoustic model of ``ppg_deps``, senone or monophone by ``is_full_ppg`` as in synthesize_wavs()) then runs in front of its
+    acoustic model on the same stream, i.e. under the previous batch's vocoder as well, and its PPGs never leave the device.
+    The samples of a ``wavs`` job are bit for bit its WaveData, as read_wav_kaldi leaves them: complete before the job is handed over.
+    ``wavs`` may also be a callable that returns that list.  It is called when the job's acoustic model is about to be enqueued,
+    with the acoustic stream current: a caller that reads its wavs there (read_wav_kaldi uploads from pageable memory, a copy
+    the host waits for behind everything queued on the current stream) waits for an idle stream and not for the previous batch's
+    vocoder, and holds one batch of audio at a time.  script.synthesize_corpus --device_ppgs reads its batches this way.
     The acoustic model of batch i+1 (PPG upload, encoder, the latency-bound autoregressive decoder, postnet -- a few
     percent of the chip for ~25 ms) runs on its own HIP stream UNDER the vocoder of batch i (MFMA-bound, ~120 ms for 16
     utterances) instead of in front of it.  The host enqueues vocoder i first, then walks through acoustic i+1, whose one
@@ -672,10 +780,24 @@ def synthesize_stream(jobs, tacotron, waveglow, denoiser=None, sigma=0.6, streng
 
     def acoustic(job):
         with torch.no_grad(), torch.cuda.stream(side):
-            # (the inputs are host arrays: nothing on the caller's stream to wait for -- in particular not the previous vocoder)
+            # (the inputs are host arrays, or wavs that are complete: nothing on the caller's stream to wait for -- in particular
+            #  not the previous vocoder)
             bound = tacotron.decoder_workgroups or (int(acoustic_workgroups or 0) if overlap else 0)
-            mel_post, tout = _acoustic(job["ppgs"], tacotron, job.get("seed"), None, job.get("utterance_seeds"), job.get("step_limits"),
-                                       decoder_workgroups=bound)
+            prepared = None
+            wavs = job.get("wavs")
+            if wavs is not None:
+                from ppg.compute_ppg import compute_ppg_padded
+                if callable(wavs):
+                    # read here, with the acoustic stream current: read_wav_kaldi's upload comes from pageable memory and waits for
+                    # the stream it is queued on -- this one, which is idle, and not the caller's, where the previous vocoder runs
+                    wavs = wavs()
+                full = _checked_wavs(wavs, ppg_deps, tacotron, is_full_ppg, "synthesize_stream", job.get("ppgs"))
+                for w in wavs:
+                    if torch.is_tensor(w.data()) and w.data().is_cuda:
+                        w.data().record_stream(side)
+                prepared = compute_ppg_padded(wavs, ppg_deps, is_full_ppg=full)
+            mel_post, tout = _acoustic(job.get("ppgs"), tacotron, job.get("seed"), None, job.get("utterance_seeds"), job.get("step_limits"),
+                                       decoder_workgroups=bound, prepared=prepared)
             done = torch.cuda.Event()
             done.record(side)
         mel_post.record_stream(main)

@@ -13,6 +13,9 @@
                            the same chain for a LIST of utterances in one pass: the utterances are laid end to end, every
                            TDNN layer is one GEMM over all of them (facppg_tdnn_forward_batch), and the monophone
                            reduction is fused into the output kernel (facppg_tdnn_forward_batch_reduced)
+  compute_ppg_padded       the batch chain again, the posteriors left on the device as the padded channel-major batch
+                           [B, D, Tmax] that Tacotron2.inference reads (facppg_tdnn_forward_batch_padded): wav in, wav out
+                           without the PPGs visiting the host (facppg.pipeline.synthesize_wavs)
 
 Matrices are float32 GPU tensors; file paths default to ``<repo data dir>/...`` like the reference's module constants and
 can be overridden (FACPPG_DATA_DIR, or the constructor arguments)."""
@@ -195,7 +198,7 @@ def compute_feat_for_nnet_internal(wav, lda, **kwargs):
     return feat.cmn_splice_transform(mfccs, options["left_context"], options["right_context"], lda)
 
 
-def _feat_for_nnet_flat(wavs, lda, **kwargs):
+def _feat_for_nnet_flat(wavs, lda, keep_tables=False, **kwargs):
     options = {"is_use_energy": False, "is_downsample": True, "frame_shift": 10, "is_snip_edges": False, "left_context": 3,
                "right_context": 3}
     for key, val in kwargs.items():
@@ -208,7 +211,7 @@ def _feat_for_nnet_flat(wavs, lda, **kwargs):
     mfcc_opts.frame_opts.allow_downsample = options["is_downsample"]
     mfcc_opts.frame_opts.frame_shift_ms = options["frame_shift"]
     mfcc_opts.frame_opts.snip_edges = options["is_snip_edges"]
-    mfccs, frames = feat.compute_mfcc_feats_batch(wavs, mfcc_opts)
+    mfccs, frames = feat.compute_mfcc_feats_batch(wavs, mfcc_opts, keep_tables=keep_tables)
     return feat.cmn_splice_transform_batch(mfccs, frames, options["left_context"], options["right_context"], lda), frames
 
 
@@ -232,6 +235,76 @@ def compute_ppg_batch(wavs, deps, is_full_ppg=True, shift=10):
     if nnet3.plan_layers(deps.nnet)[1] != "softmax":      # the fused kernel reduces posteriors: other outputs go the long way
         return [reduce_ppg_dim(p, deps.monophone_trans) for p in _split(_full_ppg_flat(deps.nnet, flat, frames), frames)]
     return _split(_full_ppg_flat(deps.nnet, flat, frames, deps.monophone_trans), frames)
+
+
+def padded_ppg_dim(deps, is_full_ppg):
+    """Channels of compute_ppg_padded's result: the model's senones, or the rows of the pdf -> monophone matrix.  Raises
+    compute_ppg_padded's refusals (host work only)."""
+    _require_model(deps.nnet, "compute_ppg_padded")
+    kept = getattr(deps.nnet, "_facppg_output", None)      # (planning the layers folds every weight matrix: milliseconds of host time)
+    if kept is None:
+        layers, final = nnet3.plan_layers(deps.nnet)
+        kept = deps.nnet._facppg_output = (final, int(layers[-1]["W"].shape[0]))
+    final, out_dim = kept
+    if not is_full_ppg and deps.monophone_trans is None:
+        raise _lib.FacppgError("compute_ppg_padded: monophone PPGs need the pdf -> monophone matrix (data/feats/reduce_dim.mat)")
+    if final != "softmax":
+        raise _lib.FacppgError("compute_ppg_padded: the padded layout holds posteriors: the model's output must be a softmax (it is %s)" % final)
+    return out_dim if is_full_ppg else int(deps.monophone_trans.shape[0])
+
+
+def _on_device(deps, name, dev, transposed=False):
+    """deps.<name> as a float32 matrix on ``dev`` (transposed: [K, d], what the output kernel reads), kept with the dependencies:
+    an upload from pageable memory waits for the stream."""
+    cache = deps.__dict__.setdefault("_facppg_on_device", {})
+    src = getattr(deps, name)
+    hit = cache.get((name, dev))
+    if hit is None or hit[0] is not src:
+        t = torch.as_tensor(src).to(dev).float()
+        hit = cache[(name, dev)] = (src, t.t().contiguous() if transposed else t.contiguous())
+    return hit[1]
+
+
+def compute_ppg_padded(wavs, deps, is_full_ppg=True, shift=10):
+    """compute_ppg_batch for a consumer on the device: list of WaveData -> (x [B, D, Tmax] float32 on the GPU, lengths [B] on
+    the host), the batch Tacotron2.inference reads -- channel-major, frames contiguous, exactly 0 behind each utterance's
+    T_b frames (facppg_tdnn_forward_batch_padded writes every element: nothing is zeroed here).  D = the model's senones, or
+    with ``is_full_ppg=False`` the monophone classes of ``deps.monophone_trans`` (bit for bit compute_ppg_batch's values).  The
+    feature pass is compute_ppg_batch's; the frame counts come from the sample counts on the host: the call copies nothing
+    back from the device and does not wait for it (from the second call on a device on: the first one packs the model and
+    uploads the feature tables and matrices, which stay).  The model's output must be a softmax.
+
+    Kept between calls, tables and never results: the model's output kind and width (``nnet._facppg_output``, next to its packed
+    handle and like it for the life of the model object), the device copies of ``deps.lda`` / ``deps.monophone_trans``
+    (``deps._facppg_on_device``, replaced when the attribute is bound to another object) and one Mfcc per set of option values
+    (common.feat._KEPT_MFCC, for the life of the process: a few hundred KB each).  A model or matrix is a loaded file here; one
+    that is changed IN PLACE after the first call is not seen -- bind a new object, or delete the attribute named above."""
+    K = padded_ppg_dim(deps, is_full_ppg)
+    if not len(wavs):
+        raise ValueError("compute_ppg_padded: no utterance")
+    L = _lib.load()
+    dev = wavs[0].data().device
+    flat, frames = _feat_for_nnet_flat(wavs, _on_device(deps, "lda", dev) if dev.type == "cuda" else deps.lda, keep_tables=True, frame_shift=shift)
+    h = _tdnn_handle(deps.nnet, dev, "compute_ppg_padded")
+    if flat.shape[1] != h.in_dim:
+        raise _lib.FacppgError("compute_ppg_padded: features have %d dims, the model's input node has %d" % (flat.shape[1], h.in_dim))
+    tr_t = None
+    if not is_full_ppg:
+        tr_t = _on_device(deps, "monophone_trans", dev, transposed=True)
+        if tr_t.shape[0] != h.out_dim:
+            raise _lib.FacppgError("reduce_ppg_dim: PPG has %d dims, the transform expects %d" % (h.out_dim, tr_t.shape[0]))
+    B, Tmax = len(frames), max(frames)
+    off = _lib.host_offsets(frames)
+    nbytes = L.facppg_tdnn_batch_workspace_bytes(h.handle, off, B)
+    if nbytes == 0:
+        _lib.check(-1)
+    off_dev = _lib.upload(list(off), torch.int32, dev)
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    x = torch.empty(B, K, Tmax, device=dev)
+    with torch.cuda.device(dev):
+        _lib.check(L.facppg_tdnn_forward_batch_padded(h.handle, _lib.ptr(flat), _lib.ptr(off_dev), off, B, _lib.ptr(tr_t), K if tr_t is not None else 0,
+                                                      Tmax, _lib.ptr(x), _lib.ptr(ws), ws.numel(), _lib.current_stream(dev)))
+    return x, [int(n) for n in frames]
 
 
 def compute_feat_for_nnet(wav_path, lda_path):

@@ -12,7 +12,9 @@ BASELINE.json's north_star.  Utterances are independent, so each rank synthesise
 
 With ``--wav_list`` instead of ``--ppg_list`` the corpus is a list of teacher wavs (the reference's purpose: wav in,
 converted wav out, generate_synthesis.py:60-98): each rank extracts the PPGs of its own shard through the batch front end
-(common.data_utils.get_ppg_batch, ``--batch_size`` utterances per pass) and then synthesises as above.
+(common.data_utils.get_ppg_batch, ``--batch_size`` utterances per pass) and then synthesises as above.  With ``--device_ppgs``
+as well, each batch's wavs are read, converted and dropped in turn: the front end runs in front of the batch's acoustic model
+and hands its PPGs to the encoder on the device, so no PPG is ever held on the host.
 """
 import argparse
 import os
@@ -39,6 +41,10 @@ def parse(argv=None):
     ap.add_argument('--nnet_path', default=None, help='nnet3 acoustic model for --wav_list (default: data/am/final.raw)')
     ap.add_argument('--feats_dir', default=None, help='directory of final.mat, reduce_dim.mat and splice_opts for --wav_list '
                                                       '(default: data/feats)')
+    ap.add_argument('--device_ppgs', action='store_true',
+                    help="with --wav_list: read, convert and drop each batch's wavs in turn -- the front end of a batch runs in front of "
+                         "its acoustic model and its PPGs go to the encoder on the device (facppg.pipeline.synthesize_stream's wavs "
+                         "jobs): no PPG is ever held on the host (without the flag: all of a rank's shard, 4.6 MB per 2 s of senone PPG)")
     ap.add_argument('--output_dir', required=True)
     ap.add_argument('--batch_size', type=int, default=64,
                     help='utterances per synthesis batch; the latency-bound decoder costs the same for 16 or 96 utterances, so larger '
@@ -62,7 +68,10 @@ def parse(argv=None):
     ap.add_argument('--hparams', default='',
                     help='comma separated "name=value" overrides of create_hparams_stage (train_ppg2mel.py:291-292), '
                          'e.g. n_symbols=40 for monophone PPGs (data_utils.py:253-258)')
-    return ap.parse_args(argv)
+    args = ap.parse_args(argv)
+    if args.device_ppgs and not args.wav_list:
+        ap.error("--device_ppgs goes with --wav_list: PPGs read with --ppg_list are on the host already")
+    return args
 
 
 def parse_hparams(text):
@@ -92,14 +101,19 @@ def wav_ppg_lengths(paths):
     return lengths
 
 
+def ppg_dependencies(args):
+    """The acoustic model and feature files of --wav_list (--nnet_path, --feats_dir)."""
+    from ppg import compute_ppg
+    feats_dir = args.feats_dir or os.path.dirname(compute_ppg.LDA_PATH)
+    return compute_ppg.DependenciesPPG(nnet_path=args.nnet_path or compute_ppg.NNET_PATH, lda_path=os.path.join(feats_dir, "final.mat"),
+                                       reduce_dim_path=os.path.join(feats_dir, "reduce_dim.mat"),
+                                       splice_opts_path=os.path.join(feats_dir, "splice_opts"))
+
+
 def extract_shard_ppgs(paths, mine, lengths, args, hparams):
     """{global id: PPG} of this rank's utterances, extracted ``args.batch_size`` at a time in batches of similar length."""
     from common.data_utils import get_ppg_batch
-    from ppg import compute_ppg
-    feats_dir = args.feats_dir or os.path.dirname(compute_ppg.LDA_PATH)
-    deps = compute_ppg.DependenciesPPG(nnet_path=args.nnet_path or compute_ppg.NNET_PATH, lda_path=os.path.join(feats_dir, "final.mat"),
-                                       reduce_dim_path=os.path.join(feats_dir, "reduce_dim.mat"),
-                                       splice_opts_path=os.path.join(feats_dir, "splice_opts"))
+    deps = ppg_dependencies(args)
     ppgs = {}
     for batch in shard.batches(mine, lengths, args.batch_size):
         for i, p in zip(batch, get_ppg_batch([paths[i] for i in batch], deps, is_full_ppg=hparams.is_full_ppg)):
@@ -107,14 +121,28 @@ def extract_shard_ppgs(paths, mine, lengths, args, hparams):
     return ppgs
 
 
-def synthesize_shard(synthesizer, ppgs, lengths, rank, world, args):
-    """This rank's utterances, longest first, in batches of similar length.  Returns (waveforms, global ids)."""
+def synthesize_shard(synthesizer, ppgs, lengths, rank, world, args, wav_paths=None, ppg_deps=None, is_full_ppg=None):
+    """This rank's utterances, longest first, in batches of similar length.  Returns (waveforms, global ids).
+    wav_paths (--device_ppgs) in place of ``ppgs``: every job carries the wavs of its batch, read when its acoustic model is
+    enqueued -- the same batches extract_shard_ppgs forms, so the front end sees the same column space with and without the flag."""
     mine = shard.partition(lengths, world)[rank]
     batches = list(shard.batches(mine, lengths, args.batch_size))
-    jobs = ({"ppgs": [np.asarray(ppgs[i]) for i in batch], "utterance_seeds": [args.seed + 2 * i for i in batch],
-             "step_limits": [lengths[i] for i in batch] if args.limit_steps_to_input else None} for batch in batches)
+
+    def source(batch):
+        if wav_paths is None:
+            return {"ppgs": [np.asarray(ppgs[i]) for i in batch]}
+        from common.feat import read_wav_kaldi
+        # a callable: the stream reads the batch on its acoustic stream, where the upload does not wait for the vocoder in front
+        return {"wavs": lambda: [read_wav_kaldi(wav_paths[i]) for i in batch]}
+    jobs = (dict(source(batch), utterance_seeds=[args.seed + 2 * i for i in batch],
+                 step_limits=[lengths[i] for i in batch] if args.limit_steps_to_input else None) for batch in batches)
     wavs, ids = [], []
-    if hasattr(synthesizer, "stream"):      # software-pipelined: batch i+1's acoustic model runs under batch i's vocoder
+    if wav_paths is not None:
+        if not hasattr(synthesizer, "stream"):
+            raise ValueError("--device_ppgs needs a synthesizer with stream() (facppg.pipeline.Synthesizer)")
+        results = synthesizer.stream(jobs, sigma=args.sigma, strength=args.denoiser_strength, return_device=True,
+                                     overlap=not getattr(args, "no_overlap", False), ppg_deps=ppg_deps, is_full_ppg=is_full_ppg)
+    elif hasattr(synthesizer, "stream"):      # software-pipelined: batch i+1's acoustic model runs under batch i's vocoder
         results = synthesizer.stream(jobs, sigma=args.sigma, strength=args.denoiser_strength, return_device=True,
                                      overlap=not getattr(args, "no_overlap", False))
     else:
@@ -164,7 +192,7 @@ def main(argv=None, synthesizer=None):
         if args.wav_list:
             paths = load_filepaths(args.wav_list)
             lengths = wav_ppg_lengths(paths)
-            ppgs = extract_shard_ppgs(paths, shard.partition(lengths, world)[rank], lengths, args, hparams)
+            ppgs = None if args.device_ppgs else extract_shard_ppgs(paths, shard.partition(lengths, world)[rank], lengths, args, hparams)
         else:
             paths = load_filepaths(args.ppg_list)
             ppgs = [np.load(p, mmap_mode="r") for p in paths]
@@ -173,7 +201,11 @@ def main(argv=None, synthesizer=None):
             from facppg.pipeline import Synthesizer
             synthesizer = Synthesizer(args.ppg2mel_model, args.waveglow_model, hparams=hparams,
                                       vocoder_arithmetic=args.vocoder_arithmetic)
-        wavs, ids = synthesize_shard(synthesizer, ppgs, lengths, rank, world, args)
+        if args.device_ppgs:
+            wavs, ids = synthesize_shard(synthesizer, None, lengths, rank, world, args, wav_paths=paths, ppg_deps=ppg_dependencies(args),
+                                         is_full_ppg=hparams.is_full_ppg)
+        else:
+            wavs, ids = synthesize_shard(synthesizer, ppgs, lengths, rank, world, args)
         gathered = collect(wavs, ids, world)
         if rank == 0:
             assert sorted(gathered) == list(range(len(paths))), "an utterance was lost or duplicated in the gather"

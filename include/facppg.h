@@ -847,6 +847,18 @@ int facppg_tdnn_forward_batch(facppg_tdnn* h, const float* feats_dev, const int3
 int facppg_tdnn_forward_batch_reduced(facppg_tdnn* h, const float* feats_dev, const int32_t* offsets_dev,
                                       const int32_t* offsets_host, int B, const float* transform_t_dev, int M,
                                       float* out_dev, void* workspace_dev, size_t ws_bytes, void* stream);
+/* The posteriors in the layout the encoder reads (facppg_taco_encode's ppg_dev [B][n_symbols][Tin]): out_dev [B][K][Tmax],
+ * out[b][k][t] = posterior k of frame t of utterance b, exactly 0.0f for T_b <= t < Tmax; the call writes every element.
+ * transform_t_dev NULL: K = out_dim, the senone posteriors of compute_full_ppg (compute_ppg.py:42-70) -- the softmax runs
+ * across the channel rows of the logits' own channel-major layout, in a fixed order, and a frame's values depend on its own
+ * logit column alone (not on B, Tmax, or its neighbours).  transform_t_dev [out_dim][M], M <= 64: K = M, the monophone PPGs
+ * of reduce_ppg_dim (compute_ppg.py:73-94), bit for bit facppg_tdnn_forward_batch_reduced's values.  The layers up to the
+ * logits are facppg_tdnn_forward_batch's.  Workspace: facppg_tdnn_batch_workspace_bytes.  Refused before any launch:
+ * B < 1, a NULL pointer, M out of range with a transform, Tmax < max T_b (FACPPG_EINVAL); a model whose output is not a
+ * softmax (FACPPG_EUNSUPPORTED); a short workspace (FACPPG_EWORKSPACE). */
+int facppg_tdnn_forward_batch_padded(facppg_tdnn* h, const float* feats_dev, const int32_t* offsets_dev,
+                                     const int32_t* offsets_host, int B, const float* transform_t_dev, int M, int Tmax,
+                                     float* out_dev, void* workspace_dev, size_t ws_bytes, void* stream);
 
 #ifdef __cplusplus
 }
