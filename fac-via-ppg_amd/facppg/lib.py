@@ -224,6 +224,9 @@ def _declare(lib):
         "facppg_tdnn_forward_batch_reduced": (c.c_int, [vp, vp, vp, vp, c.c_int, vp, c.c_int, vp, vp, sz, vp]),
         "facppg_tdnn_forward_batch_padded": (c.c_int, [vp, vp, vp, vp, c.c_int, vp, c.c_int, c.c_int, vp, vp, sz, vp]),
         "facppg_attention_window_mask": (c.c_int, [vp, c.c_int, c.c_int, c.c_int, c.c_int, vp, vp]),
+        "facppg_ppg_pause_flags": (c.c_int, [vp, vp, c.c_int, c.c_int, c.c_int, vp, vp, c.c_int, f32, vp, vp]),
+        "facppg_ppg_gather_segments": (c.c_int, [vp, c.c_int, c.c_int, c.c_int, vp, vp, c.c_int, c.c_int, vp, vp]),
+        "facppg_join_segments": (c.c_int, [vp, c.c_int, vp, vp, c.c_int, c.c_int, vp, vp]),
     }
     for name, (res, args) in sigs.items():
         fn = getattr(lib, name)      # AttributeError here = header/library mismatch

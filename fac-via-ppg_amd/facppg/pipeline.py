@@ -73,6 +73,24 @@ class Synthesizer(object):
         wavfile.write(wav_path, fs, wavs[0].astype(np.float32)[:, None])
         return tout[0]
 
+    def convert_long(self, wavs, ppg_deps=None, **kw):
+        """synthesize_long_wavs over this synthesizer's models: teacher recordings of any length (list of WaveData) ->
+        (waveforms, segment tables), cut at their pauses, converted in batches and joined on the device.  Keywords and defaults
+        are synthesize_long_wavs's (the vocoder arithmetic defaults to the synthesizer's); ppg_deps as in convert()."""
+        _checked_wav_list(wavs, None, "Synthesizer.convert_long")
+        kw.setdefault("vocoder_arithmetic", self.vocoder_arithmetic)
+        return synthesize_long_wavs(wavs, self._deps(ppg_deps), self.tacotron, self.waveglow, self.denoiser, **kw)
+
+    def convert_long_file(self, utterance_path, wav_path, fs, **kw):
+        """convert_file for a recording of any length (convert_file itself stops at max_decoder_steps frames, as the reference
+        does): ``utterance_path`` (a wav) -> ``wav_path`` (float32 [N, 1] at ``fs``).  Returns the recording's segment table."""
+        from common.feat import read_wav_kaldi
+        from scipy.io import wavfile
+        kw["return_device"] = False
+        wavs, tables = self.convert_long([read_wav_kaldi(utterance_path)], **kw)
+        wavfile.write(wav_path, fs, wavs[0].astype(np.float32)[:, None])
+        return tables[0]
+
     @staticmethod
     def has_utterance(utterance_path):
         """The reference checks the teacher wav itself (generate_synthesis.py:89); here a precomputed PPG next to
@@ -735,6 +753,14 @@ def synthesize_wavs(wavs, deps, tacotron, waveglow, denoiser=None, is_full_ppg=N
                        step_limits, timer, arithmetic, vocoder_stream)
 
 
+def _checked_job_source(job):
+    """A synthesize_stream job's utterances come from ONE of ``ppgs``, ``wavs``, ``prepared``."""
+    given = [k for k in ("ppgs", "wavs", "prepared") if job.get(k) is not None]
+    if len(given) > 1:
+        from facppg.lib import FacppgError
+        raise FacppgError("synthesize_stream: both %s given -- a job's utterances come from one of ppgs, wavs, prepared" % " and ".join(given))
+
+
 _ACOUSTIC_STREAMS = {}
 
 
@@ -771,19 +797,33 @@ def synthesize_stream(jobs, tacotron, waveglow, denoiser=None, sigma=0.6, streng
     batch), on 32 CUs the decoder takes 60 instead of 18 ms -- still hidden -- and the vocoder keeps 7/8 of the chip
     (128.3 ms; profiles/r03_experiments.txt).  The slice width that goes with the bound cuts the decoder's LSTM sums
     differently: samples then equal those of synthesize() with the same Tacotron2.decoder_workgroups bit for bit, and those
-    of the unbounded decoder to rounding.  vocoder_arithmetic: as synthesize()."""
+    of the unbounded decoder to rounding.  vocoder_arithmetic: as synthesize().
+
+    A job may also carry ``prepared`` = (x [B, D, Tmax] float32 on the device, lengths) in place of ``ppgs`` or ``wavs``: a padded
+    batch that is on the device already (ppg.compute_ppg_padded's result, a batch of synthesize_long's segments).  It goes to the
+    acoustic model as a ``wavs`` job's front-end result does.  The acoustic stream does not wait for the caller's: whoever
+    produced x on another stream orders the two (synthesize_long does).  A job with more than one of the three keys is refused:
+    when the job is drawn, the first one before anything touches the device."""
     arithmetic = _checked_arithmetic(vocoder_arithmetic)
+    it = iter(jobs)
+    first = next(it, None)
+    if first is None:
+        return
+    _checked_job_source(first)
     dev = next(tacotron.parameters()).device
     hop = waveglow.upsample.stride[0]
     main = torch.cuda.current_stream(dev)
     side = _acoustic_stream(dev) if overlap else main
 
     def acoustic(job):
+        _checked_job_source(job)
         with torch.no_grad(), torch.cuda.stream(side):
             # (the inputs are host arrays, or wavs that are complete: nothing on the caller's stream to wait for -- in particular
             #  not the previous vocoder)
             bound = tacotron.decoder_workgroups or (int(acoustic_workgroups or 0) if overlap else 0)
-            prepared = None
+            prepared = job.get("prepared")
+            if prepared is not None:
+                prepared[0].record_stream(side)
             wavs = job.get("wavs")
             if wavs is not None:
                 from ppg.compute_ppg import compute_ppg_padded
@@ -809,10 +849,6 @@ def synthesize_stream(jobs, tacotron, waveglow, denoiser=None, sigma=0.6, streng
         host = audio.cpu().numpy()
         return [host[b, :tout[b] * hop].copy() for b in range(len(tout))], tout
 
-    it = iter(jobs)
-    first = next(it, None)
-    if first is None:
-        return
     ready = acoustic(first)
     previous_vocoder = None
     while ready is not None:
@@ -836,3 +872,177 @@ def synthesize_stream(jobs, tacotron, waveglow, denoiser=None, sigma=0.6, streng
             ready = None
         previous_vocoder = vocoder_done
         yield finish(audio, tout)
+
+
+def _checked_long(tacotron, D, what, pause_rows, max_frames, min_frames, min_pause, pause_threshold, seam_fade, batch_frames, vocoder_arithmetic):
+    """The argument checks of a long-form call, all on the host and before any device work -> the call's settings."""
+    from facppg import longform
+    from facppg.lib import FacppgError
+    arithmetic = _checked_arithmetic(vocoder_arithmetic)
+    longform.check_plan_args(max_frames, min_frames, min_pause, what)
+    fade = int(seam_fade) if isinstance(seam_fade, (int, np.integer)) and not isinstance(seam_fade, bool) else -1
+    if fade < 0 or fade > 4096 or fade & (fade - 1):
+        raise FacppgError("%s: seam_fade=%r: expected 0 or a power of two up to 4096 (samples; the gains are then exact)" % (what, seam_fade))
+    if pause_rows is None:
+        if D != 40:
+            raise FacppgError("%s: pause_rows is needed for PPGs of %d symbols (only the 40 monophone classes have a known pause row, 39 = sil)"
+                              % (what, D))
+        pause_rows = [39]
+    rows = [int(r) for r in pause_rows]
+    if not rows or min(rows) < 0 or max(rows) >= D:
+        raise FacppgError("%s: pause_rows must be at least one row in [0, %d) (got %r)" % (what, D, list(pause_rows)))
+    if not 0.0 < float(pause_threshold) < float(len(rows)):
+        raise FacppgError("%s: pause_threshold=%r is outside (0, %d), the range of a sum of %d posteriors" % (what, pause_threshold, len(rows), len(rows)))
+    batch_frames = 16 * int(max_frames) if batch_frames is None else int(batch_frames)
+    if batch_frames < 1:
+        raise FacppgError("%s: batch_frames must be at least 1 (got %d)" % (what, batch_frames))
+    cap = int(tacotron.decoder.max_decoder_steps)
+    if int(max_frames) > cap:
+        raise FacppgError("%s: max_frames=%d is above the model's max_decoder_steps (%d): such a segment would be cut off" % (what, max_frames, cap))
+    return dict(arithmetic=arithmetic, rows=rows, max_frames=int(max_frames), min_frames=int(min_frames), min_pause=int(min_pause),
+                threshold=float(pause_threshold), fade=fade, batch_frames=batch_frames)
+
+
+def pause_flags(x, lengths, rows, threshold):
+    """facppg_ppg_pause_flags on the current stream: x [B, D, Tmax] fp32 on the device -> uint8 [B, Tmax] on the device, 1 where
+    the frame is inside its recording and its ``rows`` (added in that order in fp32) hold more than ``threshold``."""
+    from facppg import lib as _lib
+    L = _lib.load()
+    _lib.require_cuda(x, "pause_flags: x")
+    dev = x.device
+    B, D, Tmax = x.shape
+    flags = torch.empty(B, Tmax, dtype=torch.uint8, device=dev)
+    # (both tables are held until the launch is enqueued: a device tensor that is dropped goes back to the allocator at once, and
+    #  the next upload would land in its place)
+    lens_dev = _lib.upload([int(n) for n in lengths], torch.int32, dev)
+    rows_dev = _lib.upload([int(r) for r in rows], torch.int32, dev)
+    with torch.cuda.device(dev):
+        _lib.check(L.facppg_ppg_pause_flags(_lib.ptr(x), _lib.ptr(lens_dev), B, D, Tmax, _lib.ptr(rows_dev), _lib.offsets_array(rows), len(rows),
+                                            float(threshold), _lib.ptr(flags), _lib.current_stream(dev)))
+    return flags
+
+
+def _synthesize_long(x, lens, cfg, tacotron, waveglow, denoiser, seed, limit_to_input, sigma, strength, return_device, overlap,
+                     acoustic_workgroups):
+    """synthesize_long() behind its argument checks, over the padded device batch (x [B, D, Tmax], lens)."""
+    from facppg import lib as _lib
+    from facppg import longform
+    L = _lib.load()
+    _lib.require_cuda(x, "synthesize_long: the PPG batch")
+    dev = x.device
+    x = x.float().contiguous()
+    B, D, Tmax = x.shape
+    hop = waveglow.upsample.stride[0]
+    with torch.no_grad(), torch.cuda.device(dev):
+        st = _lib.current_stream(dev)
+        flags = pause_flags(x, lens, cfg["rows"], cfg["threshold"]).cpu().numpy()      # one byte per frame: the call's only added host wait
+        plans = [longform.plan_segments(flags[b, :lens[b]], cfg["max_frames"], cfg["min_frames"], cfg["min_pause"]) for b in range(B)]
+        pooled = [(b, s, n) for b, plan in enumerate(plans) for s, n in plan]
+        jobs = []
+        for i, j in longform.group_segments([p[2] for p in pooled], cfg["batch_frames"]):
+            flat = [v for p in pooled[i:j] for v in p]
+            frames = [p[2] for p in pooled[i:j]]
+            y = torch.empty(j - i, D, max(frames), dtype=torch.float32, device=dev)
+            table = _lib.upload(flat, torch.int32, dev)
+            _lib.check(L.facppg_ppg_gather_segments(_lib.ptr(x), B, D, Tmax, _lib.ptr(table), _lib.offsets_array(flat), j - i, max(frames),
+                                                    _lib.ptr(y), st))
+            job = dict(prepared=(y, frames), utterance_seeds=[seed + 2 * k for k in range(i, j)])
+            if limit_to_input:
+                job["step_limits"] = frames
+            jobs.append(job)
+        if overlap:           # the acoustic models run on a stream of their own, which has to see the gathers above
+            _acoustic_stream(dev).wait_stream(torch.cuda.current_stream(dev))
+        audio, tout = [], []
+        for a, t in synthesize_stream(jobs, tacotron, waveglow, denoiser, sigma=sigma, strength=strength, return_device=True, overlap=overlap,
+                                      acoustic_workgroups=acoustic_workgroups, vocoder_arithmetic=cfg["arithmetic"]):
+            audio += a
+            tout += t
+        waveforms, tables, k = [], [], 0
+        for plan in plans:
+            S = len(plan)
+            n = [tout[k + s] * hop for s in range(S)]
+            stacked = torch.nn.utils.rnn.pad_sequence(audio[k:k + S], batch_first=True).contiguous()
+            out = torch.empty(sum(n), dtype=torch.float32, device=dev)
+            n_dev = _lib.upload(n, torch.int32, dev)
+            _lib.check(L.facppg_join_segments(_lib.ptr(stacked), stacked.shape[1], _lib.ptr(n_dev), _lib.offsets_array(n), S, cfg["fade"],
+                                              _lib.ptr(out), st))
+            waveforms.append(out)
+            tables.append([(s0, fr, tout[k + s]) for s, (s0, fr) in enumerate(plan)])
+            k += S
+    if not return_device:
+        waveforms = [w.cpu().numpy() for w in waveforms]
+    return waveforms, tables
+
+
+def synthesize_long(ppgs, tacotron, waveglow, denoiser=None, *, pause_rows=None, max_frames=600, min_frames=150, min_pause=8,
+                    pause_threshold=0.5, seam_fade=64, batch_frames=None, seed=0, limit_to_input=False, sigma=0.6, strength=0.005,
+                    return_device=False, vocoder_arithmetic=None, overlap=True, acoustic_workgroups=32):
+    """Recordings of any length -> (waveforms, segment tables).  Tacotron2.inference decodes at most max_decoder_steps frames
+    (about ten seconds) and cuts a longer recording off, as the reference does (model.py:527); here a recording is cut at its
+    pauses where the posteriors already lie, the pieces are converted as padded batches under synthesize_stream, and their audio
+    is joined on the device.  One byte per frame visits the host.
+
+    ppgs: a list of recordings, host [T, D] arrays, or ONE device batch (x [B, D, Tmax], lengths) as ppg.compute_ppg_padded
+    leaves it.  The PPG of the whole recording is computed before it is cut, so the acoustic model's context crosses the cuts.
+    pause_rows: the PPG rows that mean "pause"; their fp32 sum, in this order, above ``pause_threshold`` flags a frame
+    (facppg_ppg_pause_flags).  None: [39], the monophone PPG's ``sil``, when D == 40; refused otherwise.
+    max_frames / min_frames / min_pause: facppg.longform.plan_segments' (no segment longer than max_frames, none shorter than
+    min_frames once there are several, pauses of at least min_pause frames).  max_frames above the model's max_decoder_steps is
+    refused.  The defaults are policy (6 s segments, 80 ms pauses, 4 ms fades), not measurements.
+    batch_frames: the pooled segments -- (recording, segment) order -- are grouped greedily, a group the longest run of
+    consecutive segments with count * longest <= batch_frames (None: 16 * max_frames) and at least one; each group is gathered
+    into a fresh [S, D, Lmax] batch (facppg_ppg_gather_segments) and runs as one ``prepared`` job of synthesize_stream
+    (``overlap`` / ``acoustic_workgroups`` / ``vocoder_arithmetic`` are its keywords).
+    seed: segment j in pooled order gets utterance seed ``seed + 2 * j``; the vocoder draws its noise from that seed + 1, so the
+    stride keeps the streams apart.  limit_to_input: each segment's frame count is its step limit (the reference's is_clip idea);
+    otherwise the gate ends it.
+    seam_fade: samples of linear fade on either side of every interior seam (facppg_join_segments: 0 or a power of two up to
+    4096, shortened for short segments); lengths are additive, nothing overlaps.
+    The table of a recording lists (start, frames, mel_length) per segment; its waveform has hop * sum(mel_length) samples.
+    Every argument check runs on the host before anything touches a device."""
+    from facppg.lib import FacppgError
+    what = "synthesize_long"
+    batch = isinstance(ppgs, tuple) and len(ppgs) == 2 and torch.is_tensor(ppgs[0])
+    if batch:
+        x, lens = ppgs[0], [int(n) for n in ppgs[1]]
+        if x.dim() != 3 or len(lens) != x.shape[0] or not lens or min(lens) < 1 or max(lens) > x.shape[2]:
+            raise FacppgError("%s: a device batch is (x [B, D, Tmax], B lengths in [1, Tmax])" % what)
+        D = int(x.shape[1])
+    else:
+        if ppgs is None or not hasattr(ppgs, "__len__") or len(ppgs) == 0:
+            raise FacppgError("%s: ppgs must be a non-empty list of [T, D] arrays, or one device batch (x, lengths)" % what)
+        D = int(ppgs[0].shape[1])
+    cfg = _checked_long(tacotron, D, what, pause_rows, max_frames, min_frames, min_pause, pause_threshold, seam_fade, batch_frames,
+                        vocoder_arithmetic)
+    if not batch:
+        x, lens = pad_ppgs(ppgs, device=next(tacotron.parameters()).device)
+    return _synthesize_long(x, lens, cfg, tacotron, waveglow, denoiser, int(seed), limit_to_input, sigma, strength, return_device, overlap,
+                            acoustic_workgroups)
+
+
+def synthesize_long_wavs(wavs, deps, tacotron, waveglow, denoiser=None, is_full_ppg=None, *, pause_rows=None, max_frames=600, min_frames=150,
+                         min_pause=8, pause_threshold=0.5, seam_fade=64, batch_frames=None, seed=0, limit_to_input=False, sigma=0.6,
+                         strength=0.005, return_device=False, vocoder_arithmetic=None, overlap=True, acoustic_workgroups=32):
+    """synthesize_long() from teacher audio: wavs (a list of WaveData, whole recordings) go through ppg.compute_ppg_padded once and
+    its device batch is cut, converted and joined as above; no posterior visits the host.  is_full_ppg as in synthesize_wavs().
+    pause_rows None: [39] for monophone PPGs; for senone PPGs the senones that ``deps.monophone_trans`` maps to row 39 (its
+    nonzero columns: the same mass), refused when the dependencies have no such map."""
+    from facppg.lib import FacppgError
+    from ppg.compute_ppg import compute_ppg_padded
+    what = "synthesize_long_wavs"
+    is_full_ppg = _checked_wavs(wavs, deps, tacotron, is_full_ppg, what)
+    if pause_rows is None:
+        if not is_full_ppg:
+            pause_rows = [39]
+        else:
+            trans = getattr(deps, "monophone_trans", None)
+            if trans is None or trans.shape[0] <= 39:
+                raise FacppgError("%s: pause_rows is needed for senone PPGs when the dependencies have no pdf -> monophone matrix "
+                                  "(data/feats/reduce_dim.mat) to read the pause senones from" % what)
+            pause_rows = [int(c) for c in torch.nonzero(torch.as_tensor(trans)[39]).flatten()]
+    cfg = _checked_long(tacotron, tacotron._hp["n_symbols"], what, pause_rows, max_frames, min_frames, min_pause, pause_threshold, seam_fade,
+                        batch_frames, vocoder_arithmetic)
+    with torch.no_grad():
+        x, lens = compute_ppg_padded(wavs, deps, is_full_ppg=is_full_ppg)
+    return _synthesize_long(x, lens, cfg, tacotron, waveglow, denoiser, int(seed), limit_to_input, sigma, strength, return_device, overlap,
+                            acoustic_workgroups)

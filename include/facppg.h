@@ -860,6 +860,33 @@ int facppg_tdnn_forward_batch_padded(facppg_tdnn* h, const float* feats_dev, con
                                      const int32_t* offsets_host, int B, const float* transform_t_dev, int M, int Tmax,
                                      float* out_dev, void* workspace_dev, size_t ws_bytes, void* stream);
 
+/* ------------------------------------------------------------------------------------
+ * Long recordings: cut at the pauses, convert the pieces as padded batches, join the audio
+ * (facppg.pipeline.synthesize_long).  The reference has NO counterpart: Tacotron2.inference decodes at most
+ * max_decoder_steps frames and a longer teacher recording is cut off with "Warning! Reached max decoder steps"
+ * (src/common/model.py:527, src/script/generate_synthesis.py:90-93).  PPGs are fp32 in the layout
+ * facppg_tdnn_forward_batch_padded writes and facppg_taco_encode reads: [B][K][Tmax], frames contiguous.  Tables come as a
+ * device copy (read by the kernel) next to a host copy (validated before the launch); every refusal is FACPPG_EINVAL
+ * (more than 65535 recordings / segments in one call: FACPPG_EUNSUPPORTED) and launches nothing.
+ * ---------------------------------------------------------------------------------- */
+/* flags_dev uint8 [B][Tmax]: flags[b][t] = t < lengths[b] && x[b][rows[0]][t] + x[b][rows[1]][t] + ... > threshold -- one fp32
+ * accumulator, the rows in the order given, additions only (a NumPy float32 sum in that order has the same bits).  Every
+ * element of flags is written.  Refused: n_rows < 1, a row outside [0, K), a threshold outside (0, n_rows). */
+int facppg_ppg_pause_flags(const float* x_dev, const int32_t* lengths_dev, int B, int K, int Tmax, const int32_t* rows_dev,
+                           const int32_t* rows_host, int n_rows, float threshold, uint8_t* flags_dev, void* stream);
+/* table int32 [S][3] of (recording b, start, frames); y_dev [S][K][Lmax]: y[s][k][l] = l < frames_s ? x[b_s][k][start_s + l] : 0.
+ * Every element of y is written (zeros behind each segment, as facppg_tdnn_forward_batch_padded pads).  Starts are arbitrary;
+ * the rows of y are written 16 bytes at a time when Lmax % 4 == 0.  Refused: b outside [0, B), start < 0, frames outside
+ * [1, Lmax], start + frames > Tmax. */
+int facppg_ppg_gather_segments(const float* x_dev, int B, int K, int Tmax, const int32_t* table_dev, const int32_t* table_host,
+                               int S, int Lmax, float* y_dev, void* stream);
+/* audio_dev [S][Nmax], n[s] <= Nmax valid samples each -> out_dev [sum n]: the segments laid end to end with a linear fade on
+ * both sides of every INTERIOR seam: gain (2 i + 1) / (2 f_s) over the first f_s samples of segments s > 0, mirrored over the
+ * last f_s of segments s < S - 1, f_s = min(fade, n[s] / 2) rounded down to a power of two (or 0).  fade: 0 or a power of two
+ * up to 4096 (anything else is refused) -- every gain is then exact in fp32.  S = 1 or fade = 0: a copy. */
+int facppg_join_segments(const float* audio_dev, int Nmax, const int32_t* n_dev, const int32_t* n_host, int S, int fade,
+                         float* out_dev, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
