@@ -227,6 +227,8 @@ def _declare(lib):
         "facppg_ppg_pause_flags": (c.c_int, [vp, vp, c.c_int, c.c_int, c.c_int, vp, vp, c.c_int, f32, vp, vp]),
         "facppg_ppg_gather_segments": (c.c_int, [vp, c.c_int, c.c_int, c.c_int, vp, vp, c.c_int, c.c_int, vp, vp]),
         "facppg_join_segments": (c.c_int, [vp, c.c_int, vp, vp, c.c_int, c.c_int, vp, vp]),
+        "facppg_ppg_dtw_workspace_bytes": (sz, [c.c_int, c.c_int, c.c_int, c.c_int, c.c_int]),
+        "facppg_ppg_dtw": (c.c_int, [vp, vp, vp, c.c_int, vp, vp, vp, c.c_int, c.c_int, c.c_int, c.c_int, vp, vp, vp, vp, sz, vp]),
     }
     for name, (res, args) in sigs.items():
         fn = getattr(lib, name)      # AttributeError here = header/library mismatch

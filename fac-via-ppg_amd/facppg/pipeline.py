@@ -64,6 +64,22 @@ class Synthesizer(object):
         kw.setdefault("vocoder_stream", self.vocoder_stream)
         return synthesize_wavs(wavs, self._deps(ppg_deps), self.tacotron, self.waveglow, self.denoiser, sigma=sigma, strength=strength, **kw)
 
+    def convert_scored(self, wavs, ppg_deps=None, score_band=0, **kw):
+        """convert() plus facppg.score.roundtrip of what it made: (waveforms, mel lengths, scores).  The waveforms are convert()'s
+        for the same keywords, bit for bit; the scores are roundtrip(wavs, waveforms, hparams.sampling_rate, ppg_deps,
+        band=score_band) -- the converted audio goes back through the front end next to the teacher's and the two monophone PPGs
+        are aligned on the device.  Dependencies without the pdf -> monophone matrix are refused before anything runs."""
+        from facppg import score
+        _checked_wav_list(wavs, kw.get("ppgs"), "Synthesizer.convert_scored")
+        deps = self._deps(ppg_deps)
+        score.check_roundtrip_deps(deps, "Synthesizer.convert_scored")
+        host = not kw.pop("return_device", False)
+        audio, tout = self.convert(wavs, deps, return_device=True, **kw)
+        scores = score.roundtrip(wavs, audio, self.hparams.sampling_rate, deps, band=score_band)
+        if host:
+            audio = [a.cpu().numpy() for a in audio]
+        return audio, tout, scores
+
     def convert_file(self, utterance_path, wav_path, fs, sigma=0.6, strength=0.005, ppg_deps=None):
         """synthesize_file from the teacher wav itself: ``utterance_path`` (a wav) -> ``wav_path`` (float32 [N, 1] at ``fs``,
         generate_synthesis.py:86-98), the PPGs extracted here and kept on the device."""

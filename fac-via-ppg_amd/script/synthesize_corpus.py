@@ -15,6 +15,10 @@ converted wav out, generate_synthesis.py:60-98): each rank extracts the PPGs of 
 (common.data_utils.get_ppg_batch, ``--batch_size`` utterances per pass) and then synthesises as above.  With ``--device_ppgs``
 as well, each batch's wavs are read, converted and dropped in turn: the front end runs in front of the batch's acoustic model
 and hands its PPGs to the encoder on the device, so no PPG is ever held on the host.
+
+With ``--score_file scores.tsv`` (and ``--wav_list``) every conversion is scored by its PPG round trip (facppg.score.roundtrip:
+the converted audio back through the front end, aligned with the teacher's PPG on the device): each rank scores its own batches
+and rank 0 writes one line per utterance, in list order.  The wavs do not depend on the flag.
 """
 import argparse
 import os
@@ -65,12 +69,23 @@ def parse(argv=None):
     ap.add_argument('--vocoder_arithmetic', choices=('fp32', 'bf16x3'), default=None,
                     help="arithmetic of the vocoder's WaveGlow.infer: fp32 (exact, the default) or bf16x3 (fp32 operands split into two "
                          "bf16 terms on the bf16 MFMA: fp32-class accuracy, fp32 samples out)")
+    ap.add_argument('--score_file', default=None,
+                    help='with --wav_list: score every conversion by its PPG round trip (facppg.score.roundtrip) and write one line per '
+                         'utterance, in list order: path, teacher_frames, roundtrip_frames, distance, agreement, stretch (tab separated, '
+                         'floats as %%.6g)')
+    ap.add_argument('--score_band', type=int, default=0,
+                    help="--score_file: half-width of the alignment's slanted band in frames of the longer side (0: no band; otherwise "
+                         "at least 2)")
     ap.add_argument('--hparams', default='',
                     help='comma separated "name=value" overrides of create_hparams_stage (train_ppg2mel.py:291-292), '
                          'e.g. n_symbols=40 for monophone PPGs (data_utils.py:253-258)')
     args = ap.parse_args(argv)
     if args.device_ppgs and not args.wav_list:
         ap.error("--device_ppgs goes with --wav_list: PPGs read with --ppg_list are on the host already")
+    if args.score_file and not args.wav_list:
+        ap.error("--score_file goes with --wav_list: with --ppg_list there is no teacher audio to compare the conversion with")
+    if args.score_band < 0 or args.score_band == 1:
+        ap.error("--score_band must be 0 (no band) or at least 2 (got %d)" % args.score_band)
     return args
 
 
@@ -153,6 +168,36 @@ def synthesize_shard(synthesizer, ppgs, lengths, rank, world, args, wav_paths=No
     return wavs, ids
 
 
+def score_shard(wavs, ids, paths, lengths, rank, world, args, deps):
+    """{global id: one line of the score file} for this rank's utterances: the teacher wavs of every batch synthesize_shard formed,
+    read again, against that batch's converted audio (still on the device)."""
+    from common.feat import read_wav_kaldi
+    from facppg import score
+    made = dict(zip(ids, wavs))
+    lines = {}
+    for batch in shard.batches(shard.partition(lengths, world)[rank], lengths, args.batch_size):
+        scores = score.roundtrip([read_wav_kaldi(paths[i]) for i in batch], [made[i] for i in batch], FS, deps, band=args.score_band)
+        for b, i in enumerate(batch):
+            lines[i] = score.score_line(paths[i], scores, b)
+    return lines
+
+
+def collect_scores(lines, world):
+    """Rank 0: {global id: line} of every rank; other ranks: None."""
+    if world > 1:
+        every = [None] * world
+        dist.all_gather_object(every, lines)
+        lines = {i: l for part in every for i, l in part.items()}
+    return lines if int(os.environ.get("RANK", "0")) == 0 else None
+
+
+def write_scores(score_file, n, lines):
+    assert sorted(lines) == list(range(n)), "an utterance's score was lost or duplicated in the gather"
+    with open(score_file, "w") as f:
+        for i in range(n):
+            f.write(lines[i] + "\n")
+
+
 def collect(wavs, ids, world):
     """Rank 0: {global id: CPU waveform}; other ranks: None."""
     if world > 1:
@@ -206,9 +251,13 @@ def main(argv=None, synthesizer=None):
                                          is_full_ppg=hparams.is_full_ppg)
         else:
             wavs, ids = synthesize_shard(synthesizer, ppgs, lengths, rank, world, args)
+        if args.score_file:
+            lines = collect_scores(score_shard(wavs, ids, paths, lengths, rank, world, args, ppg_dependencies(args)), world)
         gathered = collect(wavs, ids, world)
         if rank == 0:
             assert sorted(gathered) == list(range(len(paths))), "an utterance was lost or duplicated in the gather"
+            if args.score_file:
+                write_scores(args.score_file, len(paths), lines)
             return write_wavs(args.output_dir, paths, gathered)
         return None
     finally:

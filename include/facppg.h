@@ -887,6 +887,35 @@ int facppg_ppg_gather_segments(const float* x_dev, int B, int K, int Tmax, const
 int facppg_join_segments(const float* audio_dev, int Nmax, const int32_t* n_dev, const int32_t* n_host, int S, int fade,
                          float* out_dev, void* stream);
 
+/* ------------------------------------------------------------------------------------
+ * Round-trip scoring: dynamic time warping of two padded PPG batches (facppg.score.ppg_dtw / roundtrip: the teacher's PPG
+ * against the PPG of the converted audio).  The reference has NO counterpart: generate_synthesis.py:86-98 writes the wav and
+ * never compares it with anything.  a_dev [B][D][Ta_max] and b_dev [B][D][Tb_max], fp32, frames contiguous -- the layout
+ * facppg_tdnn_forward_batch_padded writes; pair p is a[p][:][0 .. la[p]) against b[p][:][0 .. lb[p]), and nothing behind a
+ * length is read (it may hold NaN).  Per pair, with Ta = la[p], Tb = lb[p]:
+ *   per frame      ra[k][i] = sqrt(max(a[k][i], 0)), ca[i] = arg max_k a[k][i] (the lowest k on a tie); rb, cb likewise
+ *   local distance d(i,j) = max(0, 1 - sum_k ra[k][i] rb[k][j]): the squared Hellinger distance of two posteriors; the sum is
+ *                  one fp32 fma chain from 0 with k increasing
+ *   band           m = max(Ta - 1, Tb - 1, 1); (i,j) is admissible iff band == 0 or |i (Tb - 1) - j (Ta - 1)| <= band m, in
+ *                  64-bit integers.  Both corners always are; from band 2 on an admissible path always exists
+ *   recurrence     C(0,0) = d(0,0); else C(i,j) = d(i,j) + min over the admissible predecessors (i-1,j-1), (i-1,j), (i,j-1),
+ *                  tried in that order with a strict <: a tie keeps the earlier one.  fp32 additions
+ *   carried along the chosen predecessor: N(i,j) = N(pred) + 1, N(0,0) = 1; M(i,j) = M(pred) + [ca[i] == cb[j]]
+ *   outputs        cost_dev[p] = C(Ta-1, Tb-1), steps_dev[p] = N(Ta-1, Tb-1), agree_dev[p] = M(Ta-1, Tb-1)   ([B] each)
+ * so there is no back-pointer matrix and no backtrace.  Lengths come as a device copy (read by the kernels) next to a host
+ * copy (validated before the first launch).  Refused, and nothing is launched: a NULL pointer, B, D, Ta_max or Tb_max < 1, a
+ * length outside [1, T*_max], band 1 or band < 0 (FACPPG_EINVAL); D > 256 -- senone posteriors: reduce them to monophone
+ * classes first --, B > 65535 (FACPPG_EUNSUPPORTED); a workspace smaller than facppg_ppg_dtw_workspace_bytes, which holds the
+ * square roots and B (Ta_max + Tb_max - 1) Ta_max distances (FACPPG_EWORKSPACE).  Launches: two frame passes, one tiled
+ * distance kernel over all pairs, and one sweep (one workgroup per pair) per 1024 rows of the longest a; all on ``stream``,
+ * none cooperative, none waits on memory. */
+size_t facppg_ppg_dtw_workspace_bytes(int B, int D, int Ta_max, int Tb_max, int band);
+int facppg_ppg_dtw(const float* a_dev, const int32_t* la_dev, const int32_t* la_host, int Ta_max,
+                   const float* b_dev, const int32_t* lb_dev, const int32_t* lb_host, int Tb_max,
+                   int B, int D, int band,
+                   float* cost_dev, int32_t* steps_dev, int32_t* agree_dev,
+                   void* ws_dev, size_t ws_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
