@@ -12,7 +12,10 @@ takes.
 ``get_ppg_batch`` is ``get_ppg`` for a list of paths: the precomputed-file rule per path, and ONE pass of the batch front
 end (ppg.compute_ppg_batch: the utterances laid end to end through the MFCC, CMN / splice / LDA and TDNN kernels) for the
 paths that have no precomputed file.  ``PPGMelLoader`` (data_utils.py:163-278) is the reference's (PPG, mel) data set on top
-of it, what ``script.train_ppg2mel.finetune`` trains from; F0 features (``is_append_f0``) are not built.
+of it, what ``script.train_ppg2mel.finetune`` trains from.
+
+``append_ppg`` with ``compute_delta_acc_feat``, ``compute_dynamic_matrix``, ``compute_dynamic_vector`` (data_utils.py:62-160) are
+the reference's F0 input columns in float64 NumPy; ``get_f0_batch`` supplies the track (``hparams.is_append_f0``).
 """
 import os
 import pickle
@@ -89,6 +92,91 @@ def get_ppg_batch(wav_paths, deps=None, is_full_ppg=True):
     return out
 
 
+DELTA_WIN = [0, -0.5, 0.0, 0.5, 0]        # data_utils.py:48-52: dx(t) = 0.5 (x(t+1) - x(t-1)), five taps wide
+ACC_WIN = [0.25, 0, -0.5, 0, 0.25]        # ddx(t) = 0.25 (x(t+2) - 2 x(t) + x(t-2))
+
+
+def compute_dynamic_vector(vector, dynamic_win, frame_number):
+    """data_utils.py:62-91: a [T] vector x a window of odd length -> [T, 1] float64, out[i] = sum_w win[w] * x[i + w - half]
+    with the first / last value repeated beyond the ends; the products are added in the order of the window."""
+    vector = np.asarray(vector, dtype=np.float64).reshape(frame_number)
+    half = len(dynamic_win) // 2
+    padded = np.concatenate([np.full(half, vector[0]), vector, np.full(half, vector[frame_number - 1])]) if frame_number else vector
+    out = np.zeros(frame_number)
+    for w, coeff in enumerate(dynamic_win):
+        out += padded[w:w + frame_number] * coeff
+    return out.reshape(frame_number, 1)
+
+
+def compute_dynamic_matrix(data_matrix, dynamic_win):
+    """data_utils.py:94-114: compute_dynamic_vector for every column of a [T, D] matrix -> [T, D] float64."""
+    data_matrix = np.asarray(data_matrix, dtype=np.float64)
+    frame_number, dimension = data_matrix.shape
+    half = len(dynamic_win) // 2
+    if frame_number == 0:
+        return np.zeros((0, dimension))
+    padded = np.concatenate([np.repeat(data_matrix[:1], half, 0), data_matrix, np.repeat(data_matrix[-1:], half, 0)], 0)
+    out = np.zeros((frame_number, dimension))
+    for w, coeff in enumerate(dynamic_win):
+        out += padded[w:w + frame_number] * coeff
+    return out
+
+
+def compute_delta_acc_feat(matrix, is_delta=False, is_acc=False):
+    """data_utils.py:117-139: [T, D] -> [T, D], [T, 2 D] (with the deltas) or [T, 3 D] (and the delta-deltas)."""
+    if not is_delta and is_acc:
+        raise ValueError('To use delta-delta feats you have to also use delta feats.')
+    parts = [matrix]
+    if is_delta:
+        parts.append(compute_dynamic_matrix(matrix, DELTA_WIN))
+    if is_acc:
+        parts.append(compute_dynamic_matrix(matrix, ACC_WIN))
+    return np.concatenate(parts, axis=1) if len(parts) > 1 else matrix
+
+
+def append_ppg(feats, f0):
+    """data_utils.py:142-160: feats [T1, D] and an F0 track [T2] (Hz, 0 = unvoiced) -> [min(T1, T2), D + 3]: the features, then
+    log(f0 + eps) with its delta and delta-delta in float64 (WORLD's tracks are float64; a float32 track is widened first)."""
+    frames = min(feats.shape[0], f0.shape[0])
+    lf0 = np.log(np.asarray(f0[:frames], dtype=np.float64) + np.finfo(float).eps).reshape(frames, 1)
+    return np.concatenate((feats[:frames, :], compute_delta_acc_feat(lf0, True, True)), axis=1)
+
+
+def f0_candidates(wav_path):
+    """Where the precomputed F0 track of ``wav_path`` may live."""
+    return [wav_path + ".f0.npy", os.path.splitext(wav_path)[0] + ".f0.npy"]
+
+
+def get_f0_batch(wav_paths, deps=None):
+    """F0 tracks for a list of wav paths -> list of [T] float32 arrays in Hz, 0 = unvoiced, in the order given.  A precomputed
+    ``<wav>.f0.npy`` / ``<stem>.f0.npy`` wins, as the ``.ppg.npy`` rule does -- that is how WORLD tracks (utterance.py:33-38) get
+    in; the other paths go through ONE pass of the device tracker (ppg.compute_f0_batch), one value per PPG frame.  ``deps`` is
+    accepted for symmetry with get_ppg_batch: the tracker needs no model."""
+    wav_paths = list(wav_paths)
+    out = [None] * len(wav_paths)
+    todo = []
+    for i, path in enumerate(wav_paths):
+        for c in f0_candidates(path):
+            if os.path.isfile(c):
+                f0 = np.load(c)
+                if f0.ndim != 1:
+                    raise ValueError("F0 file %s must hold a [T] array in Hz, got shape %s" % (c, f0.shape))
+                out[i] = f0.astype(np.float32)
+                break
+        else:
+            todo.append(i)
+    if todo:
+        from common import feat
+        from ppg import compute_f0_batch
+        for i in todo:
+            if not os.path.isfile(wav_paths[i]):
+                raise FileNotFoundError("get_f0_batch: neither %s nor a precomputed track (%s)" % (wav_paths[i], " or ".join(f0_candidates(wav_paths[i]))))
+        tracks = compute_f0_batch([feat.read_wav_kaldi(wav_paths[i]) for i in todo])
+        for i, f in zip(todo, tracks):
+            out[i] = f.cpu().numpy()
+    return out
+
+
 class PPGMelLoader(torch.utils.data.Dataset):
     """Loads [ppg, mel] pairs: the reference's data_utils.py:163-278.
 
@@ -102,8 +190,10 @@ class PPGMelLoader(torch.utils.data.Dataset):
                            mel batch stays small); the features do not depend on it beyond fp32 round-off
 
     The PPG side is the senone PPG (``is_full_ppg``) or the monophone PPG, reduced inside the acoustic model's output
-    kernel; the acoustic side is the log-mel of ``audio / max_wav_value``, [T, n_mel].  ``is_append_f0`` raises: the
-    reference reads ``utt.f0``, and nothing on this path computes an F0 track."""
+    kernel; the acoustic side is the log-mel of ``audio / max_wav_value``, [T, n_mel].  With ``is_append_f0`` every PPG becomes
+    ``append_ppg(ppg, f0)`` ([T, n_symbols + 3], data_utils.py:248-256) for either ``is_full_ppg`` setting; the reference reads
+    ``utt.f0`` (WORLD), here the track is ``get_f0_batch``'s: a ``.f0.npy`` file next to the wav, else the device tracker -- the
+    latter only for an utterance whose PPG the front end computes too (``_check_f0_sources``: otherwise NotImplementedError)."""
 
     def __init__(self, data_utterance_paths, hparams, ppg_deps=None, batch_utterances=32):
         self.data_utterance_paths = load_filepaths(data_utterance_paths)
@@ -118,15 +208,14 @@ class PPGMelLoader(torch.utils.data.Dataset):
         self.batch_utterances = int(batch_utterances)
         if self.is_cache_feats and self.load_feats_from_disk:
             raise ValueError('If you are loading feats from the disk, do not rewrite them back!')
-        if self.is_append_f0:
-            raise NotImplementedError("PPGMelLoader: is_append_f0 is not built -- the reference appends utt.f0 "
-                                      "(data_utils.py:142-160, 248-256), and no F0 extraction exists on this path")
         if self.batch_utterances < 1:
             raise ValueError("PPGMelLoader: batch_utterances must be at least 1")
         if ppg_deps is None:
             from ppg import DependenciesPPG
             ppg_deps = DependenciesPPG()
         self.ppg_deps = ppg_deps
+        if self.is_append_f0 and not self.load_feats_from_disk:
+            self._check_f0_sources()
 
         from common import layers
         self.stft = layers.TacotronSTFT(hparams.filter_length, hparams.hop_length, hparams.win_length, hparams.n_acoustic_feat_dims,
@@ -152,6 +241,21 @@ class PPGMelLoader(torch.utils.data.Dataset):
             with open(self.feats_cache_path, 'wb') as f:
                 pickle.dump([self.ppg_sequences, self.acoustic_sequences], f)
 
+    def _check_f0_sources(self):
+        """Host work, before any extraction.  The device tracker's frames are the front end's frames (one F0 frame meets one PPG
+        frame), so its track is appended only to a PPG the front end computes in the same pass.  An utterance whose PPG comes from a
+        file -- or all of them, when the dependencies hold no acoustic model -- carries a frame clock of its own, and needs its F0
+        as a file as well (``<wav>.f0.npy``: a WORLD track next to a Kaldi PPG, as the reference pairs them)."""
+        has_model = getattr(self.ppg_deps, "nnet", None) is not None
+        for path in self.data_utterance_paths:
+            if any(os.path.isfile(c) for c in f0_candidates(path)):
+                continue
+            if not has_model or _precomputed(path):
+                raise NotImplementedError(
+                    "PPGMelLoader: is_append_f0: %s has no precomputed F0 track (%s) and its PPG does not come from the front end "
+                    "(%s); the device tracker's F0 is built only for PPGs the front end computes in the same pass"
+                    % (path, " or ".join(f0_candidates(path)), "a precomputed PPG file" if _precomputed(path) else "no acoustic model"))
+
     def extract_batch_feats(self, paths, is_full_ppg=False):
         """extract_utterance_feats (data_utils.py:215-258) for a chunk of utterances: (PPGs, mels) in the order of ``paths``;
         PPG [Tin, n_symbols] numpy, mel [N // hop + 1, n_mel] CPU tensor."""
@@ -163,6 +267,8 @@ class PPGMelLoader(torch.utils.data.Dataset):
             audio.append((wav[:, 0] if wav.ndim == 2 else wav).astype(np.float32))
         order = sorted(range(len(paths)), key=lambda i: len(audio[i]))
         got = get_ppg_batch([paths[i] for i in order], self.ppg_deps, is_full_ppg=is_full_ppg)
+        if self.is_append_f0:
+            got = [append_ppg(p, f) for p, f in zip(got, get_f0_batch([paths[i] for i in order], self.ppg_deps))]
         hop = self.stft.stft_fn.hop_length
         padded = np.zeros((len(order), len(audio[order[-1]])), np.float32)
         for row, i in enumerate(order):

@@ -87,6 +87,15 @@ class MfccOptions(object):
         self.cepstral_lifter = 22.0
 
 
+class SampleBatch(object):
+    """B utterances at the features' rate laid end to end: ``flat`` [sum n] on the GPU, sample counts and frame counts, and
+    the offset tables of both as C arrays on the host (s_off, f_off) and int32 tensors on the device (s_dev, f_dev)."""
+
+    def __init__(self, flat, counts, frames, s_off, f_off, s_dev, f_dev):
+        self.flat, self.counts, self.frames = flat, counts, frames
+        self.s_off, self.f_off, self.s_dev, self.f_dev = s_off, f_off, s_dev, f_dev
+
+
 class Mfcc(object):
     """kaldi.feat.mfcc.Mfcc: folds DC removal, pre-emphasis, povey window, zero padding and the DFT into one matrix on the
     host (float64), and hands it with the mel bank and the liftered DCT to facppg_mfcc_create."""
@@ -202,10 +211,10 @@ class Mfcc(object):
         return out
 
 
-    def compute_features_batch(self, waves, samp_freqs):
-        """waves: B tensors [N_b] (GPU, int16 range) sampled at samp_freqs[b] -> (mfcc [sum T, num_ceps], frame counts [B]).
-        Each utterance is downsampled on its own where needed, straight into its place in one buffer; framing, spectrum and
-        cepstra then run once over all frames (facppg_mfcc_compute_batch).  Every row equals compute_features' bit for bit."""
+    def samples_end_to_end(self, waves, samp_freqs):
+        """waves: B tensors [N_b] (GPU, int16 range) sampled at samp_freqs[b] -> a SampleBatch: the utterances at the features'
+        rate laid end to end in one buffer (each downsampled on its own where needed, straight into its place), their sample
+        and frame counts, and both offset tables on the host and on the device -- what the batch entry points read."""
         if not len(waves):
             raise ValueError("compute_features_batch: no utterance")
         for w in waves:
@@ -224,10 +233,24 @@ class Mfcc(object):
         for b, (w, fs) in enumerate(zip(waves, samp_freqs)):
             self._at_model_rate(w, fs, out=flat[s_off[b]:s_off[b + 1]])
         s_dev, f_dev = _lib.upload(list(s_off), torch.int32, dev), _lib.upload(list(f_off), torch.int32, dev)
+        return SampleBatch(flat, counts, frames, s_off, f_off, s_dev, f_dev)
+
+    def compute_features_batch(self, waves, samp_freqs, samples=None):
+        """waves: B tensors [N_b] (GPU, int16 range) sampled at samp_freqs[b] -> (mfcc [sum T, num_ceps], frame counts [B]).
+        Each utterance is downsampled on its own where needed, straight into its place in one buffer; framing, spectrum and
+        cepstra then run once over all frames (facppg_mfcc_compute_batch).  Every row equals compute_features' bit for bit.
+        samples: a list that receives the SampleBatch the features were cut from (the F0 tracker reads the same samples)."""
+        sb = self.samples_end_to_end(waves, samp_freqs)
+        if samples is not None:
+            samples.append(sb)
+        L = _lib.load()
+        flat, frames, s_off, f_off, s_dev, f_dev = sb.flat, sb.frames, sb.s_off, sb.f_off, sb.s_dev, sb.f_dev
+        dev = flat.device
+        h = self._get(dev)
         out = torch.empty(f_off[-1], self.opts.num_ceps, device=dev)
         ws = torch.empty(L.facppg_mfcc_batch_workspace_bytes(h, f_off[-1]), dtype=torch.uint8, device=dev)
         with torch.cuda.device(dev):
-            _lib.check(L.facppg_mfcc_compute_batch(h, _lib.ptr(flat), _lib.ptr(s_dev), s_off, _lib.ptr(f_dev), f_off, len(waves),
+            _lib.check(L.facppg_mfcc_compute_batch(h, _lib.ptr(flat), _lib.ptr(s_dev), s_off, _lib.ptr(f_dev), f_off, len(frames),
                                                    1 if self.opts.use_energy else 0, _lib.ptr(out), _lib.ptr(ws), ws.numel(),
                                                    _lib.current_stream(dev)))
         return out, frames
@@ -248,11 +271,12 @@ def _kept_mfcc(opts):
     return _KEPT_MFCC[key]
 
 
-def compute_mfcc_feats_batch(wavs, mfcc_opts, keep_tables=False):
+def compute_mfcc_feats_batch(wavs, mfcc_opts, keep_tables=False, samples=None):
     """compute_mfcc_feats for a list of WaveData: (mfcc [sum T, D] of the first channels laid end to end, frame counts).
-    keep_tables: compute with the Mfcc kept for these option values (same values; no table upload or hipFree in the call)."""
+    keep_tables: compute with the Mfcc kept for these option values (same values; no table upload or hipFree in the call).
+    samples: a list that receives the SampleBatch (Mfcc.compute_features_batch)."""
     mfcc = _kept_mfcc(mfcc_opts) if keep_tables else Mfcc(mfcc_opts)
-    return mfcc.compute_features_batch([w.data()[0] for w in wavs], [w.samp_freq for w in wavs])
+    return mfcc.compute_features_batch([w.data()[0] for w in wavs], [w.samp_freq for w in wavs], samples=samples)
 
 
 def compute_mfcc_feats(wav, mfcc_opts):

@@ -122,13 +122,14 @@ __global__ void k_tdnn_output_batch(const float* __restrict__ y, const int* __re
 //    Rt per 16 multiply-adds, the posteriors broadcast from LDS;
 //  - the division by the sum of exp is applied once per output.
 // PADDED = false stores out [sum T][Md] (frame g's row); PADDED = true stores the same values into out [B][Md][Tmax], the layout
-// the encoder reads (frame t of utterance b at out[b][d][t]; the columns T_b .. Tmax-1 are k_tdnn_zero_padding's):
+// the encoder reads (frame t of utterance b at out[b * bstride + d * Tmax + t], bstride >= Md * Tmax floats from one utterance to
+// the next; the columns T_b .. Tmax-1 are k_tdnn_zero_padding's):
 // the 16 frames of the tile then lie along the lanes, so that the stores of a channel row are neighbours.
 constexpr int MONO_FT = 16, MONO_CH = 256;
 template <bool PADDED>
 __global__ __launch_bounds__(256) void k_tdnn_mono(const float* __restrict__ y, const int* __restrict__ off, const int* __restrict__ cs,
                                                    int B, int M, int N, const float* __restrict__ Rt, int Md, float* __restrict__ out,
-                                                   int Tmax) {
+                                                   int Tmax, size_t bstride) {
   __shared__ __attribute__((aligned(16))) float pe[MONO_CH * MONO_FT];   // later: the 4 parts' sums [4][16][64]
   __shared__ float red[4][MONO_FT], mxs[MONO_FT], sums[MONO_FT];
   __shared__ int col[MONO_FT];
@@ -139,7 +140,7 @@ __global__ __launch_bounds__(256) void k_tdnn_mono(const float* __restrict__ y, 
     const int g = min(g0 + tid, G - 1);      // a frame past the end repeats the last one (never stored)
     const int b = seg_of(off, B, g);
     col[tid] = cs[b] + g - off[b];
-    if (PADDED) dst[tid] = (size_t)b * Md * Tmax + (g - off[b]);
+    if (PADDED) dst[tid] = (size_t)b * bstride + (g - off[b]);
   }
   __syncthreads();
   const float* yc = y + col[f];
@@ -204,9 +205,9 @@ __global__ __launch_bounds__(256) void k_tdnn_mono(const float* __restrict__ y, 
 }
 
 // out [B][Md][Tmax]: the columns T_b .. Tmax-1 of every channel row, which k_tdnn_mono<true> does not visit, are set to 0
-__global__ void k_tdnn_zero_padding(const int* __restrict__ off, int Md, int Tmax, float* __restrict__ out) {
+__global__ void k_tdnn_zero_padding(const int* __restrict__ off, int Tmax, size_t bstride, float* __restrict__ out) {
   const int b = blockIdx.z, d = blockIdx.y, t = blockIdx.x * blockDim.x + threadIdx.x;
-  if (t < Tmax && t >= off[b + 1] - off[b]) out[((size_t)b * Md + d) * Tmax + t] = 0.0f;
+  if (t < Tmax && t >= off[b + 1] - off[b]) out[(size_t)b * bstride + (size_t)d * Tmax + t] = 0.0f;
 }
 
 // Softmax over the M channel rows of a column, written as out [B][M][Tmax] -- the layout the encoder reads (ppg_dev, channel-major
@@ -220,15 +221,16 @@ __global__ void k_tdnn_zero_padding(const int* __restrict__ off, int Md, int Tma
 //    pairwise -- k_tdnn_mono's order.  No atomics; a frame's posteriors depend on its own column alone, not on B, Tmax, the
 //    segment's start or kper;
 //  - the value is k_tdnn_output's expf(v - max) / sum;
-//  - frames T_b .. Tmax-1 of an utterance are stored as 0: every element of out is written.
+//  - frames T_b .. Tmax-1 of an utterance are stored as 0: every element of the M rows of out is written; utterance b's rows start
+//    at out + b * bstride (bstride >= M * Tmax: the rows behind them are the caller's).
 constexpr int POST_FT = 16;
 __global__ __launch_bounds__(256) void k_tdnn_post_padded(const float* __restrict__ y, const int* __restrict__ off, const int* __restrict__ cs,
-                                                          int M, int N, int Tmax, int kper, float* __restrict__ out) {
+                                                          int M, int N, int Tmax, int kper, size_t bstride, float* __restrict__ out) {
   __shared__ float red[4][POST_FT], stat[POST_FT];
   const int tid = threadIdx.x, f = tid & 15, r = tid >> 4, wave = tid >> 6;
   const int b = blockIdx.y, t0 = blockIdx.x * POST_FT, t = t0 + f, T = off[b + 1] - off[b];
   const int k0 = blockIdx.z * kper, k1 = min(M, k0 + kper);
-  float* ob = out + (size_t)b * M * Tmax + t;
+  float* ob = out + (size_t)b * bstride + t;
   if (t0 >= T) {      // (uniform over the workgroup) a tile of padding
     if (t < Tmax)
       for (int k = k0 + r; k < k1; k += 16) ob[(size_t)k * Tmax] = 0.0f;
@@ -484,14 +486,14 @@ extern "C" int facppg_tdnn_forward_batch_reduced(facppg_tdnn* h, const float* fe
   hipStream_t s = (hipStream_t)stream_;
   const float* y; const int* cs; int N;
   if (int rc = tdnn_batch_layers(h, feats_dev, offsets_dev, offsets_host, B, ws_, ws_bytes, s, &y, &cs, &N)) return rc;
-  k_tdnn_mono<false><<<(offsets_host[B] + MONO_FT - 1) / MONO_FT, 256, 0, s>>>(y, offsets_dev, cs, B, h->out_dim, N, transform_t_dev, M, out_dev, 0);
+  k_tdnn_mono<false><<<(offsets_host[B] + MONO_FT - 1) / MONO_FT, 256, 0, s>>>(y, offsets_dev, cs, B, h->out_dim, N, transform_t_dev, M, out_dev, 0, 0);
   FACPPG_HIP_CHECK(hipGetLastError());
   return FACPPG_OK;
 }
 
-extern "C" int facppg_tdnn_forward_batch_padded(facppg_tdnn* h, const float* feats_dev, const int32_t* offsets_dev,
-                                                const int32_t* offsets_host, int B, const float* transform_t_dev, int M, int Tmax,
-                                                float* out_dev, void* ws_, size_t ws_bytes, void* stream_) {
+extern "C" int facppg_tdnn_forward_batch_padded_strided(facppg_tdnn* h, const float* feats_dev, const int32_t* offsets_dev,
+                                                        const int32_t* offsets_host, int B, const float* transform_t_dev, int M, int Tmax,
+                                                        size_t batch_stride, float* out_dev, void* ws_, size_t ws_bytes, void* stream_) {
   FACPPG_REQUIRE(B >= 1, FACPPG_EINVAL, "facppg_tdnn_forward_batch_padded: B must be at least 1 (got %d)", B);
   if (int rc = check_offsets(offsets_host, B, "facppg_tdnn_forward_batch_padded")) return rc;
   FACPPG_REQUIRE(h && feats_dev && offsets_dev && out_dev && ws_, FACPPG_EINVAL, "facppg_tdnn_forward_batch_padded: NULL argument");
@@ -508,13 +510,18 @@ extern "C" int facppg_tdnn_forward_batch_padded(facppg_tdnn* h, const float* fea
   FACPPG_REQUIRE(Tmax >= Tlong, FACPPG_EINVAL, "facppg_tdnn_forward_batch_padded: Tmax %d is shorter than the longest utterance (%d frames)", Tmax,
                  Tlong);
   FACPPG_REQUIRE(B <= 65535, FACPPG_EUNSUPPORTED, "facppg_tdnn_forward_batch_padded: at most 65535 utterances per call (got %d)", B);
+  const size_t rows = transform_t_dev ? (size_t)M : (size_t)h->out_dim;
+  FACPPG_REQUIRE(batch_stride >= rows * (size_t)Tmax, FACPPG_EINVAL,
+                 "facppg_tdnn_forward_batch_padded: a batch stride of %zu floats is shorter than the %zu x %d posteriors of one utterance", batch_stride,
+                 rows, Tmax);
   hipStream_t s = (hipStream_t)stream_;
   const float* y; const int* cs; int N;
   if (int rc = tdnn_batch_layers(h, feats_dev, offsets_dev, offsets_host, B, ws_, ws_bytes, s, &y, &cs, &N)) return rc;
   if (transform_t_dev) {
     // k_tdnn_mono walks the valid frames only: the padding, where a batch has any, is zeroed next to it
-    if (Tshort < Tmax) k_tdnn_zero_padding<<<dim3((Tmax + 255) / 256, M, B), 256, 0, s>>>(offsets_dev, M, Tmax, out_dev);
-    k_tdnn_mono<true><<<(offsets_host[B] + MONO_FT - 1) / MONO_FT, 256, 0, s>>>(y, offsets_dev, cs, B, h->out_dim, N, transform_t_dev, M, out_dev, Tmax);
+    if (Tshort < Tmax) k_tdnn_zero_padding<<<dim3((Tmax + 255) / 256, M, B), 256, 0, s>>>(offsets_dev, Tmax, batch_stride, out_dev);
+    k_tdnn_mono<true><<<(offsets_host[B] + MONO_FT - 1) / MONO_FT, 256, 0, s>>>(y, offsets_dev, cs, B, h->out_dim, N, transform_t_dev, M, out_dev, Tmax,
+                                                                                batch_stride);
   } else {
     // channel rows per workgroup: whole tiles of 16 rows, split until the launch has about two workgroups per CU (at most 16 ways:
     // every split repeats the tile's max / sum passes; the values do not depend on the split)
@@ -522,8 +529,18 @@ extern "C" int facppg_tdnn_forward_batch_padded(facppg_tdnn* h, const float* fea
     long want = 2l * h->n_cu / ((long)tiles * B);
     const int split = (int)(want < 1 ? 1 : want > 16 ? 16 : want);
     const int kper = round_up((h->out_dim + split - 1) / split, 16);
-    k_tdnn_post_padded<<<dim3(tiles, B, (h->out_dim + kper - 1) / kper), 256, 0, s>>>(y, offsets_dev, cs, h->out_dim, N, Tmax, kper, out_dev);
+    k_tdnn_post_padded<<<dim3(tiles, B, (h->out_dim + kper - 1) / kper), 256, 0, s>>>(y, offsets_dev, cs, h->out_dim, N, Tmax, kper, batch_stride,
+                                                                                      out_dev);
   }
   FACPPG_HIP_CHECK(hipGetLastError());
   return FACPPG_OK;
+}
+
+extern "C" int facppg_tdnn_forward_batch_padded(facppg_tdnn* h, const float* feats_dev, const int32_t* offsets_dev,
+                                                const int32_t* offsets_host, int B, const float* transform_t_dev, int M, int Tmax,
+                                                float* out_dev, void* ws_, size_t ws_bytes, void* stream_) {
+  FACPPG_REQUIRE(h, FACPPG_EINVAL, "facppg_tdnn_forward_batch_padded: NULL argument");
+  const size_t rows = transform_t_dev ? (size_t)(M > 0 ? M : 0) : (size_t)h->out_dim;
+  return facppg_tdnn_forward_batch_padded_strided(h, feats_dev, offsets_dev, offsets_host, B, transform_t_dev, M, Tmax,
+                                                  rows * (size_t)(Tmax > 0 ? Tmax : 0), out_dev, ws_, ws_bytes, stream_);
 }

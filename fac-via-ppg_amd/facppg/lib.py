@@ -87,6 +87,12 @@ class TdnnLayer(ctypes.Structure):
     _fields_ = [(n, ctypes.c_int32) for n in ("out_dim", "in_dim", "taps", "dil", "first", "relu")] + [("renorm_target_rms", ctypes.c_float)]
 
 
+class F0Config(ctypes.Structure):
+    """facppg_f0_config (include/facppg.h)."""
+    _fields_ = [(n, ctypes.c_int32) for n in ("sample_rate", "frame_shift", "window", "lag_min", "lag_max")] + \
+        [(n, ctypes.c_float) for n in ("ballast", "voicing_cost", "freq_weight")]
+
+
 class SumSegment(ctypes.Structure):
     """facppg_sum_segment (include/facppg.h)."""
     _fields_ = [("data_dev", ctypes.c_void_p), ("outer_stride", ctypes.c_long), ("outer", ctypes.c_int), ("inner", ctypes.c_int),
@@ -229,6 +235,12 @@ def _declare(lib):
         "facppg_join_segments": (c.c_int, [vp, c.c_int, vp, vp, c.c_int, c.c_int, vp, vp]),
         "facppg_ppg_dtw_workspace_bytes": (sz, [c.c_int, c.c_int, c.c_int, c.c_int, c.c_int]),
         "facppg_ppg_dtw": (c.c_int, [vp, vp, vp, c.c_int, vp, vp, vp, c.c_int, c.c_int, c.c_int, c.c_int, vp, vp, vp, vp, sz, vp]),
+        "facppg_tdnn_forward_batch_padded_strided": (c.c_int, [vp, vp, vp, vp, c.c_int, vp, c.c_int, c.c_int, sz, vp, vp, sz, vp]),
+        "facppg_f0_workspace_bytes": (sz, [c.POINTER(F0Config), c.c_int]),
+        "facppg_f0_nccf_batch": (c.c_int, [c.POINTER(F0Config), vp, vp, vp, vp, vp, c.c_int, vp, vp]),
+        "facppg_f0_track_batch": (c.c_int, [c.POINTER(F0Config), vp, vp, vp, c.c_int, vp, vp, vp, vp, sz, vp]),
+        "facppg_f0_batch": (c.c_int, [c.POINTER(F0Config), vp, vp, vp, vp, vp, c.c_int, vp, vp, vp, vp, sz, vp]),
+        "facppg_lf0_rows_padded": (c.c_int, [vp, vp, vp, c.c_int, c.c_int, sz, vp, vp]),
     }
     for name, (res, args) in sigs.items():
         fn = getattr(lib, name)      # AttributeError here = header/library mismatch

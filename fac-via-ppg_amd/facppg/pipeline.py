@@ -723,7 +723,8 @@ def _checked_wav_list(wavs, ppgs, what):
 def _checked_wavs(wavs, deps, tacotron, is_full_ppg, what, ppgs=None):
     """The argument checks of a call that starts from audio, all on the host and before any device work: ``wavs`` a non-empty list
     (and no ``ppgs`` next to it), an acoustic model in ``deps`` whose posteriors -- senone or monophone -- have the width the
-    PPG -> mel model was built for.  Returns is_full_ppg (None: whichever width fits the model's n_symbols)."""
+    PPG -> mel model was built for, or that width + 3 (a model trained with ``is_append_f0``: _checked_append_f0).  Returns
+    is_full_ppg (None: whichever width fits the model's n_symbols)."""
     from facppg.lib import FacppgError
     from ppg.compute_ppg import _require_model, padded_ppg_dim
     _checked_wav_list(wavs, ppgs, what)
@@ -732,17 +733,35 @@ def _checked_wavs(wavs, deps, tacotron, is_full_ppg, what, ppgs=None):
     _require_model(getattr(deps, "nnet", None), what)
     n_symbols = tacotron._hp["n_symbols"]
     if is_full_ppg is None:
-        is_full_ppg = padded_ppg_dim(deps, True) == n_symbols or getattr(deps, "monophone_trans", None) is None
+        is_full_ppg = padded_ppg_dim(deps, True) in (n_symbols, n_symbols - 3) or getattr(deps, "monophone_trans", None) is None
     D = padded_ppg_dim(deps, bool(is_full_ppg))
-    if D != n_symbols:
+    if n_symbols not in (D, D + 3):
         raise FacppgError("%s: the %s PPGs of these dependencies have %d symbols, the PPG -> mel model was built for %d"
                           % (what, "senone" if is_full_ppg else "monophone", D, n_symbols))
     return bool(is_full_ppg)
 
 
+def _checked_append_f0(deps, tacotron, is_full_ppg, append_f0, what):
+    """Whether the front end appends the three log-F0 rows (ppg.compute_ppg_padded(append_f0=True)): None means on iff the model's
+    n_symbols is the PPG width + 3 (hparams.is_append_f0 at training time); a choice the width contradicts is refused.  Host work
+    only, after _checked_wavs."""
+    from facppg.lib import FacppgError
+    from ppg.compute_ppg import padded_ppg_dim
+    n_symbols = tacotron._hp["n_symbols"]
+    D = padded_ppg_dim(deps, is_full_ppg)
+    fits = n_symbols == D + 3
+    if append_f0 is None:
+        append_f0 = fits
+    if bool(append_f0) != fits:
+        raise FacppgError("%s: append_f0=%s gives %d input rows (%d %s PPG rows%s), the PPG -> mel model was built for %d"
+                          % (what, bool(append_f0), D + (3 if append_f0 else 0), D, "senone" if is_full_ppg else "monophone",
+                             " + 3 log-F0 rows" if append_f0 else "", n_symbols))
+    return bool(append_f0)
+
+
 def synthesize_wavs(wavs, deps, tacotron, waveglow, denoiser=None, is_full_ppg=None, sigma=0.6, strength=0.005, seed=None,
                     dropout_masks=None, z=None, return_device=False, utterance_seeds=None, step_limits=None, timer=None,
-                    vocoder_arithmetic=None, vocoder_stream=None, ppgs=None):
+                    vocoder_arithmetic=None, vocoder_stream=None, ppgs=None, append_f0=None):
     """synthesize() from teacher audio (the reference's purpose, generate_synthesis.py:86-98): wavs, a list of WaveData on the GPU
     (common.feat.read_wav_kaldi), go through the batch front end (ppg.compute_ppg_padded: features, acoustic model of ``deps``,
     a ppg.DependenciesPPG) and their posteriors reach the encoder where the front end left them -- on the device, in the padded
@@ -752,6 +771,8 @@ def synthesize_wavs(wavs, deps, tacotron, waveglow, denoiser=None, is_full_ppg=N
     is_full_ppg: senone posteriors (True) or monophone PPGs through deps.monophone_trans (False); None picks the one whose width
     is the model's n_symbols.  A width that differs from n_symbols is refused before anything is launched, and so is a call that
     names ``ppgs`` as well: an utterance comes from one of the two.
+    append_f0: the front end's F0 track as three more input rows (log F0, delta, delta-delta: ppg.compute_ppg_padded), for a model
+    trained with ``is_append_f0``; None: on iff n_symbols is the PPG width + 3.
     The monophone PPGs are compute_ppg_batch's bit for bit, so the samples are those of synthesize() over its host copies; the
     senone posteriors sum their softmax in another order than the row-major output kernels (the same bounds against the
     oracle), so there the samples are those of synthesize() over host copies of compute_ppg_padded's own values."""
@@ -759,10 +780,11 @@ def synthesize_wavs(wavs, deps, tacotron, waveglow, denoiser=None, is_full_ppg=N
     is_full_ppg = _checked_wavs(wavs, deps, tacotron, is_full_ppg, "synthesize_wavs", ppgs)
     arithmetic = _checked_arithmetic(vocoder_arithmetic)
     _checked_stream(vocoder_stream)
+    append_f0 = _checked_append_f0(deps, tacotron, is_full_ppg, append_f0, "synthesize_wavs")
     if timer is not None:
         timer.__init__()
     with torch.no_grad():
-        prepared = compute_ppg_padded(wavs, deps, is_full_ppg=is_full_ppg)
+        prepared = compute_ppg_padded(wavs, deps, is_full_ppg=is_full_ppg, append_f0=append_f0)
     if timer is not None:
         timer.mark("front_end")
     return _synthesize(None, prepared, tacotron, waveglow, denoiser, sigma, strength, seed, dropout_masks, z, return_device, utterance_seeds,
@@ -788,12 +810,13 @@ def _acoustic_stream(device):
 
 
 def synthesize_stream(jobs, tacotron, waveglow, denoiser=None, sigma=0.6, strength=0.005, return_device=True, overlap=True,
-                      acoustic_workgroups=32, vocoder_arithmetic=None, ppg_deps=None, is_full_ppg=None):
+                      acoustic_workgroups=32, vocoder_arithmetic=None, ppg_deps=None, is_full_ppg=None, append_f0=None):
     """A sequence of batches, software-pipelined: generator of (waveforms, mel lengths), one per job, in order.
 
     jobs: iterable of dicts with ``ppgs`` and optionally ``seed``, ``utterance_seeds``, ``step_limits`` (as synthesize()).
     A job may carry ``wavs`` (a list of WaveData, as synthesize_wavs() takes it) in place of ``ppgs``: its front end (features,
-    acoustic model of ``ppg_deps``, senone or monophone by ``is_full_ppg`` as in synthesize_wavs()) then runs in front of its
+    acoustic model of ``ppg_deps``, senone or monophone by ``is_full_ppg`` and with or without the log-F0 rows by ``append_f0``,
+    both as in synthesize_wavs()) then runs in front of its
     acoustic model on the same stream, i.e. under the previous batch's vocoder as well, and its PPGs never leave the device.
     The samples of a ``wavs`` job are bit for bit its WaveData, as read_wav_kaldi leaves them: complete before the job is handed over.
     ``wavs`` may also be a callable that returns that list.  It is called when the job's acoustic model is about to be enqueued,
@@ -851,7 +874,8 @@ def synthesize_stream(jobs, tacotron, waveglow, denoiser=None, sigma=0.6, streng
                 for w in wavs:
                     if torch.is_tensor(w.data()) and w.data().is_cuda:
                         w.data().record_stream(side)
-                prepared = compute_ppg_padded(wavs, ppg_deps, is_full_ppg=full)
+                with_f0 = _checked_append_f0(ppg_deps, tacotron, full, append_f0, "synthesize_stream")
+                prepared = compute_ppg_padded(wavs, ppg_deps, is_full_ppg=full, append_f0=with_f0)
             mel_post, tout = _acoustic(job.get("ppgs"), tacotron, job.get("seed"), None, job.get("utterance_seeds"), job.get("step_limits"),
                                        decoder_workgroups=bound, prepared=prepared)
             done = torch.cuda.Event()
@@ -1038,9 +1062,11 @@ def synthesize_long(ppgs, tacotron, waveglow, denoiser=None, *, pause_rows=None,
 
 def synthesize_long_wavs(wavs, deps, tacotron, waveglow, denoiser=None, is_full_ppg=None, *, pause_rows=None, max_frames=600, min_frames=150,
                          min_pause=8, pause_threshold=0.5, seam_fade=64, batch_frames=None, seed=0, limit_to_input=False, sigma=0.6,
-                         strength=0.005, return_device=False, vocoder_arithmetic=None, overlap=True, acoustic_workgroups=32):
+                         strength=0.005, return_device=False, vocoder_arithmetic=None, overlap=True, acoustic_workgroups=32, append_f0=None):
     """synthesize_long() from teacher audio: wavs (a list of WaveData, whole recordings) go through ppg.compute_ppg_padded once and
-    its device batch is cut, converted and joined as above; no posterior visits the host.  is_full_ppg as in synthesize_wavs().
+    its device batch is cut, converted and joined as above; no posterior visits the host.  is_full_ppg and append_f0 as in
+    synthesize_wavs(): with the log-F0 rows the segments carry K + 3 rows, and their delta rows are those of the WHOLE recording (a
+    segment's first frame keeps the slope it had there).
     pause_rows None: [39] for monophone PPGs; for senone PPGs the senones that ``deps.monophone_trans`` maps to row 39 (its
     nonzero columns: the same mass), refused when the dependencies have no such map."""
     from facppg.lib import FacppgError
@@ -1058,7 +1084,8 @@ def synthesize_long_wavs(wavs, deps, tacotron, waveglow, denoiser=None, is_full_
             pause_rows = [int(c) for c in torch.nonzero(torch.as_tensor(trans)[39]).flatten()]
     cfg = _checked_long(tacotron, tacotron._hp["n_symbols"], what, pause_rows, max_frames, min_frames, min_pause, pause_threshold, seam_fade,
                         batch_frames, vocoder_arithmetic)
+    append_f0 = _checked_append_f0(deps, tacotron, is_full_ppg, append_f0, what)
     with torch.no_grad():
-        x, lens = compute_ppg_padded(wavs, deps, is_full_ppg=is_full_ppg)
+        x, lens = compute_ppg_padded(wavs, deps, is_full_ppg=is_full_ppg, append_f0=append_f0)
     return _synthesize_long(x, lens, cfg, tacotron, waveglow, denoiser, int(seed), limit_to_input, sigma, strength, return_device, overlap,
                             acoustic_workgroups)

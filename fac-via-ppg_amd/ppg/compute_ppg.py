@@ -15,7 +15,8 @@
                            reduction is fused into the output kernel (facppg_tdnn_forward_batch_reduced)
   compute_ppg_padded       the batch chain again, the posteriors left on the device as the padded channel-major batch
                            [B, D, Tmax] that Tacotron2.inference reads (facppg_tdnn_forward_batch_padded): wav in, wav out
-                           without the PPGs visiting the host (facppg.pipeline.synthesize_wavs)
+                           without the PPGs visiting the host (facppg.pipeline.synthesize_wavs); with ``append_f0`` the log F0
+                           of ppg.compute_f0's track and its two deltas in three more rows (hparams.is_append_f0)
 
 Matrices are float32 GPU tensors; file paths default to ``<repo data dir>/...`` like the reference's module constants and
 can be overridden (FACPPG_DATA_DIR, or the constructor arguments)."""
@@ -28,6 +29,7 @@ import torch
 
 from common import decode, feat, kaldi_io, nnet3
 from facppg import lib as _lib
+from ppg.compute_f0 import F0Options, f0_flat, lf0_rows_padded
 
 DATA_DIR = os.environ.get("FACPPG_DATA_DIR", os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "..", "data"))
 NNET_PATH = os.path.join(DATA_DIR, 'am', 'final.raw')
@@ -198,7 +200,16 @@ def compute_feat_for_nnet_internal(wav, lda, **kwargs):
     return feat.cmn_splice_transform(mfccs, options["left_context"], options["right_context"], lda)
 
 
-def _feat_for_nnet_flat(wavs, lda, keep_tables=False, **kwargs):
+def _mfcc_options(options):
+    mfcc_opts = feat.MfccOptions()
+    mfcc_opts.use_energy = options["is_use_energy"]
+    mfcc_opts.frame_opts.allow_downsample = options["is_downsample"]
+    mfcc_opts.frame_opts.frame_shift_ms = options["frame_shift"]
+    mfcc_opts.frame_opts.snip_edges = options["is_snip_edges"]
+    return mfcc_opts
+
+
+def _feat_for_nnet_flat(wavs, lda, keep_tables=False, samples=None, **kwargs):
     options = {"is_use_energy": False, "is_downsample": True, "frame_shift": 10, "is_snip_edges": False, "left_context": 3,
                "right_context": 3}
     for key, val in kwargs.items():
@@ -206,12 +217,7 @@ def _feat_for_nnet_flat(wavs, lda, keep_tables=False, **kwargs):
             options[key] = val
         else:
             logging.error("Option %s not allowed!" % (key))
-    mfcc_opts = feat.MfccOptions()
-    mfcc_opts.use_energy = options["is_use_energy"]
-    mfcc_opts.frame_opts.allow_downsample = options["is_downsample"]
-    mfcc_opts.frame_opts.frame_shift_ms = options["frame_shift"]
-    mfcc_opts.frame_opts.snip_edges = options["is_snip_edges"]
-    mfccs, frames = feat.compute_mfcc_feats_batch(wavs, mfcc_opts, keep_tables=keep_tables)
+    mfccs, frames = feat.compute_mfcc_feats_batch(wavs, _mfcc_options(options), keep_tables=keep_tables, samples=samples)
     return feat.cmn_splice_transform_batch(mfccs, frames, options["left_context"], options["right_context"], lda), frames
 
 
@@ -265,7 +271,7 @@ def _on_device(deps, name, dev, transposed=False):
     return hit[1]
 
 
-def compute_ppg_padded(wavs, deps, is_full_ppg=True, shift=10):
+def compute_ppg_padded(wavs, deps, is_full_ppg=True, shift=10, append_f0=False, f0_options=None):
     """compute_ppg_batch for a consumer on the device: list of WaveData -> (x [B, D, Tmax] float32 on the GPU, lengths [B] on
     the host), the batch Tacotron2.inference reads -- channel-major, frames contiguous, exactly 0 behind each utterance's
     T_b frames (facppg_tdnn_forward_batch_padded writes every element: nothing is zeroed here).  D = the model's senones, or
@@ -278,13 +284,26 @@ def compute_ppg_padded(wavs, deps, is_full_ppg=True, shift=10):
     handle and like it for the life of the model object), the device copies of ``deps.lda`` / ``deps.monophone_trans``
     (``deps._facppg_on_device``, replaced when the attribute is bound to another object) and one Mfcc per set of option values
     (common.feat._KEPT_MFCC, for the life of the process: a few hundred KB each).  A model or matrix is a loaded file here; one
-    that is changed IN PLACE after the first call is not seen -- bind a new object, or delete the attribute named above."""
+    that is changed IN PLACE after the first call is not seen -- bind a new object, or delete the attribute named above.
+
+    append_f0: x is [B, D + 3, Tmax], the input of a model trained with ``is_append_f0`` (append_ppg, data_utils.py:142-160):
+    rows [:D] are the posteriors above, bit for bit (written in place through a batch stride: no copy), rows [D:] the log F0,
+    its delta and its delta-delta of ppg.compute_f0's track over the very samples the features were cut from
+    (facppg_f0_batch, facppg_lf0_rows_padded), exactly 0 behind T_b as well.  ``f0_options``: an F0Options whose sample rate and
+    frame shift are the front end's.  Still nothing is copied back and nothing waits."""
     K = padded_ppg_dim(deps, is_full_ppg)
     if not len(wavs):
         raise ValueError("compute_ppg_padded: no utterance")
+    if append_f0:
+        f0_options = f0_options or F0Options()
+        if int(f0_options.sample_rate) != 16000 or int(f0_options.frame_shift) * 1000 != int(shift) * int(f0_options.sample_rate):
+            raise _lib.FacppgError("compute_ppg_padded: F0 frames of %d samples at %d Hz are not the front end's %d ms frames at 16000 Hz"
+                                   % (f0_options.frame_shift, f0_options.sample_rate, shift))
     L = _lib.load()
     dev = wavs[0].data().device
-    flat, frames = _feat_for_nnet_flat(wavs, _on_device(deps, "lda", dev) if dev.type == "cuda" else deps.lda, keep_tables=True, frame_shift=shift)
+    samples = [] if append_f0 else None
+    flat, frames = _feat_for_nnet_flat(wavs, _on_device(deps, "lda", dev) if dev.type == "cuda" else deps.lda, keep_tables=True, samples=samples,
+                                       frame_shift=shift)
     h = _tdnn_handle(deps.nnet, dev, "compute_ppg_padded")
     if flat.shape[1] != h.in_dim:
         raise _lib.FacppgError("compute_ppg_padded: features have %d dims, the model's input node has %d" % (flat.shape[1], h.in_dim))
@@ -300,10 +319,19 @@ def compute_ppg_padded(wavs, deps, is_full_ppg=True, shift=10):
         _lib.check(-1)
     off_dev = _lib.upload(list(off), torch.int32, dev)
     ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
-    x = torch.empty(B, K, Tmax, device=dev)
+    if not append_f0:
+        x = torch.empty(B, K, Tmax, device=dev)
+        with torch.cuda.device(dev):
+            _lib.check(L.facppg_tdnn_forward_batch_padded(h.handle, _lib.ptr(flat), _lib.ptr(off_dev), off, B, _lib.ptr(tr_t),
+                                                          K if tr_t is not None else 0, Tmax, _lib.ptr(x), _lib.ptr(ws), ws.numel(),
+                                                          _lib.current_stream(dev)))
+        return x, [int(n) for n in frames]
+    x = torch.empty(B, K + 3, Tmax, device=dev)
     with torch.cuda.device(dev):
-        _lib.check(L.facppg_tdnn_forward_batch_padded(h.handle, _lib.ptr(flat), _lib.ptr(off_dev), off, B, _lib.ptr(tr_t), K if tr_t is not None else 0,
-                                                      Tmax, _lib.ptr(x), _lib.ptr(ws), ws.numel(), _lib.current_stream(dev)))
+        _lib.check(L.facppg_tdnn_forward_batch_padded_strided(h.handle, _lib.ptr(flat), _lib.ptr(off_dev), off, B, _lib.ptr(tr_t),
+                                                              K if tr_t is not None else 0, Tmax, (K + 3) * Tmax, _lib.ptr(x), _lib.ptr(ws),
+                                                              ws.numel(), _lib.current_stream(dev)))
+    lf0_rows_padded(f0_flat(samples[0], f0_options), samples[0], x, K)
     return x, [int(n) for n in frames]
 
 

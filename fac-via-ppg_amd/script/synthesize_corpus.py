@@ -41,7 +41,8 @@ def parse(argv=None):
     src = ap.add_mutually_exclusive_group(required=True)
     src.add_argument('--ppg_list', help='text file, one precomputed PPG .npy path per line')
     src.add_argument('--wav_list', help='text file, one teacher wav per line: the PPGs are extracted here (acoustic model: --nnet_path '
-                                        'and the files of --feats_dir; senone or monophone PPGs by the hparam is_full_ppg)')
+                                        'and the files of --feats_dir; senone or monophone PPGs by the hparam is_full_ppg, with the three log-F0 columns by '
+                                        'the hparam is_append_f0 -- set n_symbols to the PPG width + 3 with it)')
     ap.add_argument('--nnet_path', default=None, help='nnet3 acoustic model for --wav_list (default: data/am/final.raw)')
     ap.add_argument('--feats_dir', default=None, help='directory of final.mat, reduce_dim.mat and splice_opts for --wav_list '
                                                       '(default: data/feats)')
@@ -126,20 +127,26 @@ def ppg_dependencies(args):
 
 
 def extract_shard_ppgs(paths, mine, lengths, args, hparams):
-    """{global id: PPG} of this rank's utterances, extracted ``args.batch_size`` at a time in batches of similar length."""
-    from common.data_utils import get_ppg_batch
+    """{global id: PPG} of this rank's utterances, extracted ``args.batch_size`` at a time in batches of similar length.  With the
+    hparam ``is_append_f0`` every PPG carries the three log-F0 columns (common.data_utils.append_ppg over get_f0_batch's track: a
+    ``.f0.npy`` file next to the wav, else the device tracker)."""
+    from common.data_utils import append_ppg, get_f0_batch, get_ppg_batch
     deps = ppg_dependencies(args)
     ppgs = {}
     for batch in shard.batches(mine, lengths, args.batch_size):
-        for i, p in zip(batch, get_ppg_batch([paths[i] for i in batch], deps, is_full_ppg=hparams.is_full_ppg)):
+        got = get_ppg_batch([paths[i] for i in batch], deps, is_full_ppg=hparams.is_full_ppg)
+        if hparams.is_append_f0:
+            got = [append_ppg(p, f).astype(np.float32) for p, f in zip(got, get_f0_batch([paths[i] for i in batch], deps))]
+        for i, p in zip(batch, got):
             ppgs[i] = p
     return ppgs
 
 
-def synthesize_shard(synthesizer, ppgs, lengths, rank, world, args, wav_paths=None, ppg_deps=None, is_full_ppg=None):
+def synthesize_shard(synthesizer, ppgs, lengths, rank, world, args, wav_paths=None, ppg_deps=None, is_full_ppg=None, append_f0=False):
     """This rank's utterances, longest first, in batches of similar length.  Returns (waveforms, global ids).
     wav_paths (--device_ppgs) in place of ``ppgs``: every job carries the wavs of its batch, read when its acoustic model is
-    enqueued -- the same batches extract_shard_ppgs forms, so the front end sees the same column space with and without the flag."""
+    enqueued -- the same batches extract_shard_ppgs forms, so the front end sees the same column space with and without the flag.
+    append_f0 (the hparam is_append_f0): the front end appends the log-F0 rows of its own track on the device."""
     mine = shard.partition(lengths, world)[rank]
     batches = list(shard.batches(mine, lengths, args.batch_size))
 
@@ -156,7 +163,8 @@ def synthesize_shard(synthesizer, ppgs, lengths, rank, world, args, wav_paths=No
         if not hasattr(synthesizer, "stream"):
             raise ValueError("--device_ppgs needs a synthesizer with stream() (facppg.pipeline.Synthesizer)")
         results = synthesizer.stream(jobs, sigma=args.sigma, strength=args.denoiser_strength, return_device=True,
-                                     overlap=not getattr(args, "no_overlap", False), ppg_deps=ppg_deps, is_full_ppg=is_full_ppg)
+                                     overlap=not getattr(args, "no_overlap", False), ppg_deps=ppg_deps, is_full_ppg=is_full_ppg,
+                                     **({"append_f0": True} if append_f0 else {}))
     elif hasattr(synthesizer, "stream"):      # software-pipelined: batch i+1's acoustic model runs under batch i's vocoder
         results = synthesizer.stream(jobs, sigma=args.sigma, strength=args.denoiser_strength, return_device=True,
                                      overlap=not getattr(args, "no_overlap", False))
@@ -248,7 +256,7 @@ def main(argv=None, synthesizer=None):
                                       vocoder_arithmetic=args.vocoder_arithmetic)
         if args.device_ppgs:
             wavs, ids = synthesize_shard(synthesizer, None, lengths, rank, world, args, wav_paths=paths, ppg_deps=ppg_dependencies(args),
-                                         is_full_ppg=hparams.is_full_ppg)
+                                         is_full_ppg=hparams.is_full_ppg, append_f0=bool(hparams.is_append_f0))
         else:
             wavs, ids = synthesize_shard(synthesizer, ppgs, lengths, rank, world, args)
         if args.score_file:

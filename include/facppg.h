@@ -859,6 +859,14 @@ int facppg_tdnn_forward_batch_reduced(facppg_tdnn* h, const float* feats_dev, co
 int facppg_tdnn_forward_batch_padded(facppg_tdnn* h, const float* feats_dev, const int32_t* offsets_dev,
                                      const int32_t* offsets_host, int B, const float* transform_t_dev, int M, int Tmax,
                                      float* out_dev, void* workspace_dev, size_t ws_bytes, void* stream);
+/* The same with batch_stride floats from one utterance's rows to the next (>= K * Tmax, else FACPPG_EINVAL):
+ * out[b * batch_stride + k * Tmax + t].  The K rows of every utterance are written in full and nothing behind them is touched,
+ * so the posteriors go straight into rows [:K] of a wider batch -- [B][K + 3][Tmax] with the log-F0 rows of
+ * facppg_lf0_rows_padded behind them -- without a copy.  facppg_tdnn_forward_batch_padded is this call with K * Tmax. */
+int facppg_tdnn_forward_batch_padded_strided(facppg_tdnn* h, const float* feats_dev, const int32_t* offsets_dev,
+                                             const int32_t* offsets_host, int B, const float* transform_t_dev, int M,
+                                             int Tmax, size_t batch_stride, float* out_dev, void* workspace_dev,
+                                             size_t ws_bytes, void* stream);
 
 /* ------------------------------------------------------------------------------------
  * Long recordings: cut at the pauses, convert the pieces as padded batches, join the audio
@@ -915,6 +923,80 @@ int facppg_ppg_dtw(const float* a_dev, const int32_t* la_dev, const int32_t* la_
                    int B, int D, int band,
                    float* cost_dev, int32_t* steps_dev, int32_t* agree_dev,
                    void* ws_dev, size_t ws_bytes, void* stream);
+
+/* ------------------------------------------------------------------------------------
+ * F0 track on the device, and the reference's log-F0 input columns (hparams.is_append_f0: append_ppg,
+ * src/common/data_utils.py:142-160, makes n_symbols = K + 3).  The reference takes its F0 from WORLD through pyworld
+ * (utterance.py:33-38: harvest, 48-400 Hz, 5 ms shift), which does not exist in this image and cannot be reproduced here:
+ * PARITY UNPINNED at the WORLD boundary.  The tracker is therefore DEFINED here -- a normalised cross-correlation and one
+ * Viterbi pass over its peaks -- and the kernels are held to a float64 / float32 restatement of this text
+ * (tests/f0_helpers.py).  A user who has WORLD tracks brings them as files (common.data_utils.get_f0_batch).
+ *
+ * Input: the front end's own samples, int16-range floats at the model's rate (after common.feat's resampling), the B
+ * utterances laid end to end with sample_offsets[B + 1], exactly as facppg_mfcc_compute_batch takes them.  Samples outside
+ * an utterance's own [0, n) read as 0; an utterance never sees a neighbour's samples.
+ * Frames are the PPG's frames: T_b = (n_b + S / 2) / S (facppg_mfcc_num_frames), frame t centred at t S + S / 2.  The
+ * reference's WORLD shift is 5 ms and append_ppg just truncates to the shorter of the two tracks; here ONE F0 FRAME MEETS ONE
+ * PPG FRAME.  With S = frame_shift, W = window, L = lag_max - lag_min + 1 candidate lags:
+ *   tables_dev float [2][L], computed by the host: wl[l] = float32(1 - 0.3 l / lag_max), g[l] = float32(log2 l), l = lag_min ..
+ *                  lag_max -- no transcendental function runs on the device inside the tracker
+ *   NCCF           a = t S + S / 2 - (W + lag_max + 1) / 2 (integer division); for every lag l in lag_min - 1 .. lag_max + 1
+ *                  (L + 2 columns): phi(t,l) = sum_{j<W} x[a+j] x[a+j+l] / sqrt(E(a) E(a+l) + (W ballast^2)^2),
+ *                  E(p) = sum_{j<W} x[p+j]^2; fp32 sums in an order that depends on W alone (a frame has the same bits in any
+ *                  batch).  nccf_dev [sum T][L + 2], row-major
+ *   track          one Viterbi pass per utterance over its own rows.  State 0 is unvoiced, state s = 1 .. L is lag
+ *                  lag_min + s - 1.  Lag l is a PEAK at t iff phi(t,l) >= phi(t,l-1) and phi(t,l) > phi(t,l+1).
+ *                  voiced local cost   dv(t,l) = 1 - phi(t,l) wl[l] at a peak, +inf elsewhere
+ *                  unvoiced local cost du(t) = max_l phi(t,l) over lag_min .. lag_max only
+ *                  start               C(0,0) = du(0), C(0,l) = dv(0,l)
+ *                  t >= 1              predecessors tried with s' increasing and a strict <:
+ *                                      into unvoiced: C(t-1,0), then C(t-1,s') + voicing_cost
+ *                                      into lag l:    C(t-1,0) + voicing_cost, then C(t-1,s') + freq_weight |g[l] - g[l']|
+ *                                      and the local cost is added to the winner
+ *                  all fp32, every multiply and add rounded on its own.  The end state is the first minimum of C(T-1, .);
+ *                  back-pointers uint16 [T][L + 1] live in the workspace, then a backtrace
+ *   outputs        per frame lag_dev int32 (0 = unvoiced) and f0_dev float: 0 when unvoiced; voiced, with p = phi(l-1), q = phi(l),
+ *                  r = phi(l+1): den = (p - (q + q)) + r, delta = den < 0 ? 0.5 (p - r) / den : 0, f0 = sample_rate / (l + delta),
+ *                  fp32 in that order (the two guard columns exist for this)
+ * facppg_f0_nccf_batch writes the matrix, facppg_f0_track_batch reads one (the caller's own, if it likes), facppg_f0_batch
+ * runs the two back to back with the matrix in the workspace.  Offsets come as a device copy (read by the kernels) next to a
+ * host copy (validated before the first launch).  Refused, and nothing is launched: a NULL pointer, B < 1, offsets that do
+ * not start at 0 or do not increase, a sample count with no frame, frame offsets that are not the sample counts' T_b,
+ * lag_min < 2, lag_max >= 2048 or < lag_min, window < 1, a negative cost (FACPPG_EINVAL); more than 1023 candidate lags, a
+ * frame span beyond what a workgroup stages, B > 65535 (FACPPG_EUNSUPPORTED); a workspace smaller than
+ * facppg_f0_workspace_bytes(cfg, sum T) (FACPPG_EWORKSPACE; 0 with facppg_last_error set for a refused configuration).
+ *
+ * facppg_lf0_rows_padded: f0_dev [sum T] (Hz, 0 = unvoiced) -> the three rows append_ppg appends, in the padded batch:
+ *   x0 = logf(f0 + 2.220446e-16f)  (the reference's np.finfo(float).eps: unvoiced frames come out near -36.04, as they do there)
+ *   x1 = 0.5 (x0[t+1] - x0[t-1]),  x2 = 0.25 x0[t-2] - 0.5 x0[t] + 0.25 x0[t+2]      (DELTA_WIN, ACC_WIN)
+ *   indices clamped to the utterance's own first and last frame (compute_dynamic_vector's edge replication)
+ * out_dev[b * batch_stride + r * Tmax + t], r = 0 .. 2 -- with out_dev = x + K * Tmax and batch_stride = (K + 3) * Tmax these are
+ * the rows [K:] of the [B][K + 3][Tmax] batch whose rows [:K] facppg_tdnn_forward_batch_padded_strided writes.  Exactly 0.0f
+ * for T_b <= t < Tmax; every element of the three rows is written.  Refused: a NULL pointer, B < 1, bad offsets, Tmax below the
+ * longest utterance, batch_stride < 3 Tmax. */
+typedef struct facppg_f0_config {
+  int32_t sample_rate;   /* 16000 */
+  int32_t frame_shift;   /* 160 */
+  int32_t window;        /* 320 */
+  int32_t lag_min;       /* 40  = floor(16000 / 400) */
+  int32_t lag_max;       /* 334 = ceil(16000 / 48): L = 295 */
+  float ballast;         /* 50 */
+  float voicing_cost;    /* 0.2 */
+  float freq_weight;     /* 2.0 */
+} facppg_f0_config;
+size_t facppg_f0_workspace_bytes(const facppg_f0_config* cfg, int total_frames);
+int facppg_f0_nccf_batch(const facppg_f0_config* cfg, const float* wav_dev, const int32_t* sample_offsets_dev,
+                         const int32_t* sample_offsets_host, const int32_t* frame_offsets_dev,
+                         const int32_t* frame_offsets_host, int B, float* nccf_dev, void* stream);
+int facppg_f0_track_batch(const facppg_f0_config* cfg, const float* nccf_dev, const int32_t* frame_offsets_dev,
+                          const int32_t* frame_offsets_host, int B, const float* tables_dev, int32_t* lag_dev,
+                          float* f0_dev, void* ws_dev, size_t ws_bytes, void* stream);
+int facppg_f0_batch(const facppg_f0_config* cfg, const float* wav_dev, const int32_t* sample_offsets_dev,
+                    const int32_t* sample_offsets_host, const int32_t* frame_offsets_dev,
+                    const int32_t* frame_offsets_host, int B, const float* tables_dev, int32_t* lag_dev, float* f0_dev,
+                    void* ws_dev, size_t ws_bytes, void* stream);
+int facppg_lf0_rows_padded(const float* f0_dev, const int32_t* frame_offsets_dev, const int32_t* frame_offsets_host,
+                           int B, int Tmax, size_t batch_stride, float* out_dev, void* stream);
 
 #ifdef __cplusplus
 }
