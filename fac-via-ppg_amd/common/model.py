@@ -33,7 +33,7 @@ from facppg import lib as _lib
 
 # One decoder launch as facppg_taco_decode reports it: mode 'single', 'coop' or 'split', its workgroups, and whether it published
 # its frames to the call's frame consumer.
-DecoderLaunch = collections.namedtuple("DecoderLaunch", "mode workgroups streamed")
+DecoderLaunch = collections.namedtuple("DecoderLaunch", "mode workgroups streamed step", defaults=(0,))
 
 
 class InferenceOutputs(list):
@@ -495,7 +495,7 @@ class Tacotron2(nn.Module):
             _lib.check(L.facppg_taco_decode(h, _lib.ptr(memory), _lib.ptr(pm), _lib.ptr(lt), _lib.ptr(sl), _lib.ptr(dec_m), seed, B, Tin,
                                             steps, _lib.ptr(mel), _lib.ptr(gate), _lib.ptr(align), _lib.ptr(out_len),
                                             _lib.ptr(ws), ws.numel(), _lib.ctypes.byref(opts), st))
-            launch = DecoderLaunch(("single", "coop", "split")[opts.mode], opts.workgroups, bool(opts.streamed))
+            launch = DecoderLaunch(("single", "coop", "split")[opts.mode], opts.workgroups, bool(opts.streamed), int(opts.step))
             if frame_consumer is not None and B == 1:
                 if launch.streamed:
                     frame_consumer.enqueue(out_len, launch.workgroups)   # its launches, gated on the frames, on its own stream

@@ -491,6 +491,10 @@ struct DecArgs {
   float gate_thr;
   // k_decoder_split: worker workgroups per group
   int nwk, dbg_flags;
+  // k_decoder_split's main workgroup: the first q_res of a thread's QR query-weight rows are kept in LDS for the whole launch
+  int q_res;
+  // k_decoder_split's workers: units of 128 cycles a worker stays off the exchange words between publishing and polling
+  int pause;
   // k_decoder_split, B = 1: every mel value of frame t is ALSO published as a {value, t + 1} word at melx[t * NF + row] the moment
   // its projection row is formed (agent-scope store: visible to kernels on other streams while this launch is still running --
   // the plain stores to `mel` are only guaranteed visible once it has ended); facppg_taco_collect_frames reads them
@@ -1261,7 +1265,9 @@ __global__ __launch_bounds__(NTC) void k_decoder_coop(DecArgs p) {
 // utterance: worker w owns LSTM units 4w..4w+3 of both LSTMCells (16 gate rows x K/32 columns per
 // thread) and, for w < ceil(rows/16), rows 16w..16w+15 of the projection+gate and of the two prenet
 // layers.  A step therefore streams no weights at all; what remains is a chain of tagged-word
-// exchanges (see coop_gather; ~1.5 us each):
+// exchanges (see coop_gather; worker 0's phase cycles, profiles/r20_decoder_ab.txt: 1.5-2.2 us from
+// a stage's end to its last word gathered, 0.85 of it SPLIT_PAUSE, against 0.8-1.2 us for the matvec stage in front of it --
+// the chain is the exchanges' latency, and that latency grows with the polling: see SPLIT_PAUSE):
 //   workers: [project rows -> MEL(t) | gather -> stop?]  prenet-1 rows -> X1 | gather | prenet-2 rows
 //            -> X2 | gather | attention-LSTM slice -> AH | gather AH, CTX | decoder-LSTM slice -> DH | gather
 //   main:    [gate word of MEL(t) -> stop?]  location features (they depend only on the previous
@@ -1270,6 +1276,25 @@ __global__ __launch_bounds__(NTC) void k_decoder_coop(DecArgs p) {
 // Every word is written once per frame and a writer reaches frame t+1 only through gathers that
 // required all its readers to have consumed frame t, so single buffers suffice.  Sums are in a fixed
 // order and every value has exactly one producer, so all roles see identical bits and stop together.
+//
+// The worker stages (LEGACY = false; FACPPG_DECODER_STEP=legacy keeps the stages up to round 19, two barriers inside every
+// matvec, ~15 per frame).  A row's 32 K parts sit in one half-wave and meet by DPP adds and lane reads (stat_row_sum): a matvec
+// has no LDS array and no barrier of its own.  Six block barriers per frame remain, each for a read-after-write through LDS:
+//   A  behind the gate word -> s_stop and the X1 gather -> p1   (one wait: X1 is published ahead of the stop check by every
+//      prenet worker for every utterance alive so far, so gathering it before the check cannot wait for a missing word)
+//   B  behind the X2 gather -> in_att[0:P]
+//   C  behind the attention LSTM's 16 gate-row sums -> gs, which threads 0..3 combine per unit (a unit's four gate rows lie in
+//      four waves)
+//   D  behind the AH and CTX gathers -> in_att, in_dec, in_proj
+//   E  as C for the decoder LSTM        F  behind the DH gather -> in_dec, in_proj
+// Write-after-read, single buffers: every LDS vector is read by ONE matvec per frame, and at least one of A-F lies between
+// that matvec and the next gather that writes the vector -- p1: read before B, written before A of the next frame (C-F
+// between); in_att[0:P]: read before C, written before B of the next frame; in_att[P:], in_dec[:A+E]: read before C / E,
+// written behind C of the same / the next frame; in_dec[A+E:], in_proj[:D]: read before E / A, written behind E; in_proj[D:]:
+// read before A, written behind C.  gs: written before C (E), read behind it, written again behind D (behind F, A, B).
+// s_stop: written before A, read behind it, next written behind F.  No wave passes a barrier before all have arrived, so a
+// fast wave cannot overwrite what a slow one still reads.  The exchange words are untouched: same words, tags and publishers,
+// and a writer still reaches frame t+1 only through gathers of everything its readers publish behind consuming frame t.
 // ------------------------------------------------------------------------------------------
 constexpr int SU = 4, SSC = 4 * SU, SKP = NTC / SSC;   // 16 rows x 32 K parts per workgroup
 constexpr int SKR_LSTM = 40, SKR_PROJ = 32, SKR_P1 = 4, SKR_P2 = 12;   // columns per thread: K <= 1280 / 1024 / 128 / 384
@@ -1284,13 +1309,24 @@ __device__ __forceinline__ float xwait(const unsigned long long* w, unsigned tag
 // thread (row r = tid % 16, K part kp = tid / 16) keeps columns kp*KR .. kp*KR+KR-1 of row `row0 + r` of a
 // K-major matrix W[k][ld] (zero beyond nrows / K)
 template <int KRM>
-__device__ __forceinline__ void stat_load(float (&w)[KRM], const float* __restrict__ W, int ld, int row0, int nrows, int K, int tid) {
-  const int r = tid % SSC, kp = tid / SSC, KR = (K + SKP - 1) / SKP;
+__device__ __forceinline__ void stat_load_rk(float (&w)[KRM], const float* __restrict__ W, int ld, int row0, int nrows, int K, int r, int kp) {
+  const int KR = (K + SKP - 1) / SKP;
 #pragma unroll
   for (int i = 0; i < KRM; ++i) {
     const int k = kp * KR + i;
     w[i] = (i < KR && k < K && row0 + r < nrows) ? W[(size_t)k * ld + row0 + r] : 0.0f;
   }
+}
+template <int KRM>
+__device__ __forceinline__ void stat_load(float (&w)[KRM], const float* __restrict__ W, int ld, int row0, int nrows, int K, int tid) {
+  stat_load_rk(w, W, ld, row0, nrows, K, tid % SSC, tid / SSC);
+}
+// The wave layout of the same (row, K part) weight sets: all 32 K parts of a row in one half of a wave -- lane = kp + 32 * (row & 1),
+// wave = row >> 1 -- so that a row's sum needs no other wave (stat_mv_wave).
+__device__ __forceinline__ int stat_wave_row(int tid) { return ((tid >> 6) << 1) | ((tid >> 5) & 1); }
+template <int KRM>
+__device__ __forceinline__ void stat_load_wave(float (&w)[KRM], const float* __restrict__ W, int ld, int row0, int nrows, int K, int tid) {
+  stat_load_rk(w, W, ld, row0, nrows, K, stat_wave_row(tid), tid & 31);
 }
 // 16-row matvec from the register-resident stretch; the row sums land in part[256 .. 271] (after a barrier)
 template <int KRM>
@@ -1315,6 +1351,28 @@ __device__ __forceinline__ void stat_mv16(const float (&w)[KRM], int K, const fl
 }
 
 constexpr int SNU = 4;   // max utterances sharing one set of workers
+// A worker that has published its rows stays off the exchange words for SPLIT_PAUSE x 128 cycles (0.85 us at 2.4 GHz) before it
+// starts to poll them -- ahead of the gate / X1, X2, AH and DH gathers.  The words of one exchange are a few KB in a few L2 channels,
+// and 75 workgroups poll them with their eight waves: polls that start the moment the matvec ends (no barrier holds the waves back
+// any more) queue ahead of the very stores they wait for and of the main workgroup's query-weight stream.  Without the pause the
+// one-barrier stages make the FRAME slower than the legacy ones; with it they are faster, and faster than the legacy stages with
+// the same pause, in every launch shape (Tacotron2.inference alone, 200 frames, ms, medians of 12, two alternating rounds each,
+// round-to-round spread <= 0.03; `legacy` is the parent's code; profiles/r20_decoder_ab.txt section 7):
+//   B, NU, workgroups      legacy   legacy + pause 16   one-barrier, no pause   one-barrier + pause 16   + pause 24
+//   1, 1,  76               4.84         4.77                  4.93                    4.59                4.75
+//   2, 1, 152               5.05         4.89                  5.21                    4.73                4.86
+//   3, 1, 228               5.23         4.99                  5.40                    4.82                4.93
+//   2, 2,  77               6.40         6.34                  6.46                    6.31                6.35
+//   3, 3,  78               8.79         8.71                  8.42                    8.34                8.25
+//   8, 3, 234 (3 groups)    9.34         9.23                  9.02                    8.94                8.78
+// (legacy + pause 12 / 20 at B = 1: 4.76 / 4.88.)  The length was scanned at B = 1 only: no pause 4.85-4.93, 0.43 us 4.84, 0.53 us
+// 4.76, 0.64 us 4.55-4.69, 0.75 us 4.50-4.61, 0.85 us 4.51-4.59, 0.96 us 4.53-4.60, 1.07 us 4.55-4.65, 1.28 us 4.63-4.75, 1.7 us 4.87,
+// 2.6 us 5.37; each of the four pauses contributes (leaving one out: 4.54-4.77); a pause ahead of the context gather as well changes
+// nothing.  With NU = 3 a longer pause would gain another 1 %; one constant serves all shapes.  The batch-1 bench runs the streamed
+// path (the vocoder's seed passes under the decoder) and is the headline figure.  FACPPG_DECODER_PAUSE=n overrides (A/B runs; it
+// also gives the legacy stages, which have none by default, the same pauses).
+constexpr int SPLIT_PAUSE = 16;
+constexpr int SPLIT_QR = 24;   // query-weight rows (float4) a thread of the main workgroup holds per frame
 
 // The same for up to NU input vectors at once (in0 + u * ustride, utterances with their `alive` bit set): one
 // pass over the register-resident weights, one pair of barriers; row sums land in part[512 + 16 u .. ].
@@ -1357,7 +1415,83 @@ __device__ __forceinline__ void stat_mv16n(const float (&w)[KRM], int K, const f
   (void)alive;
 }
 
-template <int NU>
+// The sum of a row's 32 K-part sums in stat_load_wave's layout, in stat_mv16's order and shape: two quad-permute DPP adds form the
+// eight four-part values (p0 + p1) + (p2 + p3) that a legacy wave formed by shuffles, and they are added in a chain, j = 0 .. 7,
+// from 0.0f -- the operands and the order of every add are the legacy step's, so the bits are.  Every lane of the row's half-wave
+// returns the sum.  No LDS array, no barrier.
+__device__ __forceinline__ float stat_row_sum(float acc, int tid) {
+  acc += lane_mov<0xB1>(acc);   // quad_perm [1,0,3,2]: p(kp) + p(kp ^ 1)
+  acc += lane_mov<0x4E>(acc);   // quad_perm [2,3,0,1]: lane 4j holds (p(4j) + p(4j+1)) + (p(4j+2) + p(4j+3))
+  float s = 0.0f;
+#pragma unroll
+  for (int j = 0; j < SKP / 4; ++j) s += __shfl(acc, (tid & 32) + 4 * j);
+  return s;
+}
+// In the wave layout the 32 K parts of an operand vector are distinct addresses of one LDS read, so the vector is kept with K part kp
+// at kp * KRS floats: KRS = KR rounded up to a multiple of 4 whose quarter is odd.  A part is then read as float4 (a quarter of the
+// reads of the legacy stage, which is bound by their latency), and the 16 lanes of a ds_read_b128 lane group -- 16 K parts that are
+// distinct modulo 16 -- fall on 16 distinct 16-byte slots of the 256-byte bank row.  The padding stays zero.
+struct StatVec { int KR, KRS, M; };
+__host__ __device__ inline int stat_krs(int K) {
+  const int k4 = round_up((K + SKP - 1) / SKP, 4);
+  return (k4 >> 2) & 1 ? k4 : k4 + 4;
+}
+__device__ __forceinline__ StatVec stat_vec(int K) {
+  StatVec v;
+  v.KR = (K + SKP - 1) / SKP; v.KRS = stat_krs(K);
+  v.M = 65536 / v.KR + 1;   // (i * M) >> 16 == i / KR for i < 32 KR <= 1280, KR <= 40: i * (M KR - 65536) <= 1280 * 40 < 65536
+  return v;
+}
+// where element i of the vector is kept
+__device__ __forceinline__ int stat_slot(const StatVec& v, int i) { return i + ((i * v.M) >> 16) * (v.KRS - v.KR); }
+
+// floats of a worker's operand vectors per utterance (legacy: plain, with the unused xin; else padded)
+__host__ __device__ inline int split_ustride(int P, int E, int A, int D, int NF, bool legacy) {
+  return legacy ? (P + E + A) + (A + E + D) + (D + E) + round_up(NF, 4) + round_up(P, 4)
+                : SKP * (stat_krs(P + E + A) + stat_krs(A + E + D) + stat_krs(D + E) + stat_krs(P));
+}
+
+// stat_mv16n in the wave layout: s[u] = the sum of this thread's row for utterance u (0 for one that is not alive, NU > 2).  The
+// products and their order are stat_mv16's: one accumulator, ascending k (columns beyond KR meet zero weights, as there).
+template <int KRM, int NU>
+__device__ __forceinline__ void stat_mv_wave(const float (&w)[KRM], int KRS, const float* in0, int ustride, unsigned alive, float (&s)[NU],
+                                             int tid) {
+  static_assert(KRM % 4 == 0, "stat_mv_wave reads float4");
+  const int kb = (tid & 31) * KRS;
+  if constexpr (NU > 2) {   // (one vector at a time, as stat_mv16n)
+#pragma unroll
+    for (int u = 0; u < NU; ++u) {
+      s[u] = 0.0f;
+      if (alive >> u & 1) {
+        const float4* in = reinterpret_cast<const float4*>(in0 + (size_t)u * ustride + kb);
+        float acc = 0.0f;
+#pragma unroll
+        for (int j = 0; j < KRM / 4; ++j) {
+          const float4 v = in[j];
+          acc = fmaf(w[4 * j], v.x, acc); acc = fmaf(w[4 * j + 1], v.y, acc);
+          acc = fmaf(w[4 * j + 2], v.z, acc); acc = fmaf(w[4 * j + 3], v.w, acc);
+        }
+        s[u] = stat_row_sum(acc, tid);
+      }
+    }
+  } else {
+    float acc[NU];
+#pragma unroll
+    for (int u = 0; u < NU; ++u) acc[u] = 0.0f;
+#pragma unroll
+    for (int j = 0; j < KRM / 4; ++j)
+#pragma unroll
+      for (int u = 0; u < NU; ++u) {
+        const float4 v = reinterpret_cast<const float4*>(in0 + (size_t)u * ustride + kb)[j];
+        acc[u] = fmaf(w[4 * j], v.x, acc[u]); acc[u] = fmaf(w[4 * j + 1], v.y, acc[u]);
+        acc[u] = fmaf(w[4 * j + 2], v.z, acc[u]); acc[u] = fmaf(w[4 * j + 3], v.w, acc[u]);
+      }
+#pragma unroll
+    for (int u = 0; u < NU; ++u) s[u] = stat_row_sum(acc[u], tid);
+  }
+}
+
+template <int NU, bool LEGACY>
 __global__ __launch_bounds__(NTC) void k_decoder_split(DecArgs p) {
   extern __shared__ float sm[];
   __shared__ int s_stop[SNU];
@@ -1370,17 +1504,23 @@ __global__ __launch_bounds__(NTC) void k_decoder_split(DecArgs p) {
   if (tid < SNU) s_stop[tid] = 0;
   if (blk >= NU) {   // ------------------------------------------------ worker
     const int wg = blk - NU, unit0 = wg * SU, row0 = wg * SSC;
-    // per utterance: in_att [prenet | ctx | ah], in_dec [ah | ctx | dh], in_proj [dh | ctx], xin (previous mel
-    // frame), p1 (prenet layer-1 output); then 512 floats of reduction scratch
-    const int ustride = KA + KD + KP + round_up(p.NF, 4) + round_up(p.P, 4);
+    // per utterance: in_att [prenet | ctx | ah], in_dec [ah | ctx | dh], in_proj [dh | ctx], (legacy: xin, the previous mel
+    // frame, unused,) p1 (prenet layer-1 output); then 1024 floats of reduction scratch.  The one-barrier stages keep each
+    // vector in stat_vec's padded K-part layout.
+    const StatVec va = stat_vec(KA), vd = stat_vec(KD), vp = stat_vec(KP), v1 = stat_vec(p.P);
+    const int oD = LEGACY ? KA : SKP * va.KRS, oP = oD + (LEGACY ? KD : SKP * vd.KRS);
+    const int oP1 = oP + (LEGACY ? KP + round_up(p.NF, 4) : SKP * vp.KRS);
+    const int ustride = split_ustride(p.P, p.E, p.A, p.D, p.NF, LEGACY);
     float* part = sm + (size_t)NU * ustride;   // 1024 floats
     for (int i = tid; i < NU * ustride + 1024; i += NTC) sm[i] = 0.0f;
     if (tid < SNU * SU) { (&c_att[0][0])[tid] = 0.0f; (&c_dec[0][0])[tid] = 0.0f; }
     // w_p1 holds rows of W1.Wp (prenet layer 1 composed with the projection, k_fold_prenet): the prenet
     // starts from [dh | ctx] in the same stage as the projection, one exchange earlier
     float w_att[SKR_LSTM], w_dec[SKR_LSTM], w_proj[SKR_PROJ], w_p1[SKR_PROJ], w_p2[SKR_P2];
-    stat_load(w_att, p.att_w4 + (size_t)wg * KA * SSC, SSC, 0, SSC, KA, tid);
-    stat_load(w_dec, p.dec_w4 + (size_t)wg * KD * SSC, SSC, 0, SSC, KD, tid);
+    // (the same weight set per (row, K part) in both layouts; which thread holds it differs)
+#define SLOAD(w, ...) do { if constexpr (LEGACY) stat_load(w, __VA_ARGS__); else stat_load_wave(w, __VA_ARGS__); } while (0)
+    SLOAD(w_att, p.att_w4 + (size_t)wg * KA * SSC, SSC, 0, SSC, KA, tid);
+    SLOAD(w_dec, p.dec_w4 + (size_t)wg * KD * SSC, SSC, 0, SSC, KD, tid);
     // The projection + gate rows go to the workers BEHIND those that hold prenet rows (workers 19..24 with the reference's widths)
     // when there are enough of them: both matvecs start from the same [dh | ctx] and then run side by side instead of one after
     // the other in workers 0..5, the slowest link of every frame (worker 0: 2.3 us of its 11 us outside the attention).  Same rows,
@@ -1388,9 +1528,10 @@ __global__ __launch_bounds__(NTC) void k_decoder_split(DecArgs p) {
     const int pre_wk = (p.P + SSC - 1) / SSC, proj_wk = (p.NF + 1 + SSC - 1) / SSC;
     const int proj_w0 = pre_wk + proj_wk <= p.nwk ? pre_wk : 0;
     const int prow0 = (wg - proj_w0) * SSC;   // (negative: none)
-    stat_load(w_proj, p.proj_t, round_up(p.NF + 1, 4), prow0 < 0 ? p.NF + 1 : prow0, p.NF + 1, KP, tid);
-    stat_load(w_p1, p.w1p_t, round_up(p.P, 4), row0, p.P, KP, tid);
-    stat_load(w_p2, p.dp1_t, round_up(p.P, 4), row0, p.P, p.P, tid);
+    SLOAD(w_proj, p.proj_t, round_up(p.NF + 1, 4), prow0 < 0 ? p.NF + 1 : prow0, p.NF + 1, KP, tid);
+    SLOAD(w_p1, p.w1p_t, round_up(p.P, 4), row0, p.P, KP, tid);
+    SLOAD(w_p2, p.dp1_t, round_up(p.P, 4), row0, p.P, p.P, tid);
+#undef SLOAD
     const bool has_proj = prow0 >= 0 && prow0 < p.NF + 1, has_pre = row0 < p.P;
     unsigned alive = 0;   // bit u: utterance u of the group is still decoding (identical in every workgroup)
     for (int u = 0; u < NU; ++u)
@@ -1401,9 +1542,9 @@ __global__ __launch_bounds__(NTC) void k_decoder_split(DecArgs p) {
   const int b = grp * NU + u;                                                                           \
   unsigned long long* MEL = p.xsplit + (size_t)b * xstride;                                             \
   unsigned long long *X1 = MEL + p.NF + 1, *X2 = X1 + p.P, *AH = X2 + p.P, *CTX = AH + p.A, *DH = CTX + p.E; \
-  float* in_att = sm + (size_t)u * ustride; float* in_dec = in_att + KA; float* in_proj = in_dec + KD;  \
-  float* xin = in_proj + KP; float* p1 = xin + round_up(p.NF, 4);                                       \
-  (void)MEL; (void)X1; (void)X2; (void)AH; (void)CTX; (void)DH; (void)in_att; (void)in_dec; (void)in_proj; (void)xin; (void)p1
+  float* in_att = sm + (size_t)u * ustride; float* in_dec = in_att + oD; float* in_proj = in_att + oP;  \
+  float* p1 = in_att + oP1;                                                                             \
+  (void)MEL; (void)X1; (void)X2; (void)AH; (void)CTX; (void)DH; (void)in_att; (void)in_dec; (void)in_proj; (void)p1
     long long wtk = clock64();
 #define WPROF(slot)                                                       \
   if (p.prof && wg == 0 && grp == 0 && tid == 0) {                        \
@@ -1411,11 +1552,14 @@ __global__ __launch_bounds__(NTC) void k_decoder_split(DecArgs p) {
     p.prof[16 + slot] += now - wtk;                                       \
     wtk = now;                                                            \
   }
+    const int pause = p.pause;
+#define NAP() for (int k_ = 0; k_ < pause; ++k_) __builtin_amdgcn_s_sleep(2)
+    if constexpr (LEGACY)   // FACPPG_DECODER_STEP=legacy: the worker stages up to round 19, ~15 block barriers per frame
     for (int t = 0;; ++t) {
       const unsigned tag = t + 1;
       if (t > 0) {
         // projection + gate rows of frame t-1 (model.py:436-441); the stopping frame is kept (:524-528)
-        if (has_proj) stat_mv16n<SKR_PROJ, NU>(w_proj, KP, sm + KA + KD, ustride, alive, part, tid);
+        if (has_proj) stat_mv16n<SKR_PROJ, NU>(w_proj, KP, sm + oP, ustride, alive, part, tid);
         if (has_proj) FOR_ALIVE(u) {
           UTT(u);
           if (tid < SSC && prow0 + tid <= p.NF) {
@@ -1428,7 +1572,7 @@ __global__ __launch_bounds__(NTC) void k_decoder_split(DecArgs p) {
           }
         }
         // prenet layer 1 of frame t from the same [dh | ctx]: relu((W1 Wp) v + W1 bp), dropout  (model.py:132-135)
-        if (has_pre) stat_mv16n<SKR_PROJ, NU>(w_p1, KP, sm + KA + KD, ustride, alive, part, tid);
+        if (has_pre) stat_mv16n<SKR_PROJ, NU>(w_p1, KP, sm + oP, ustride, alive, part, tid);
         if (has_pre) FOR_ALIVE(u) {
           UTT(u);
           // (this runs ahead of the stop check below: an utterance that reaches max_steps comes here once more with t = max_steps,
@@ -1438,6 +1582,7 @@ __global__ __launch_bounds__(NTC) void k_decoder_split(DecArgs p) {
             xpub(X1 + row0 + tid, fmaxf(part[512 + u * SSC + tid] + p.b1p[row0 + tid], 0.0f) * (float)mk[row0 + tid] * 2.0f, tag);
         }
         WPROF(0)   // projection + prenet-1 rows
+        NAP();
         FOR_ALIVE(u) {
           UTT(u);
           if (tid == 0) s_stop[u] = sigm(xwait(MEL + p.NF, tag)) > p.gate_thr || t == dec_step_limit(p, b);
@@ -1454,7 +1599,7 @@ __global__ __launch_bounds__(NTC) void k_decoder_split(DecArgs p) {
         WPROF(1)   // gather gate + X1
       }
       // (frame 0: the go frame is zero and the prenet has no bias, so p1 = 0 as initialised)
-      if (has_pre) stat_mv16n<SKR_P2, NU>(w_p2, p.P, sm + KA + KD + KP + round_up(p.NF, 4), ustride, alive, part, tid);
+      if (has_pre) stat_mv16n<SKR_P2, NU>(w_p2, p.P, sm + oP1, ustride, alive, part, tid);
       if (has_pre) FOR_ALIVE(u) {
         UTT(u);
         const uint8_t* mk = p.masks + ((size_t)t * 2 * p.B + b) * p.P;
@@ -1462,6 +1607,7 @@ __global__ __launch_bounds__(NTC) void k_decoder_split(DecArgs p) {
           xpub(X2 + row0 + tid, fmaxf(part[512 + u * SSC + tid], 0.0f) * (float)mk[(size_t)p.B * p.P + row0 + tid] * 2.0f, tag);
       }
       WPROF(2)   // prenet-2 rows
+      NAP();
       FOR_ALIVE(u) {
         UTT(u);
         for (int i = tid; i < p.P; i += NTC) in_att[i] = xwait(X2 + i, tag);
@@ -1480,6 +1626,7 @@ __global__ __launch_bounds__(NTC) void k_decoder_split(DecArgs p) {
         }
       }
       WPROF(4)   // attention LSTM slice
+      NAP();
       FOR_ALIVE(u) {
         UTT(u);
         for (int i = tid; i < p.A; i += NTC) { const float h = xwait(AH + i, tag); in_att[p.P + p.E + i] = h; in_dec[i] = h; }
@@ -1495,7 +1642,7 @@ __global__ __launch_bounds__(NTC) void k_decoder_split(DecArgs p) {
       __syncthreads();
       WPROF(6)   // gather CTX (= the main workgroup's attention)
       // decoder LSTMCell slice on [ah | ctx | dh]  (model.py:425-428)
-      stat_mv16n<SKR_LSTM, NU>(w_dec, KD, sm + KA, ustride, alive, part, tid);
+      stat_mv16n<SKR_LSTM, NU>(w_dec, KD, sm + oD, ustride, alive, part, tid);
       FOR_ALIVE(u) {
         UTT(u);
         if (tid < SU && unit0 + tid < p.D) {
@@ -1505,6 +1652,7 @@ __global__ __launch_bounds__(NTC) void k_decoder_split(DecArgs p) {
                                    gs[3 * SU + tid] + p.dec_b[3 * p.D + un], &c_dec[u][tid]), tag);
         }
       }
+      NAP();
       FOR_ALIVE(u) {
         UTT(u);
         for (int i = tid; i < p.D; i += NTC) { const float h = xwait(DH + i, tag); in_dec[p.A + p.E + i] = h; in_proj[i] = h; }
@@ -1513,6 +1661,132 @@ __global__ __launch_bounds__(NTC) void k_decoder_split(DecArgs p) {
       __syncthreads();
       WPROF(8)
     }
+    else {
+    // The same stages in stat_load_wave's layout: a row's sum is formed inside its half-wave (stat_mv_wave), and the half-wave's
+    // first lane adds the bias, applies the legacy expression and publishes.  The barriers left are A-F below (see the hazard
+    // argument above the kernel); the words, their tags and their publishers are the legacy stages'.
+    const int wr = stat_wave_row(tid);
+    const bool head = (tid & 31) == 0;
+    float* gs_all = part + 512;   // [NU][16] gate-row sums of the LSTM stage at hand
+    float rs[NU];
+    for (int t = 0;; ++t) {
+      const unsigned tag = t + 1;
+      if (t > 0) {
+        // projection + gate rows of frame t-1 (model.py:436-441); the stopping frame is kept (:524-528)
+        if (has_proj) {
+          stat_mv_wave<SKR_PROJ, NU>(w_proj, vp.KRS, sm + oP, ustride, alive, rs, tid);
+          FOR_ALIVE(u) {
+            UTT(u);
+            if (head && prow0 + wr <= p.NF) {
+              const int row = prow0 + wr;
+              const float v = rs[u] + p.proj_b[row];
+              if (row < p.NF) {
+                p.mel[((size_t)b * p.NF + row) * p.max_steps + t - 1] = v;
+                if (p.melx) xpub(p.melx + (size_t)(t - 1) * p.NF + row, v, tag - 1);
+              } else { p.gate[(size_t)b * p.max_steps + t - 1] = v; xpub(MEL + row, v, tag); }   // only the gate crosses workgroups
+            }
+          }
+        }
+        // prenet layer 1 of frame t from the same [dh | ctx]: relu((W1 Wp) v + W1 bp), dropout  (model.py:132-135)
+        if (has_pre) {
+          stat_mv_wave<SKR_PROJ, NU>(w_p1, vp.KRS, sm + oP, ustride, alive, rs, tid);
+          FOR_ALIVE(u) {
+            UTT(u);
+            // (ahead of the stop check, as in the legacy stage: with t = max_steps the row is formed from the last step's mask and never read)
+            const uint8_t* mk = p.masks + ((size_t)min(t, p.max_steps - 1) * 2 * p.B + b) * p.P;
+            if (head && row0 + wr < p.P)
+              xpub(X1 + row0 + wr, fmaxf(rs[u] + p.b1p[row0 + wr], 0.0f) * (float)mk[row0 + wr] * 2.0f, tag);
+          }
+        }
+        WPROF(0)   // projection + prenet-1 rows
+        // the stop check and the X1 gather share one wait and one barrier: X1 of every utterance alive so far is published above,
+        // ahead of the check, by every prenet worker, so the gather cannot wait for a word that never comes; an utterance that
+        // stops here leaves a p1 nobody reads
+        NAP();
+        FOR_ALIVE(u) {
+          UTT(u);
+          if (tid == 0) s_stop[u] = sigm(xwait(MEL + p.NF, tag)) > p.gate_thr || t == dec_step_limit(p, b);
+          for (int i = tid; i < p.P; i += NTC) p1[stat_slot(v1, i)] = xwait(X1 + i, tag);
+        }
+        __syncthreads();   // A
+        for (int u = 0; u < NU; ++u)
+          if (s_stop[u]) alive &= ~(1u << u);
+        if (!alive) break;
+        WPROF(1)   // gather gate + X1
+      }
+      // (frame 0: the go frame is zero and the prenet has no bias, so p1 = 0 as initialised)
+      if (has_pre) {
+        stat_mv_wave<SKR_P2, NU>(w_p2, v1.KRS, sm + oP1, ustride, alive, rs, tid);
+        FOR_ALIVE(u) {
+          UTT(u);
+          const uint8_t* mk = p.masks + ((size_t)t * 2 * p.B + b) * p.P;
+          if (head && row0 + wr < p.P)
+            xpub(X2 + row0 + wr, fmaxf(rs[u], 0.0f) * (float)mk[(size_t)p.B * p.P + row0 + wr] * 2.0f, tag);
+        }
+      }
+      WPROF(2)   // prenet-2 rows
+      NAP();
+      FOR_ALIVE(u) {
+        UTT(u);
+        for (int i = tid; i < p.P; i += NTC) in_att[stat_slot(va, i)] = xwait(X2 + i, tag);
+      }
+      __syncthreads();   // B
+      WPROF(3)   // gather X2
+      // attention LSTMCell slice on [prenet | ctx | ah]  (model.py:400-403)
+      stat_mv_wave<SKR_LSTM, NU>(w_att, va.KRS, sm, ustride, alive, rs, tid);
+      FOR_ALIVE(u)
+        if (head) gs_all[u * SSC + wr] = rs[u];
+      __syncthreads();   // C
+      FOR_ALIVE(u) {
+        UTT(u);
+        if (tid < SU && unit0 + tid < p.A) {
+          const float* gs = gs_all + u * SSC;
+          const int un = unit0 + tid;
+          xpub(AH + un, lstm_point(gs[tid] + p.att_b[un], gs[SU + tid] + p.att_b[p.A + un], gs[2 * SU + tid] + p.att_b[2 * p.A + un],
+                                   gs[3 * SU + tid] + p.att_b[3 * p.A + un], &c_att[u][tid]), tag);
+        }
+      }
+      WPROF(4)   // attention LSTM slice
+      NAP();
+      FOR_ALIVE(u) {
+        UTT(u);
+        for (int i = tid; i < p.A; i += NTC) { const float h = xwait(AH + i, tag); in_att[stat_slot(va, p.P + p.E + i)] = h; in_dec[stat_slot(vd, i)] = h; }
+      }
+      WPROF(5)   // gather AH
+      FOR_ALIVE(u) {
+        UTT(u);
+        for (int i = tid; i < p.E; i += NTC) {
+          const float c = xwait(CTX + i, tag);
+          in_att[stat_slot(va, p.P + i)] = c; in_dec[stat_slot(vd, p.A + i)] = c; in_proj[stat_slot(vp, p.D + i)] = c;
+        }
+      }
+      __syncthreads();   // D
+      WPROF(6)   // gather CTX (= the main workgroup's attention)
+      // decoder LSTMCell slice on [ah | ctx | dh]  (model.py:425-428)
+      stat_mv_wave<SKR_LSTM, NU>(w_dec, vd.KRS, sm + oD, ustride, alive, rs, tid);
+      FOR_ALIVE(u)
+        if (head) gs_all[u * SSC + wr] = rs[u];
+      __syncthreads();   // E
+      FOR_ALIVE(u) {
+        UTT(u);
+        if (tid < SU && unit0 + tid < p.D) {
+          const float* gs = gs_all + u * SSC;
+          const int un = unit0 + tid;
+          xpub(DH + un, lstm_point(gs[tid] + p.dec_b[un], gs[SU + tid] + p.dec_b[p.D + un], gs[2 * SU + tid] + p.dec_b[2 * p.D + un],
+                                   gs[3 * SU + tid] + p.dec_b[3 * p.D + un], &c_dec[u][tid]), tag);
+        }
+      }
+      NAP();
+      FOR_ALIVE(u) {
+        UTT(u);
+        for (int i = tid; i < p.D; i += NTC) { const float h = xwait(DH + i, tag); in_dec[stat_slot(vd, p.A + p.E + i)] = h; in_proj[stat_slot(vp, i)] = h; }
+      }
+      WPROF(7)   // decoder LSTM slice + gather DH
+      __syncthreads();   // F
+      WPROF(8)
+    }
+    }
+#undef NAP
 #undef WPROF
 #undef FOR_ALIVE
 #undef UTT
@@ -1537,10 +1811,18 @@ __global__ __launch_bounds__(NTC) void k_decoder_split(DecArgs p) {
   // waiting for the workers (gate, then the attention LSTM's hidden state: ~10 us): the 180 KB stream's L2 latency, which was
   // 2.9 us of the 12.7 us attention, hides in that wait.  (Keeping them in registers for the whole utterance spills: 96 registers
   // next to the context's 48 and the kernel's 224 for the workers' LSTM slices.)
-  constexpr int QR = 24;
+  constexpr int QR = SPLIT_QR;
   const int q_ks = pick_ks<NTC>(L.ADp, p.A);
   const int q_ns = L.ADp >> 2, q_slot = tid % q_ns, q_part = tid / q_ns;
   const int q_k0 = (int)((long)q_part * p.A / q_ks), q_k1 = (int)((long)(q_part + 1) * p.A / q_ks);
+  // ... except the first q_res rows of every thread, which fit behind the stash in the LDS this workgroup has to spare (the host
+  // sizes it; 3 of the 19 live rows at Tin = 200: Tacotron2.inference 4.61 -> 4.55 ms with 0 -> 3 rows, FACPPG_DECODER_QRES caps it
+  // for A/B runs) and are loaded once per launch: [q_res][NTC] float4, each thread reads back its own
+  float4* qres = stash + 8 * NTC;
+  const int q_res = p.q_res;
+  for (int i = 0; i < q_res; ++i)
+    qres[i * NTC + tid] = (q_part < q_ks && q_k0 + i < q_k1) ? reinterpret_cast<const float4*>(p.q_t)[(size_t)(q_k0 + i) * q_ns + q_slot]
+                                                             : make_float4(0.f, 0.f, 0.f, 0.f);
   CtxRows crows;
 #pragma unroll
   for (int i = 0; i < CTX_SLOTS; ++i)
@@ -1570,8 +1852,8 @@ __global__ __launch_bounds__(NTC) void k_decoder_split(DecArgs p) {
     float4 wq[QR];
 #pragma unroll
     for (int i = 0; i < QR; ++i)
-      wq[i] = (q_part < q_ks && q_k0 + i < q_k1) ? reinterpret_cast<const float4*>(p.q_t)[(size_t)(q_k0 + i) * q_ns + q_slot]
-                                                           : make_float4(0.f, 0.f, 0.f, 0.f);
+      wq[i] = (i >= q_res && q_part < q_ks && q_k0 + i < q_k1) ? reinterpret_cast<const float4*>(p.q_t)[(size_t)(q_k0 + i) * q_ns + q_slot]
+                                                                         : make_float4(0.f, 0.f, 0.f, 0.f);
     PROF(2)
     if (t > 0) {
       if (tid == 0) s_stop[0] = sigm(xwait(MEL + p.NF, tag)) > p.gate_thr || t == dec_step_limit(p, b);
@@ -1586,6 +1868,9 @@ __global__ __launch_bounds__(NTC) void k_decoder_split(DecArgs p) {
     PROF(0)
     for (int i = tid; i < p.A; i += NTC) ah[i] = xwait(AH + i, tag);
     __syncthreads();
+#pragma unroll
+    for (int i = 0; i < QR; ++i)
+      if (i < q_res) wq[i] = qres[i * NTC + tid];   // the resident rows: the same values from LDS
     PROF(3)
     dec_attention<NTC, QR, true, true>(p, L, mem, pm, len, t, b, tid, true, true, wq, stash, crows, rows_on, CTX, tag);   // (publishes CTX)
     PROF(5)
@@ -1862,8 +2147,10 @@ extern "C" int facppg_taco_create(const facppg_taco_config* cfg, const float* ws
     // the neighbouring stages' kernels on other streams find a CU.  0 => the one-workgroup kernels run instead.
     int per_cu = 1;
     const struct { const void* fn; size_t lds; } coop_kernels[] = {
-        {(const void*)k_decoder_coop, 150 * 1024}, {(const void*)k_decoder_forced<false>, 150 * 1024}, {(const void*)k_decoder_forced<true>, 150 * 1024}, {(const void*)k_decoder_split<1>, 150 * 1024},
-        {(const void*)k_decoder_split<2>, 150 * 1024}, {(const void*)k_decoder_split<3>, 150 * 1024},
+        {(const void*)k_decoder_coop, 150 * 1024}, {(const void*)k_decoder_forced<false>, 150 * 1024}, {(const void*)k_decoder_forced<true>, 150 * 1024}, {(const void*)k_decoder_split<1, false>, 150 * 1024},
+        {(const void*)k_decoder_split<2, false>, 150 * 1024}, {(const void*)k_decoder_split<3, false>, 150 * 1024},
+        {(const void*)k_decoder_split<1, true>, 150 * 1024}, {(const void*)k_decoder_split<2, true>, 150 * 1024},
+        {(const void*)k_decoder_split<3, true>, 150 * 1024},
         {(const void*)k_bilstm_coop<32, 96, true>, 0}, {(const void*)k_bilstm_coop<64, 152, true>, 0},
         {(const void*)k_bilstm_coop<32, 96, false>, 0}, {(const void*)k_bilstm_coop<64, 152, false>, 0}};
     for (const auto& k : coop_kernels) {
@@ -2268,6 +2555,7 @@ extern "C" int facppg_taco_decode(const facppg_taco* h, const float* memory_dev,
   // the previous batch, facppg.pipeline.synthesize_stream) bounds the CUs it takes away from them
   const int max_wgs = opts ? opts->max_workgroups : 0;
   const int wg_limit = max_wgs > 0 && max_wgs < h->coop_limit ? max_wgs : h->coop_limit;
+  int launch_step = 0;                   // split launch: 1 = one-barrier worker stages, 2 = FACPPG_DECODER_STEP=legacy
   int launch_mode = 0, launch_wgs = B;   // reported in opts: 0 k_decoder (one workgroup per utterance), 1 k_decoder_coop, 2 k_decoder_split
   const char* mode = getenv("FACPPG_DECODER_MODE");
   int variant = -1;
@@ -2290,7 +2578,8 @@ extern "C" int facppg_taco_decode(const facppg_taco* h, const float* memory_dev,
   static const char* no_split = getenv("FACPPG_DECODER_NO_SPLIT");
   const char* max_nu_env = getenv("FACPPG_DECODER_SPLIT_MAX_NU");
   const int max_nu = max_nu_env ? atoi(max_nu_env) : 3;   // 4 utterances per worker set only ties with the cooperative kernel (12.5 vs 12.4 ms at B = 12)
-  const size_t ustride = (size_t)(a.P + a.E + a.A) + (a.A + a.E + a.D) + (a.D + a.E) + round_up(a.NF, 4) + round_up(a.P, 4);
+  // (the larger of the two worker layouts, so that NU does not depend on FACPPG_DECODER_STEP)
+  const size_t ustride = std::max(split_ustride(a.P, a.E, a.A, a.D, a.NF, true), split_ustride(a.P, a.E, a.A, a.D, a.NF, false));
   int NU = 0;
   for (int nu = 1; nu <= SNU && nu <= max_nu && !NU; ++nu)
     if ((long)((B + nu - 1) / nu) * (h->split_nwk + nu) <= wg_limit && (nu * ustride + 1024) * 4 <= 150 * 1024) NU = nu;
@@ -2304,10 +2593,22 @@ extern "C" int facppg_taco_decode(const facppg_taco* h, const float* memory_dev,
     a.w1p_t = h->w1p_t; a.b1p = h->b1p;
     FACPPG_HIP_CHECK(hipMemsetAsync(ws + w.xchg, 0, w.total - w.xchg, s));
     size_t ssm = (NU * ustride + 1024) * 4;
-    const size_t main_smem = (round_up((int)(smem / 4), 4) + (size_t)8 * NTC * 4) * 4;   // + attn_energy_pre's stash
+    size_t main_smem = (round_up((int)(smem / 4), 4) + (size_t)8 * NTC * 4) * 4;   // + attn_energy_pre's stash
+    // FACPPG_DECODER_STEP=legacy: the worker stages up to round 19 (read per call: the tests flip it)
+    const char* step_env = getenv("FACPPG_DECODER_STEP");
+    const bool legacy_step = step_env && !strcmp(step_env, "legacy");
+    launch_step = legacy_step ? 2 : 1;
+    const void* fn = legacy_step ? (NU == 1 ? (const void*)k_decoder_split<1, true> : NU == 2 ? (const void*)k_decoder_split<2, true>
+                                    : NU == 3 ? (const void*)k_decoder_split<3, true> : (const void*)k_decoder_split<4, true>)
+                                 : (NU == 1 ? (const void*)k_decoder_split<1, false> : NU == 2 ? (const void*)k_decoder_split<2, false>
+                                    : NU == 3 ? (const void*)k_decoder_split<3, false> : (const void*)k_decoder_split<4, false>);
+    // ... + as many of the main workgroup's query-weight rows (one float4 per thread each) as the rest of the LDS holds
+    const size_t lds_cap = 160 * 1024 - 1024, q_row = (size_t)NTC * 16;
+    const char* qres_env = getenv("FACPPG_DECODER_QRES");   // A/B runs: at most this many
+    a.q_res = legacy_step || main_smem > lds_cap ? 0 : (int)std::min<size_t>(SPLIT_QR, (lds_cap - main_smem) / q_row);
+    if (qres_env) a.q_res = std::max(0, std::min(a.q_res, atoi(qres_env)));
+    main_smem += a.q_res * q_row;
     if (ssm < main_smem) ssm = main_smem;
-    const void* fn = NU == 1 ? (const void*)k_decoder_split<1> : NU == 2 ? (const void*)k_decoder_split<2>
-                   : NU == 3 ? (const void*)k_decoder_split<3> : (const void*)k_decoder_split<4>;
     FACPPG_HIP_CHECK(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)ssm));
     void* args[] = {(void*)&a};
     const int groups = (B + NU - 1) / NU;
@@ -2315,6 +2616,8 @@ extern "C" int facppg_taco_decode(const facppg_taco* h, const float* memory_dev,
     unsigned long long* words = opts ? (unsigned long long*)opts->frame_words_dev : nullptr;
     a.melx = (B == 1 && words && opts->frame_words_frames >= max_steps) ? words : nullptr;
     a.dbg_flags = getenv("FACPPG_DECODER_NO_ROWS") ? 1 : 0;
+    const char* pause_env = getenv("FACPPG_DECODER_PAUSE");   // A/B runs: units of 128 cycles, 0 = none
+    a.pause = pause_env ? std::max(0, std::min(255, atoi(pause_env))) : legacy_step ? 0 : SPLIT_PAUSE;
     FACPPG_HIP_CHECK(launch_coop(fn, dim3(h->split_nwk + NU, groups), dim3(NTC), args, ssm, s));
     launch_mode = 2; launch_wgs = (h->split_nwk + NU) * groups;
     if (a.prof) {
@@ -2323,9 +2626,11 @@ extern "C" int facppg_taco_decode(const facppg_taco* h, const float* memory_dev,
       FACPPG_HIP_CHECK(hipStreamSynchronize(s));
       fprintf(stderr, "[facppg split decoder prof (main), shader cycles] location features %lld energy_pre %lld entering row %lld query weights requested %lld wait_gate %lld wait_ah %lld attention %lld | att: query %lld energy %lld softmax %lld update %lld context %lld\n",
               pr[6], pr[7], pr[14], pr[2], pr[0], pr[3], pr[5], pr[8], pr[10], pr[11], pr[12], pr[13]);
-      fprintf(stderr, "[facppg split decoder prof (worker 0), shader cycles] proj+prenet1 %lld | gather gate,X1 %lld | prenet2 %lld | gather X2 %lld | "
-              "att LSTM %lld | gather AH %lld | gather CTX %lld | dec LSTM + gather DH %lld | barrier %lld\n",
-              pr[16], pr[17], pr[18], pr[19], pr[20], pr[21], pr[22], pr[23], pr[24]);
+      // (with a pause, every gather phase but CTX's begins with it; with the one-barrier stages "att LSTM" and "dec LSTM" include barriers C and E)
+      const char* pz = a.pause ? "pause+" : "";
+      fprintf(stderr, "[facppg split decoder prof (worker 0, %s stages, pause %d x 128 cycles), shader cycles] proj+prenet1 %lld | %sgather gate,X1 %lld | prenet2 %lld | %sgather X2 %lld | "
+              "att LSTM %lld | %sgather AH %lld | gather CTX %lld | dec LSTM + %sgather DH %lld | barrier %lld\n",
+              legacy_step ? "legacy" : "one-barrier", a.pause, pr[16], pz, pr[17], pr[18], pz, pr[19], pr[20], pz, pr[21], pr[22], pz, pr[23], pr[24]);
     }
   } else
   if (coop) {
@@ -2355,7 +2660,7 @@ extern "C" int facppg_taco_decode(const facppg_taco* h, const float* memory_dev,
     k_decoder<<<B, NT, smem, s>>>(a);
   }
   FACPPG_HIP_CHECK(hipGetLastError());
-  if (opts) { opts->mode = launch_mode; opts->workgroups = launch_wgs; opts->streamed = a.melx != nullptr; }
+  if (opts) { opts->mode = launch_mode; opts->workgroups = launch_wgs; opts->streamed = a.melx != nullptr; opts->step = launch_step; }
   return FACPPG_OK;
 }
 
@@ -2507,7 +2812,7 @@ extern "C" int facppg_taco_decode_forced(const facppg_taco* h, const float* memo
     k_forced_outputs<<<(unsigned)((n + 255) / 256), 256, 0, s>>>(mg, mel_dev, gate_dev, B, NF, T);
   }
   FACPPG_HIP_CHECK(hipGetLastError());
-  if (opts) { opts->mode = 1; opts->workgroups = launch_wgs; opts->streamed = 0; }
+  if (opts) { opts->mode = 1; opts->workgroups = launch_wgs; opts->streamed = 0; opts->step = 0; }
   return FACPPG_OK;
 }
 

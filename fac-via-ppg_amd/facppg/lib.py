@@ -41,7 +41,7 @@ class TacoConfig(ctypes.Structure):
 class TacoDecodeOpts(ctypes.Structure):
     """facppg_taco_decode_opts (include/facppg.h): the inputs, then the launch report the call fills in."""
     _fields_ = [("max_workgroups", ctypes.c_int32), ("frame_words_dev", ctypes.c_void_p), ("frame_words_frames", ctypes.c_int32),
-                ("mode", ctypes.c_int32), ("workgroups", ctypes.c_int32), ("streamed", ctypes.c_int32)]
+                ("mode", ctypes.c_int32), ("workgroups", ctypes.c_int32), ("streamed", ctypes.c_int32), ("step", ctypes.c_int32)]
 
 
 class TacoAttentionBackwardArgs(ctypes.Structure):

@@ -601,7 +601,8 @@ int facppg_taco_encode(const facppg_taco* h, const float* ppg_dev, const int32_t
  *     visible once the launch has ended); otherwise nothing is published.
  *   Filled in by the call: mode = 0 one workgroup per utterance (k_decoder), 1 cooperative slices (k_decoder_coop), 2 split
  *     (k_decoder_split); workgroups = workgroups of that launch (of the last one when a large batch runs in chunks);
- *     streamed = 1 if the frames were published. */
+ *     streamed = 1 if the frames were published; step = which worker stages a split launch ran: 1 the one-barrier stages,
+ *     2 FACPPG_DECODER_STEP=legacy (0 for the other modes). */
 typedef struct facppg_taco_decode_opts {
   int32_t max_workgroups;       /* in: 0 = no bound */
   void* frame_words_dev;        /* in: NULL = publish nothing */
@@ -609,6 +610,7 @@ typedef struct facppg_taco_decode_opts {
   int32_t mode;                 /* out */
   int32_t workgroups;           /* out */
   int32_t streamed;             /* out */
+  int32_t step;                 /* out */
 } facppg_taco_decode_opts;
 int facppg_taco_decode(const facppg_taco* h, const float* memory_dev, const float* pm_dev,
                        const int32_t* lengths_dev, const int32_t* step_limits_dev,
