@@ -934,6 +934,16 @@ __device__ __forceinline__ void store_f4(float* g, const float4 v) {
   const f32x4s x = {v.x, v.y, v.z, v.w};
   *(FACPPG_AS1 f32x4s*)g = x;
 }
+// WT: a write-through (sc0 sc1) store -- the line goes on to memory now and does not stay dirty in this XCD's L2 for the write-back
+// at the end of the kernel to move.  (An asm store is not on hipcc's memory counters; nothing in a kernel here waits for a store.
+// The s_nop keeps the next instruction off the data registers until the store has read them.)
+template <bool WT>
+__device__ __forceinline__ void store_f4(float* g, const float4 v) {
+  if constexpr (WT) {
+    const f32x4s x = {v.x, v.y, v.z, v.w};
+    asm volatile("global_store_dwordx4 %0, %1, off sc0 sc1\n\ts_nop 1" : : "v"((FACPPG_AS1 f32x4s*)g), "v"(x));
+  } else store_f4(g, v);
+}
 __device__ __forceinline__ void store_f1(float* g, const float v) { *(__attribute__((address_space(1))) float*)g = v; }
 
 // ------------------------------------------------------------------------------------------
@@ -983,7 +993,7 @@ __device__ __forceinline__ void wn_edge_column(const WnArgs& p, const int ph, co
 }
 
 // q0: the tile's first frame, ncol: its live columns.  Every thread of the tile calls this (two barriers inside).
-template <int TW>
+template <int TW, bool WT = false>
 __device__ __forceinline__ void wn_edge_tile(const WnArgs& p, const int ph, const int q0, const int ncol, float* __restrict__ smem) {
   const int tid = threadIdx.x, lane = tid & 63, w8 = tid >> 6;
   const int hn = (p.fe_mode >> 1) + (p.fe_mode & 1);   // conditioning channels of the NEXT flow
@@ -1028,15 +1038,23 @@ __device__ __forceinline__ void wn_edge_tile(const WnArgs& p, const int ph, cons
       }
     }
     float* g = hd + (size_t)ch * p.Lp;
-    if (nv >= 4) store_f4(g, make_float4(v[0], v[1], v[2], v[3]));
+    if (nv >= 4) store_f4<WT>(g, make_float4(v[0], v[1], v[2], v[3]));
     else
       for (int k = 0; k < nv; ++k) store_f1(g + k, v[k]);
   }
 }
 
-template <bool LAST, int NCB, bool EF, bool SEED = false>
+// NS: the small-launch schedule (32-frame tiles; FACPPG_WN_SMALL=legacy runs NS = false).  Same operands, same MFMAs, same
+// order of every sum -- only when things are requested and how stores leave the CU differ:
+//   * the second GEMM's first operands (three ring sets of w2, its bias, the end-row image, the residual rows) are requested
+//     in front of the gate, whose arithmetic covers their L2 round trip; behind the K loop the weight ring is dead, so the
+//     requests take the registers it held
+//   * every 16-byte row segment the epilogue publishes (h_out, the end rows in `skip`, the fused edge's start-conv rows) is
+//     stored write-through, so the write-back at the end of the kernel finds nothing dirty
+template <bool LAST, int NCB, bool EF, bool SEED = false, bool NS = false>
 __device__ __forceinline__ void wn_layer8_tile(const WnArgs& p, const int lin, float* __restrict__ smem) {
   static_assert(!SEED || NCB == 1, "seeded tiles: 32 frames");
+  static_assert(!NS || (NCB == 1 && EF), "small-launch schedule: 32 frames, folded flow edges");
   constexpr int TNt = 32 * NCB;
   WN8_STAMP_DECL(0, blockIdx.x == 0, p.first ? 0 : LAST ? 2 : 1);
   const int tid = threadIdx.x, lane = tid & 63, w8 = tid >> 6, wq = w8 >> 1, sub = w8 & 1;
@@ -1172,14 +1190,6 @@ __device__ __forceinline__ void wn_layer8_tile(const WnArgs& p, const int lin, f
     __syncthreads();   // (ablation bit 1: no barrier per chunk -- racy, timing only)
   }
   WN8_STAMP(1);   // K loop
-  // gate -> LDS [256][TNt]
-#pragma unroll
-  for (int cb = 0; cb < NCB; ++cb)
-#pragma unroll
-    for (int r = 0; r < 16; ++r)
-      smem[k4_index(chb + 8 * (r >> 2) + (r & 3) + 4 * kh, cb * 32 + li, TNt)] = gate_tanh_sigmoid(acc[0][cb][r], acc[1][cb][r]);
-  __syncthreads();
-  WN8_STAMP(2);   // gate
   // res_skip 1x1 conv
   constexpr int NRB2 = EF ? (LAST ? 0 : 1) : LAST ? 1 : 2;   // EF: res rows only (image laid out like a LAST layer's 256 rows)
   constexpr bool ROWS256 = LAST || EF;
@@ -1189,40 +1199,63 @@ __device__ __forceinline__ void wn_layer8_tile(const WnArgs& p, const int lin, f
   // k_wn_layer16 -- wave w8 forms slice w8 of both 16-column blocks; its 32 bytes of the image are fetched here, ahead of
   // the second GEMM.  (One wave per column block doing all eight slices cost 3.9 us of a 75 us launch, six waves idle.)
   constexpr bool ESPLIT = EF && NCB == 1;
-  float4 es0, es1;
-  if constexpr (ESPLIT) {
-    const float4* wimg = reinterpret_cast<const float4*>(p.we) + w8 * 128 + lane * 2;
-    es0 = gld(wimg); es1 = gld(wimg + 1);
-  }
   constexpr bool HPRE = !LAST && NCB == 1;
+  float4 es0, es1;
   float4 hpre[HPRE ? 32 / RPL4 : 1];
-  if constexpr (HPRE) {
-    if (nvalid >= 4) {
-      const float* rb0 = p.h_in + (size_t)b * C * p.Lp + in_off;
-#pragma unroll
-      for (int i = 0; i < 32 / RPL4; ++i) hpre[i] = gld(reinterpret_cast<const float4*>(rb0 + (size_t)(chb + i * RPL4 + srow4) * p.Lp));
+  float4 b2v[NRB2 > 0 ? NRB2 : 1][4];
+  // w2 image: float4 index ((wq*nrb + rb4)*NG2 + g)*64 + lane, nrb = 2 (LAST) or 4
+  const float4* ap2 = p.w2 + (size_t)(ROWS256 ? wq * 2 + sub : wq * 4 + sub) * NG2 * 64 + lane;
+  auto load_a2 = [&](float4 (&a)[2], int g) __attribute__((always_inline)) {
+    a[0] = gld(ap2 + g * 64);
+    if constexpr (!ROWS256) a[1] = gld(ap2 + (size_t)2 * NG2 * 64 + g * 64);
+  };
+  // everything the second GEMM, the end rows and the epilogue read from memory (the K loop's ring `ar` and `stg` are dead)
+  auto request2 = [&]() __attribute__((always_inline)) {
+    if constexpr (ESPLIT) {
+      const float4* wimg = reinterpret_cast<const float4*>(p.we) + w8 * 128 + lane * 2;
+      es0 = gld(wimg); es1 = gld(wimg + 1);
     }
+    if constexpr (HPRE) {
+      if (nvalid >= 4) {
+        const float* rb0 = p.h_in + (size_t)b * C * p.Lp + in_off;
+#pragma unroll
+        for (int i = 0; i < 32 / RPL4; ++i) hpre[i] = gld(reinterpret_cast<const float4*>(rb0 + (size_t)(chb + i * RPL4 + srow4) * p.Lp));
+      }
+    }
+#pragma unroll
+    for (int rb = 0; rb < NRB2; ++rb)
+#pragma unroll
+      for (int q = 0; q < 4; ++q) b2v[rb][q] = gld(reinterpret_cast<const float4*>(p.b2 + (ROWS256 ? 0 : rb * C) + chb + 4 * kh + 8 * q));
+    if constexpr (NRB2 > 0) {
+#pragma unroll
+      for (int i = 0; i < RING - 1; ++i) load_a2(ar[i], i);
+    }
+  };
+  if constexpr (NS) {   // in front of the gate: its arithmetic covers the round trip
+    request2();
+    __builtin_amdgcn_sched_barrier(0);
   }
+  // gate -> LDS [256][TNt]
+#pragma unroll
+  for (int cb = 0; cb < NCB; ++cb)
+#pragma unroll
+    for (int r = 0; r < 16; ++r)
+      smem[k4_index(chb + 8 * (r >> 2) + (r & 3) + 4 * kh, cb * 32 + li, TNt)] = gate_tanh_sigmoid(acc[0][cb][r], acc[1][cb][r]);
+  __syncthreads();
+  WN8_STAMP(2);   // gate
+  if constexpr (!NS) request2();
 #pragma unroll
   for (int rb = 0; rb < NRB2; ++rb) {
 #pragma unroll
     for (int q = 0; q < 4; ++q) {
-      const float4 bv = gld(reinterpret_cast<const float4*>(p.b2 + (ROWS256 ? 0 : rb * C) + chb + 4 * kh + 8 * q));
+      const float4 bv = b2v[rb][q];
       acc[rb][0][4 * q + 0] = bv.x; acc[rb][0][4 * q + 1] = bv.y; acc[rb][0][4 * q + 2] = bv.z; acc[rb][0][4 * q + 3] = bv.w;
     }
 #pragma unroll
     for (int cb = 1; cb < NCB; ++cb) acc[rb][cb] = acc[rb][0];
   }
   if constexpr (NRB2 > 0) {
-    // w2 image: float4 index ((wq*nrb + rb4)*NG2 + g)*64 + lane, nrb = 2 (LAST) or 4
-    const float4* ap2 = p.w2 + (size_t)(ROWS256 ? wq * 2 + sub : wq * 4 + sub) * NG2 * 64 + lane;
     const float* lb = smem + (kh * TNt + li) * 4;
-    auto load_a2 = [&](float4 (&a)[2], int g) __attribute__((always_inline)) {
-      a[0] = gld(ap2 + g * 64);
-      if constexpr (!ROWS256) a[1] = gld(ap2 + (size_t)2 * NG2 * 64 + g * 64);
-    };
-#pragma unroll
-    for (int i = 0; i < RING - 1; ++i) load_a2(ar[i], i);
     for (int c = 0; c < NG2 / 8; ++c) {
 #pragma unroll
       for (int g = 0; g < 8; ++g) {
@@ -1297,7 +1330,7 @@ __device__ __forceinline__ void wn_layer8_tile(const WnArgs& p, const int lin, f
         float4 x = make_float4(bias, bias, bias, bias);
         if (!p.first) x = *reinterpret_cast<const float4*>(g);
         fs[0] = x.x + vv[0]; fs[1] = x.y + vv[1]; fs[2] = x.z + vv[2]; fs[3] = x.w + vv[3];
-        store_f4(g, make_float4(fs[0], fs[1], fs[2], fs[3]));
+        store_f4<NS>(g, make_float4(fs[0], fs[1], fs[2], fs[3]));
       } else {
 #pragma unroll
         for (int k = 0; k < 3; ++k)
@@ -1311,7 +1344,7 @@ __device__ __forceinline__ void wn_layer8_tile(const WnArgs& p, const int lin, f
   if constexpr (LAST && ESPLIT) {
     if (p.fe_mode) {   // (B = 1: the tile's first frame follows from its index alone)
       const int q0 = (p.flat_cols > 0 ? tile : tile % p.ntq) * TNt;
-      wn_edge_tile<TNt>(p, ph, q0, min(TNt, (p.t_valid ? p.t_valid[0] : p.T) - q0), smem);
+      wn_edge_tile<TNt, NS>(p, ph, q0, min(TNt, (p.t_valid ? p.t_valid[0] : p.T) - q0), smem);
     }
   }
   WN8_STAMP(6);   // fused flow edge (with the add into skip)
@@ -1341,7 +1374,7 @@ __device__ __forceinline__ void wn_layer8_tile(const WnArgs& p, const int lin, f
           else x = gld(reinterpret_cast<const float4*>(rbase + o));
           v.x += x.x; v.y += x.y; v.z += x.z; v.w += x.w;
         }
-        store_f4(gbase + o, v);
+        store_f4<NS>(gbase + o, v);
       } else {
         const float vv[4] = {v.x, v.y, v.z, v.w};
         for (int k = 0; k < nv; ++k) store_f1(gbase + o + k, vv[k] + (add ? gld(rbase + o + k) : 0.0f));
@@ -1351,10 +1384,10 @@ __device__ __forceinline__ void wn_layer8_tile(const WnArgs& p, const int lin, f
   WN8_STAMP(5);   // epilogue
 }
 
-template <bool LAST, int NCB, bool EF = false, bool SEED = false>
+template <bool LAST, int NCB, bool EF = false, bool SEED = false, bool NS = false>
 __global__ __launch_bounds__(512, NCB == 4 ? 2 : 4) void k_wn_layer8(WnArgs p) {
   extern __shared__ __attribute__((aligned(16))) float smem[];
-  wn_layer8_tile<LAST, NCB, EF, SEED>(p, (int)blockIdx.x, smem);
+  wn_layer8_tile<LAST, NCB, EF, SEED, NS>(p, (int)blockIdx.x, smem);
 }
 
 
@@ -1554,7 +1587,8 @@ __global__ __launch_bounds__(512, NCB <= 2 ? 4 : 2) void k_cond_seed(SeedArgs p)
 constexpr int TN16 = 16;
 
 // one 16-frame tile: phase ph, frames q0 .. q0 + 15 of utterance b
-template <bool LAST, bool EF>
+// WT: the epilogue's 16-byte row segments are stored write-through (the mixed launch's small-launch schedule, see wn_layer8_tile)
+template <bool LAST, bool EF, bool WT = false>
 __device__ __forceinline__ void wn_layer16_tile(const WnArgs& p, const int ph, const int b, const int q0, float* __restrict__ smem,
                                                 const bool stamp = false) {   // stamp: FACPPG_WN8_PROF builds, this workgroup reports
   const int tid = threadIdx.x, lane = tid & 63, w8 = tid >> 6;
@@ -1733,7 +1767,7 @@ __device__ __forceinline__ void wn_layer16_tile(const WnArgs& p, const int ph, c
           float4 x = make_float4(bias, bias, bias, bias);
           if (!p.first) x = *reinterpret_cast<const float4*>(g);
           fs[0] = x.x + vv[0]; fs[1] = x.y + vv[1]; fs[2] = x.z + vv[2]; fs[3] = x.w + vv[3];
-          store_f4(g, make_float4(fs[0], fs[1], fs[2], fs[3]));
+          store_f4<WT>(g, make_float4(fs[0], fs[1], fs[2], fs[3]));
         } else {
 #pragma unroll
           for (int k = 0; k < 3; ++k)
@@ -1745,7 +1779,7 @@ __device__ __forceinline__ void wn_layer16_tile(const WnArgs& p, const int ph, c
       }
     }
     if constexpr (LAST) {
-      if (p.fe_mode) wn_edge_tile<TN16>(p, ph, q0, min(TN16, nvalid), smem);
+      if (p.fe_mode) wn_edge_tile<TN16, WT>(p, ph, q0, min(TN16, nvalid), smem);
     }
   }
   WN8_STAMP(6);   // fused flow edge (with the add into skip)
@@ -1776,7 +1810,7 @@ __device__ __forceinline__ void wn_layer16_tile(const WnArgs& p, const int ph, c
           else x = *reinterpret_cast<const float4*>(rbase + o);
           v.x += x.x; v.y += x.y; v.z += x.z; v.w += x.w;
         }
-        store_f4(gbase + o, v);
+        store_f4<WT>(gbase + o, v);
       } else {
         const float vv[4] = {v.x, v.y, v.z, v.w};
         for (int k = 0; k < nv; ++k) gbase[o + k] = vv[k] + (add ? rbase[o + k] : 0.0f);
@@ -1807,7 +1841,7 @@ __global__ __launch_bounds__(512, 4) void k_wn_layer16(WnArgs p) {
 // the vocoder.  Per phase: n32 seeded tiles, then the 16-frame tiles from frame 32 * n32 on.  Both kinds of tile are the code of
 // the single-kind launches (wn_layer8_tile<SEED>, wn_layer16_tile): same sums in the same order, same bits.
 // ------------------------------------------------------------------------------------------
-template <bool LAST>
+template <bool LAST, bool NS>
 __global__ __launch_bounds__(512, 4) void k_wn_layer_mixed(WnArgs p32, WnArgs p16, int n32) {
   extern __shared__ __attribute__((aligned(16))) float smem[];
   const int lin = (int)blockIdx.x, nt = p32.nt;   // tiles per phase of this launch: n32 + the 16-frame tiles
@@ -1815,8 +1849,8 @@ __global__ __launch_bounds__(512, 4) void k_wn_layer_mixed(WnArgs p32, WnArgs p1
   if (p32.xcd_map == 1) { const int r = lin >> 3; ph = (r / nt) * 8 + (lin & 7); tile = r % nt; }
   else { ph = lin / nt; tile = lin % nt; }
   if (ph >= p32.P) return;
-  if (tile < n32) wn_layer8_tile<LAST, 1, true, true>(p32, lin, smem);
-  else wn_layer16_tile<LAST, true>(p16, ph, 0, 32 * n32 + (tile - n32) * TN16, smem, ph == 0 && tile == n32);
+  if (tile < n32) wn_layer8_tile<LAST, 1, true, true, NS>(p32, lin, smem);
+  else wn_layer16_tile<LAST, true, NS>(p16, ph, 0, 32 * n32 + (tile - n32) * TN16, smem, ph == 0 && tile == n32);
 }
 
 // ------------------------------------------------------------------------------------------
@@ -2397,7 +2431,7 @@ extern "C" int facppg_wg_create(const facppg_wg_config* cfg, const float* weight
   FACPPG_HIP_CHECK(hipSetDevice(device));
   facppg_wg* h = new (std::nothrow) facppg_wg();
   FACPPG_REQUIRE(h, FACPPG_EINVAL, "out of host memory");
-  h->cfg = *cfg; h->device = device; h->profiling = 0; h->ev_used = 0; h->ev_layers = 1; h->poll_limit = 0; h->n_cu = 0; h->last_tile = h->last_waves = h->last_tiles = 0; h->arena = nullptr;
+  h->cfg = *cfg; h->device = device; h->profiling = 0; h->ev_used = 0; h->ev_layers = 1; h->poll_limit = 0; h->n_cu = 0; h->last_tile = h->last_waves = h->last_tiles = 0; h->last_schedule = 0; h->arena = nullptr;
   wg_flow_channels(cfg, h->n_rem, h->n_half, h->early);
 
   // arena layout (bytes, 256-aligned pieces)
@@ -2733,6 +2767,12 @@ extern "C" int facppg_wg_last_launch_shape(const facppg_wg* h, int* tile_frames,
   return FACPPG_OK;
 }
 
+extern "C" int facppg_wg_last_layer_schedule(const facppg_wg* h, int* schedule) {
+  FACPPG_REQUIRE(h && schedule, FACPPG_EINVAL, "NULL argument");
+  *schedule = h->last_schedule;
+  return FACPPG_OK;
+}
+
 template <int H>
 static void launch_flow_end(bool early, bool qs, dim3 grid, hipStream_t s, const EdgeArgs& a) {
   const char* no4 = getenv("FACPPG_FLOW_END_NO4");   // (read per call: the tests flip it)
@@ -2765,6 +2805,7 @@ static int wg_infer_pm(facppg_wg* h, const float* mel_dev, const int32_t* T_vali
                        const float4* seeds = nullptr, int seeded_frames = 0, int T_layout = 0, void* const* flow_events = nullptr) {
   const facppg_wg_config& c = h->cfg;
   // ONE short utterance: the persistent launch (facppg_wgp.hip) -- same bits, no kernel boundary per layer
+  h->last_schedule = 0;
   if (!seeds && wgp_eligible(h, B, T, T_valid_dev)) return wgp_infer(h, mel_dev, z_dev, seed, sigma, T, audio_dev, ws, s);
   // T_layout >= T: the strides (frames per phase row) of buffers that were laid out before T was known -- the mel buffer and
   // the seeds of a streamed utterance -- while everything that is counted (positions, tiles, noise, samples) follows T itself
@@ -2889,6 +2930,13 @@ static int wg_infer_pm(facppg_wg* h, const float* mel_dev, const int32_t* T_vali
   // LAST layer's tiles run the inner flow edges themselves (wn_edge_tile).  FACPPG_WG_EDGE_FUSE=0: the separate launches.
   const char* fuse_env = getenv("FACPPG_WG_EDGE_FUSE");   // (read per call: the tests flip it)
   const bool fuse = fold && fqs && B == 1 && (tile16 || (narrow && w8mode != 0)) && (!fuse_env || atoi(fuse_env) != 0);
+  // 8-wave 32-frame tiles with folded flow edges run the small-launch schedule (wn_layer8_tile<..., NS>).  FACPPG_WN_SMALL=legacy:
+  // the schedule before it.  (Without the folded edges the second GEMM has twice the rows and its operands do not fit in front
+  // of the gate: those launches, FACPPG_WG_EDGE_FOLD=0, keep the legacy schedule.)
+  const char* small_env = getenv("FACPPG_WN_SMALL");   // (read per call: the tests flip it)
+  FACPPG_REQUIRE(!small_env || !*small_env || !strcmp(small_env, "legacy"), FACPPG_EINVAL, "FACPPG_WN_SMALL=%s: expected legacy", small_env);
+  const bool ns = !(small_env && *small_env);
+  h->last_schedule = narrow && w8mode != 0 ? (ns && fold ? 2 : 1) : 0;
   for (int k = nf - 1; k >= 0; --k) {
     // (streamed utterance: the seeds of this flow come from a pass that may still be running on another stream)
     if (flow_events && flow_events[k]) FACPPG_HIP_CHECK(hipStreamWaitEvent(s, (hipEvent_t)flow_events[k], 0));
@@ -2932,6 +2980,11 @@ static int wg_infer_pm(facppg_wg* h, const float* mel_dev, const int32_t* T_vali
     if (last) KERNEL_LAST<<<lgrid, THREADS, LDS, s>>>(a);              \
     else KERNEL_MID<<<lgrid, THREADS, LDS, s>>>(a);                    \
   } while (0)
+#define WN_LAUNCH_NS(SEED, LDS)   /* 8-wave 32-frame tiles, folded flow edges: small-launch or legacy schedule */                \
+  do {                                                                                                                         \
+    if (ns) WN_LAUNCH((k_wn_layer8<true, 1, true, SEED, true>), (k_wn_layer8<false, 1, true, SEED, true>), 512, LDS);         \
+    else WN_LAUNCH((k_wn_layer8<true, 1, true, SEED>), (k_wn_layer8<false, 1, true, SEED>), 512, LDS);                        \
+  } while (0)
       if (fold) {
         if (wide128) WN_LAUNCH((k_wn_layer8<true, 4, true>), (k_wn_layer8<false, 4, true>), 512, 131072 + 4096);
         else if (tile16) WN_LAUNCH((k_wn_layer16<true, true>), (k_wn_layer16<false, true>), 512, 16384 + 4096);
@@ -2942,11 +2995,13 @@ static int wg_infer_pm(facppg_wg* h, const float* mel_dev, const int32_t* T_vali
               WnArgs a16 = a;
               a16.w1 = i == 0 ? h->w1f_16[k] : h->w1_16[k][i]; a16.wc = h->wc_16[k][i]; a16.w2 = last ? h->w2_16[k][i] : h->w2r_16[k][i];
               a16.flat_cols = 0; a16.groups = nullptr;
-              if (last) k_wn_layer_mixed<true><<<lgrid, 512, 32768 + 8 * 1024, s>>>(a, a16, n32);
-              else k_wn_layer_mixed<false><<<lgrid, 512, 32768 + 8 * 1024, s>>>(a, a16, n32);
-            } else WN_LAUNCH((k_wn_layer8<true, 1, true, true>), (k_wn_layer8<false, 1, true, true>), 512, 32768 + 8 * 1024);
+              if (last && ns) k_wn_layer_mixed<true, true><<<lgrid, 512, 32768 + 8 * 1024, s>>>(a, a16, n32);
+              else if (last) k_wn_layer_mixed<true, false><<<lgrid, 512, 32768 + 8 * 1024, s>>>(a, a16, n32);
+              else if (ns) k_wn_layer_mixed<false, true><<<lgrid, 512, 32768 + 8 * 1024, s>>>(a, a16, n32);
+              else k_wn_layer_mixed<false, false><<<lgrid, 512, 32768 + 8 * 1024, s>>>(a, a16, n32);
+            } else WN_LAUNCH_NS(true, 32768 + 8 * 1024);
           } else if (w8mode == 0) WN_LAUNCH((k_wn_layer<true, 1, false, true, true>), (k_wn_layer<false, 1, false, true, true>), 256, 32768 + 1024);
-          else WN_LAUNCH((k_wn_layer8<true, 1, true>), (k_wn_layer8<false, 1, true>), 512, 32768 + 8 * 1024);   // + the end rows' 8 K-slice partials
+          else WN_LAUNCH_NS(false, 32768 + 8 * 1024);   // + the end rows' 8 K-slice partials
         } else if (w8mode == 2) WN_LAUNCH((k_wn_layer8<true, 2, true>), (k_wn_layer8<false, 2, true>), 512, 65536 + 2048);
         else WN_LAUNCH((k_wn_layer<true, 2, false, true, true>), (k_wn_layer<false, 2, false, true, true>), 256, 65536 + 2048);
       } else {
@@ -2957,6 +3012,7 @@ static int wg_infer_pm(facppg_wg* h, const float* mel_dev, const int32_t* T_vali
         } else if (w8mode == 2) WN_LAUNCH((k_wn_layer8<true, 2>), (k_wn_layer8<false, 2>), 512, 65536);
         else WN_LAUNCH((k_wn_layer<true, 2, false, true>), (k_wn_layer<false, 2, false, true>), 256, 65536);
       }
+#undef WN_LAUNCH_NS
 #undef WN_LAUNCH
       if (!last) hi ^= 1;
       if (h->profiling && last) FACPPG_HIP_CHECK(hipEventRecord(h->ev[h->ev_used++], s));
@@ -3063,7 +3119,7 @@ extern "C" int facppg_wg_infer(facppg_wg* h, const float* mel_dev, const int32_t
   // the chip's 512 workgroup slots 1.5 times (single short utterances), halving the per-layer latency
   const bool narrow = (long)(w.Lr / TN) * B < 768;
   const dim3 lgrid(narrow ? w.Lr / 32 : w.Lr / TN, B);
-  h->last_tile = narrow ? 32 : TN; h->last_waves = 4; h->last_tiles = (int)(lgrid.x * lgrid.y);
+  h->last_tile = narrow ? 32 : TN; h->last_waves = 4; h->last_tiles = (int)(lgrid.x * lgrid.y); h->last_schedule = 0;
   h->ev_layers = c.wn_layers;
   for (int k = nf - 1; k >= 0; --k) {
     for (int i = 0; i < c.wn_layers; ++i) {

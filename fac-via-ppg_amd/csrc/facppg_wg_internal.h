@@ -71,6 +71,7 @@ struct facppg_wg {
   int n_cu;
   facppg::WgpState* wgp;   // persistent small-launch path (facppg_wgp.hip), or null
   int last_tile, last_waves, last_tiles;   // shape of the WN layer launches of the most recent infer (facppg_wg_last_launch_shape)
+  int last_schedule;       // ... and the schedule of their 8-wave 32-frame tiles (facppg_wg_last_layer_schedule)
   facppg::Wg16State* w16;  // fp16 handle (facppg_wg_create_f16): its images live in `arena`, no fp32 image is kept
 };
 

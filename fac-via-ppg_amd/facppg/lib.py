@@ -152,6 +152,7 @@ def _declare(lib):
         "facppg_wg_set_profiling": (c.c_int, [vp, c.c_int]),
         "facppg_wg_last_layer_ms": (c.c_int, [vp, c.POINTER(f32), c.POINTER(c.c_int)]),
         "facppg_wg_last_launch_shape": (c.c_int, [vp, c.POINTER(c.c_int), c.POINTER(c.c_int), c.POINTER(c.c_int)]),
+        "facppg_wg_last_layer_schedule": (c.c_int, [vp, c.POINTER(c.c_int)]),
         "facppg_wg_seed_layout": (c.c_int, [vp, c.c_int, c.POINTER(c.c_int), c.POINTER(c.c_int), c.POINTER(sz)]),
         "facppg_wg_cond_seed": (c.c_int, [vp, vp, c.c_int, c.c_int, c.c_int, c.c_int, c.c_int, c.c_int, c.c_int, vp, sz, vp, c.c_int, vp, vp]),
         "facppg_wg_mel_pad": (c.c_int, [vp, vp, c.c_int, c.c_int, vp, vp]),

@@ -942,6 +942,16 @@ class WaveGlow(torch.nn.Module):
         _lib.check(query(h[0], c.byref(tile), c.byref(waves), c.byref(tiles)))
         return tile.value, waves.value, tiles.value
 
+    def last_layer_schedule(self):
+        """Schedule of the 8-wave 32-frame layer tiles of the most recent fp32 infer() / infer_seeded(): "small" (the default),
+        "legacy" (FACPPG_WN_SMALL=legacy) or None when the call ran no such tile (facppg_wg_last_layer_schedule)."""
+        h = self.__dict__.get("_facppg_handle")
+        if h is None:
+            raise _lib.FacppgError("last_layer_schedule: no inference has run on this model yet")
+        v = _lib.ctypes.c_int(0)
+        _lib.check(_lib.load().facppg_wg_last_layer_schedule(h[0], _lib.ctypes.byref(v)))
+        return {0: None, 1: "legacy", 2: "small"}[v.value]
+
     def invalidate_packed_weights(self):
         """Forget the packed MFMA weight images; the next infer()/forward() repacks from the live parameters."""
         self._release()

@@ -336,6 +336,12 @@ int facppg_wg_last_layer_ms(facppg_wg* h, float* avg_ms, int* n_launches);
  * Lets the parity tests assert WHICH instantiation of k_wn_layer (glow.py:154-175) they compared with the oracle. */
 int facppg_wg_last_launch_shape(const facppg_wg* h, int* tile_frames, int* waves, int* n_tiles);
 
+/* Schedule of the 8-wave 32-frame layer tiles of the most recent facppg_wg_infer / facppg_wg_infer_seeded on this handle:
+ * 2 = the small-launch schedule (second-GEMM operands requested ahead of the gate, write-through epilogue stores),
+ * 1 = the schedule before it (FACPPG_WN_SMALL=legacy in the environment, read per call), 0 = the call ran no such tile.
+ * Both schedules form the same sums in the same order: the outputs are equal bit for bit. */
+int facppg_wg_last_layer_schedule(const facppg_wg* h, int* schedule);
+
 /* ---- ONE utterance whose mel frames arrive over time (the metric's "batch = 1" case): the conditioning part of every WN
  * layer's gate GEMM ahead of the layers.  No reference counterpart as code -- the reference computes cond_layers[i](spect)
  * inside WN.forward (glow.py:154-175) on the upsampled mel (glow.py:253-259) -- but the same arithmetic: the fused layer
