@@ -93,6 +93,11 @@ class F0Config(ctypes.Structure):
         [(n, ctypes.c_float) for n in ("ballast", "voicing_cost", "freq_weight")]
 
 
+class AlignConfig(ctypes.Structure):
+    """facppg_align_config (include/facppg.h)."""
+    _fields_ = [("floor", ctypes.c_float), ("switch_cost", ctypes.c_float)]
+
+
 class SumSegment(ctypes.Structure):
     """facppg_sum_segment (include/facppg.h)."""
     _fields_ = [("data_dev", ctypes.c_void_p), ("outer_stride", ctypes.c_long), ("outer", ctypes.c_int), ("inner", ctypes.c_int),
@@ -242,6 +247,11 @@ def _declare(lib):
         "facppg_f0_track_batch": (c.c_int, [c.POINTER(F0Config), vp, vp, vp, c.c_int, vp, vp, vp, vp, sz, vp]),
         "facppg_f0_batch": (c.c_int, [c.POINTER(F0Config), vp, vp, vp, vp, vp, c.c_int, vp, vp, vp, vp, sz, vp]),
         "facppg_lf0_rows_padded": (c.c_int, [vp, vp, vp, c.c_int, c.c_int, sz, vp, vp]),
+        "facppg_ppg_emissions": (c.c_int, [c.POINTER(AlignConfig), vp, c.c_int, c.c_int, c.c_int, vp, vp, vp, vp, vp, vp]),
+        "facppg_ppg_decode_phones_workspace_bytes": (sz, [c.c_int, c.c_int]),
+        "facppg_ppg_decode_phones": (c.c_int, [c.POINTER(AlignConfig), vp, vp, vp, c.c_int, c.c_int, vp, vp, vp, sz, vp]),
+        "facppg_ppg_force_align_workspace_bytes": (sz, [c.c_int, c.c_int]),
+        "facppg_ppg_force_align": (c.c_int, [vp, vp, vp, vp, vp, c.c_int, c.c_int, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, sz, vp]),
     }
     for name, (res, args) in sigs.items():
         fn = getattr(lib, name)      # AttributeError here = header/library mismatch

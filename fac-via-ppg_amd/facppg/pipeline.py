@@ -64,18 +64,19 @@ class Synthesizer(object):
         kw.setdefault("vocoder_stream", self.vocoder_stream)
         return synthesize_wavs(wavs, self._deps(ppg_deps), self.tacotron, self.waveglow, self.denoiser, sigma=sigma, strength=strength, **kw)
 
-    def convert_scored(self, wavs, ppg_deps=None, score_band=0, **kw):
+    def convert_scored(self, wavs, ppg_deps=None, score_band=0, phones=False, **kw):
         """convert() plus facppg.score.roundtrip of what it made: (waveforms, mel lengths, scores).  The waveforms are convert()'s
         for the same keywords, bit for bit; the scores are roundtrip(wavs, waveforms, hparams.sampling_rate, ppg_deps,
-        band=score_band) -- the converted audio goes back through the front end next to the teacher's and the two monophone PPGs
-        are aligned on the device.  Dependencies without the pdf -> monophone matrix are refused before anything runs."""
+        band=score_band, phones=phones) -- the converted audio goes back through the front end next to the teacher's and the two
+        monophone PPGs are aligned on the device; with ``phones`` the scores also say per teacher phone where it landed
+        (facppg.align.phone_report).  Dependencies without the pdf -> monophone matrix are refused before anything runs."""
         from facppg import score
         _checked_wav_list(wavs, kw.get("ppgs"), "Synthesizer.convert_scored")
         deps = self._deps(ppg_deps)
         score.check_roundtrip_deps(deps, "Synthesizer.convert_scored")
         host = not kw.pop("return_device", False)
         audio, tout = self.convert(wavs, deps, return_device=True, **kw)
-        scores = score.roundtrip(wavs, audio, self.hparams.sampling_rate, deps, band=score_band)
+        scores = score.roundtrip(wavs, audio, self.hparams.sampling_rate, deps, band=score_band, phones=phones)
         if host:
             audio = [a.cpu().numpy() for a in audio]
         return audio, tout, scores

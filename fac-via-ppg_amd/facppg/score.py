@@ -10,6 +10,9 @@ the number of cells whose top classes agree.
   distance   cost / steps: the mean squared Hellinger distance along the path; 0 = the same phones
   agreement  agree / steps: the share of path cells whose top class matches
   stretch    steps / max(la, lb): 1.0 = a path with no stalls beyond the length difference
+
+Three numbers per utterance do not say WHICH phones were lost: ``roundtrip(..., phones=True)`` adds facppg.align.phone_report's
+per-phone records from the same padded batch.
 """
 import numpy as np
 import torch
@@ -77,12 +80,15 @@ def check_roundtrip_deps(deps, what="roundtrip"):
                           "matrix (data/feats/reduce_dim.mat)" % what)
 
 
-def roundtrip(wavs, audio, sampling_rate, deps, band=0):
+def roundtrip(wavs, audio, sampling_rate, deps, band=0, phones=False):
     """wavs: the B teacher WaveData (common.feat.read_wav_kaldi), on the GPU.  audio: the conversion's samples per utterance --
     device tensors or host arrays [N_b], floats in [-1, 1] at ``sampling_rate`` (one rate, or one per utterance).  The audio is
     wrapped as WaveData in Kaldi's int16 range, teacher and converted audio go through ONE ppg.compute_ppg_padded pass of 2 B
     utterances (monophone classes; the front end downsamples as it does for any wav), and rows [:B] of that padded batch are
     scored against rows [B:].  Returns ppg_dtw's dict plus teacher_frames and roundtrip_frames.
+    phones: the scores gain "phones" (facppg.align.phone_report: per utterance one record per teacher phone -- where it landed in
+    the conversion and how well it is supported) and "phones_kept" [B], from the same padded batch: there is no further front-end
+    pass.
     Without ``deps.monophone_trans`` the call is refused on the host, before any device work."""
     from common.feat import WaveData
     from ppg.compute_ppg import compute_ppg_padded
@@ -101,6 +107,9 @@ def roundtrip(wavs, audio, sampling_rate, deps, band=0):
     with torch.no_grad():
         x, frames = compute_ppg_padded(list(wavs) + back, deps, is_full_ppg=False)
         scores = ppg_dtw(x[:B], frames[:B], x[B:], frames[B:], band=band)
+        if phones:
+            from facppg import align
+            scores["phones"], scores["phones_kept"] = align.phone_report(x[:B], frames[:B], x[B:], frames[B:])
     scores["teacher_frames"] = np.asarray(frames[:B], dtype=np.int32)
     scores["roundtrip_frames"] = np.asarray(frames[B:], dtype=np.int32)
     return scores

@@ -19,6 +19,11 @@ and hands its PPGs to the encoder on the device, so no PPG is ever held on the h
 With ``--score_file scores.tsv`` (and ``--wav_list``) every conversion is scored by its PPG round trip (facppg.score.roundtrip:
 the converted audio back through the front end, aligned with the teacher's PPG on the device): each rank scores its own batches
 and rank 0 writes one line per utterance, in list order.  The wavs do not depend on the flag.
+
+With ``--phone_file phones.tsv`` (and ``--wav_list``) the same round trip also says, per phone of the teacher, where it landed in
+the conversion (facppg.align.phone_report: the teacher's phone sequence decoded from its own PPG, the conversion force-aligned to
+it): one line per teacher phone, the utterances in list order; ``--phone_table FILE`` (``name index`` lines, data/arpa_phonemes)
+names the phones.  Neither the wavs nor the score file depend on the flag.
 """
 import argparse
 import os
@@ -77,6 +82,13 @@ def parse(argv=None):
     ap.add_argument('--score_band', type=int, default=0,
                     help="--score_file: half-width of the alignment's slanted band in frames of the longer side (0: no band; otherwise "
                          "at least 2)")
+    ap.add_argument('--phone_file', default=None,
+                    help='with --wav_list: run the PPG round trip and write one line per phone of the teacher, utterances in list order: '
+                         'path, index, phone, teacher_start, teacher_frames, start, frames, gop, share, kept (tab separated, frames of 10 ms, '
+                         'start -1: the phone was skipped; facppg.align.phone_report)')
+    ap.add_argument('--phone_table', default=None,
+                    help='--phone_file: a table of `name index` lines (data/arpa_phonemes) that names the phones; without it their class numbers '
+                         'are written')
     ap.add_argument('--hparams', default='',
                     help='comma separated "name=value" overrides of create_hparams_stage (train_ppg2mel.py:291-292), '
                          'e.g. n_symbols=40 for monophone PPGs (data_utils.py:253-258)')
@@ -85,6 +97,10 @@ def parse(argv=None):
         ap.error("--device_ppgs goes with --wav_list: PPGs read with --ppg_list are on the host already")
     if args.score_file and not args.wav_list:
         ap.error("--score_file goes with --wav_list: with --ppg_list there is no teacher audio to compare the conversion with")
+    if args.phone_file and not args.wav_list:
+        ap.error("--phone_file goes with --wav_list: with --ppg_list there is no teacher audio to compare the conversion with")
+    if args.phone_table and not args.phone_file:
+        ap.error("--phone_table names the phones of --phone_file")
     if args.score_band < 0 or args.score_band == 1:
         ap.error("--score_band must be 0 (no band) or at least 2 (got %d)" % args.score_band)
     return args
@@ -177,17 +193,22 @@ def synthesize_shard(synthesizer, ppgs, lengths, rank, world, args, wav_paths=No
 
 
 def score_shard(wavs, ids, paths, lengths, rank, world, args, deps):
-    """{global id: one line of the score file} for this rank's utterances: the teacher wavs of every batch synthesize_shard formed,
-    read again, against that batch's converted audio (still on the device)."""
+    """({global id: one line of the score file}, {global id: the lines of the phone file}) for this rank's utterances: the teacher
+    wavs of every batch synthesize_shard formed, read again, against that batch's converted audio (still on the device).  The
+    second dict is empty without --phone_file."""
     from common.feat import read_wav_kaldi
-    from facppg import score
+    from facppg import align, score
     made = dict(zip(ids, wavs))
-    lines = {}
+    names = align.read_phone_table(args.phone_table) if args.phone_table else None
+    lines, phone_lines = {}, {}
     for batch in shard.batches(shard.partition(lengths, world)[rank], lengths, args.batch_size):
-        scores = score.roundtrip([read_wav_kaldi(paths[i]) for i in batch], [made[i] for i in batch], FS, deps, band=args.score_band)
+        scores = score.roundtrip([read_wav_kaldi(paths[i]) for i in batch], [made[i] for i in batch], FS, deps, band=args.score_band,
+                                 phones=bool(args.phone_file))
         for b, i in enumerate(batch):
             lines[i] = score.score_line(paths[i], scores, b)
-    return lines
+            if args.phone_file:
+                phone_lines[i] = "\n".join(align.phone_lines(paths[i], scores["phones"][b], names))
+    return lines, phone_lines
 
 
 def collect_scores(lines, world):
@@ -259,13 +280,19 @@ def main(argv=None, synthesizer=None):
                                          is_full_ppg=hparams.is_full_ppg, append_f0=bool(hparams.is_append_f0))
         else:
             wavs, ids = synthesize_shard(synthesizer, ppgs, lengths, rank, world, args)
-        if args.score_file:
-            lines = collect_scores(score_shard(wavs, ids, paths, lengths, rank, world, args, ppg_dependencies(args)), world)
+        if args.score_file or args.phone_file:
+            lines, phone_lines = score_shard(wavs, ids, paths, lengths, rank, world, args, ppg_dependencies(args))
+            if args.score_file:            # (one gather per file that was asked for: a --score_file run exchanges what it always did)
+                lines = collect_scores(lines, world)
+            if args.phone_file:
+                phone_lines = collect_scores(phone_lines, world)
         gathered = collect(wavs, ids, world)
         if rank == 0:
             assert sorted(gathered) == list(range(len(paths))), "an utterance was lost or duplicated in the gather"
             if args.score_file:
                 write_scores(args.score_file, len(paths), lines)
+            if args.phone_file:
+                write_scores(args.phone_file, len(paths), phone_lines)
             return write_wavs(args.output_dir, paths, gathered)
         return None
     finally:

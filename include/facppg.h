@@ -1006,6 +1006,80 @@ int facppg_f0_batch(const facppg_f0_config* cfg, const float* wav_dev, const int
 int facppg_lf0_rows_padded(const float* f0_dev, const int32_t* frame_offsets_dev, const int32_t* frame_offsets_host,
                            int B, int Tmax, size_t batch_stride, float* out_dev, void* stream);
 
+/* ------------------------------------------------------------------------------------
+ * Per-phone report of a conversion: phone-loop decode and forced alignment of monophone PPGs (facppg.align: decode_phones,
+ * force_align, phone_report; score.roundtrip(phones=True)).  The reference has NO counterpart: its DataUtterance carries phone
+ * tiers and its align.py reads and writes TextGrids that an EXTERNAL aligner produced from a transcript; the wav -> wav path
+ * has neither.  Here the teacher's own phone sequence is decoded from its PPG and the conversion's PPG is aligned to it.  The
+ * two dynamic programs are therefore DEFINED here and the kernels are held to a float64 / float32 restatement of this text
+ * (tests/align_helpers.py).  All arithmetic is fp32 and every add is rounded on its own.
+ *
+ * Input: x_dev [B][D][Tmax], fp32, frames contiguous -- the layout facppg_tdnn_forward_batch_padded writes.  The lengths are
+ * the differences T_b of frame_offsets[B + 1], which come as a device copy (read by the kernels) next to a host copy
+ * (validated before the first launch); nothing behind a length is read (it may hold NaN).  Ragged per-frame arrays are laid
+ * end to end by frame_offsets, as the F0 entry points lay theirs; ragged per-state arrays by seq_offsets[B + 1].
+ *
+ * facppg_ppg_emissions -- one kernel, frame-major outputs, so that both DPs read a frame's row:
+ *   em_dev float [sum T][D]   em[t][k] = -logf(max(x[k][t], floor))      (finite by the floor, >= 0 for posteriors)
+ *   eb_dev float [sum T]      eb[t] = min_k em[t][k]
+ *   top_dev int32 [sum T]     top[t] = arg max_k x[k][t], the lowest k on a tie
+ * The transpose from channel-major to frame-major goes through an LDS tile: the reads of x and the writes of em are both
+ * coalesced.
+ *
+ * facppg_ppg_decode_phones -- the phone loop over the emissions, per utterance, T = T_b:
+ *   start          C(0,k) = em[0][k]
+ *   t >= 1         m = the first minimum of C(t-1,.), at class j;
+ *                  C(t,k) = em[t][k] + (m + switch_cost < C(t-1,k) ? m + switch_cost : C(t-1,k))      (strict <: a tie stays)
+ *                  back-pointer: k for a stay, j for a switch (one byte, in the workspace)
+ *   end            the first minimum of C(T-1,.), then a backtrace
+ *   outputs        labels_dev int32 [sum T], cost_dev float [B]
+ * switch_cost is a parameter of the definition that the user tunes (the price of one more phone), not a measurement.  One
+ * workgroup per utterance, one thread per class; D <= 64 (40 monophones: the real case) is a single wave whose frame loop has
+ * no barrier.
+ *
+ * facppg_ppg_force_align -- utterance b has the states s = 0 .. S_b - 1 (seq_offsets), state s of class seq[s] in [0, D) and
+ * with the flag optional[s] (one byte, 0 or not 0):
+ *   start          C(0,0) = em[0][seq[0]]; if state 0 is optional also C(0,1) = em[0][seq[1]]; every other state +inf
+ *   t >= 1         predecessors tried in the order stay (s), advance (s-1), skip (s-2, admissible only when state s-1 is
+ *                  optional) with a strict <; the local cost em[t][seq[s]] is added to the winner
+ *   end            state S-1; if S-1 is optional and C(T-1,S-2) < C(T-1,S-1): state S-2.  Then a backtrace over the
+ *                  back-pointers, one byte per (frame, state), in the workspace
+ *   +inf loses every strict comparison and +inf + em is +inf, so there is no second case, and no NaN can form
+ *   per state [sum S]   start_dev int32 (first frame; -1 for a skipped optional state), frames_dev int32,
+ *                  hits_dev int32 = the segment's frames with top[t] == seq[s],
+ *                  gop_dev float = (sum over the segment's frames, in frame order, of (eb[t] - em[t][seq[s]])) / frames:
+ *                  at most 0, 0 where the phone is the top class on every one of its frames, 0 for a skipped state
+ *   per utterance [B]   cost_dev float, ok_dev int32.  An utterance with fewer frames than mandatory states has no path:
+ *                  ok = 0, cost = +inf, start = -1 and frames = hits = gop = 0 throughout.  That is not an error of the call.
+ * One workgroup per utterance, one thread per state; the neighbours' costs go through a two-slot LDS exchange (one write, two
+ * reads, one barrier per frame), S <= 64 is a single wave without a barrier in the frame loop.
+ *
+ * Refused, and nothing is launched: a NULL pointer, B or D < 1, offsets that do not start at 0 or do not increase, a length
+ * beyond Tmax, floor outside (0, 1], a negative switch_cost, a class outside [0, D), S_b < 1, two adjacent optional states --
+ * the skip reaches over one state only -- (FACPPG_EINVAL); D > 256 -- senone posteriors: reduce them to monophone classes
+ * first --, S_b > 1024, B > 65535 (FACPPG_EUNSUPPORTED); a workspace smaller than *_workspace_bytes: (sum T) D bytes for the
+ * decode, (sum T) max_b S_b bytes for the alignment (FACPPG_EWORKSPACE; 0 with facppg_last_error set for refused sizes).
+ * Plain grid launches on ``stream``: none cooperative, none waits on memory, no atomics; every loop is bounded by the lengths. */
+typedef struct facppg_align_config {
+  float floor;         /* 1e-10f */
+  float switch_cost;   /* 2.0f */
+} facppg_align_config;
+int facppg_ppg_emissions(const facppg_align_config* cfg, const float* x_dev, int B, int D, int Tmax,
+                         const int32_t* frame_offsets_dev, const int32_t* frame_offsets_host,
+                         float* em_dev, float* eb_dev, int32_t* top_dev, void* stream);
+size_t facppg_ppg_decode_phones_workspace_bytes(int total_frames, int D);
+int facppg_ppg_decode_phones(const facppg_align_config* cfg, const float* em_dev, const int32_t* frame_offsets_dev,
+                             const int32_t* frame_offsets_host, int B, int D, int32_t* labels_dev, float* cost_dev,
+                             void* ws_dev, size_t ws_bytes, void* stream);
+size_t facppg_ppg_force_align_workspace_bytes(int total_frames, int S_max);
+int facppg_ppg_force_align(const float* em_dev, const float* eb_dev, const int32_t* top_dev,
+                           const int32_t* frame_offsets_dev, const int32_t* frame_offsets_host, int B, int D,
+                           const int32_t* seq_dev, const int32_t* seq_host,
+                           const uint8_t* optional_dev, const uint8_t* optional_host,
+                           const int32_t* seq_offsets_dev, const int32_t* seq_offsets_host,
+                           int32_t* start_dev, int32_t* frames_dev, int32_t* hits_dev, float* gop_dev,
+                           float* cost_dev, int32_t* ok_dev, void* ws_dev, size_t ws_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
