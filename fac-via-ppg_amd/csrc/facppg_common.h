@@ -4,6 +4,7 @@
 
 #include <cstdarg>
 #include <cstdio>
+#include <cstdlib>
 
 #include "facppg.h"
 
@@ -34,6 +35,29 @@ typedef float f32x4 __attribute__((ext_vector_type(4)));
 constexpr int kWave = 64;  // CDNA wavefront
 
 __host__ __device__ inline int round_up(int x, int m) { return (x + m - 1) / m * m; }
+
+// The cooperating kernels (decoder, BiLSTM) need all their workgroups co-resident; hipLaunchCooperativeKernel checks that the
+// grid fits, and the callers size their grids from the occupancy calculator.  (The persistent vocoder's launch in
+// facppg_wgp.hip and the vocoder handles' poll limit still carry their own copies of these two helpers.)
+// FACPPG_COOP_PLAIN=1 launches the SAME kernels with the same grids as ordinary launches (read per call): rocprofv3 on this
+// stack dies on cooperative launches, and an ordinary launch of a grid that fits an otherwise idle GPU is co-resident all the
+// same (every poll is bounded in wall-clock time: a launch that did not fit traps instead of hanging) -- the profiling mode of
+// tools/profile_coop.sh, not a production setting.
+inline hipError_t launch_coop(const void* fn, dim3 grid, dim3 block, void** args, size_t smem, hipStream_t s) {
+  const char* plain = getenv("FACPPG_COOP_PLAIN");
+  if (plain && atoi(plain) != 0) return hipLaunchKernel(fn, grid, block, args, smem, s);
+  return hipLaunchCooperativeKernel(fn, grid, block, args, smem, s);
+}
+
+// FACPPG_POLL_LIMIT (seconds a cooperative kernel may wait on one exchange word before it traps; default 20, 0 = never) in
+// ticks of the device's constant-rate clock; 0 = unbounded (also when the clock rate is unknown).
+inline unsigned long long poll_limit_ticks(int device) {
+  const char* pl = getenv("FACPPG_POLL_LIMIT");
+  const double seconds = pl ? strtod(pl, nullptr) : 20.0;
+  int khz = 0;
+  (void)hipDeviceGetAttribute(&khz, hipDeviceAttributeWallClockRate, device);
+  return seconds > 0 && khz > 0 ? (unsigned long long)(seconds * 1e3 * khz) : 0ull;
+}
 
 // Frame / sample offsets of a batch of utterances laid end to end (host copy): B + 1 values, off[0] = 0, strictly increasing
 // (every utterance holds at least one element).

@@ -29,13 +29,14 @@
 #include <new>
 
 #include "facppg_gemm.h"
+#include "facppg_taco_plan.h"
 
 using namespace facppg;
 
 struct facppg_taco {
   facppg_taco_config c;
   int device;
-  int coop_limit;   // workgroups the cooperative (co-resident) kernels may use: from the occupancy calculator, see facppg_taco_create
+  TacoGeometry g;   // layer widths, slice widths, and coop_limit: the workgroups the cooperative (co-resident) kernels may use, see facppg_taco_create
   int wall_khz;              // the device's constant-rate clock (facppg_taco_collect_frames bounds its wait in it)
   char* arena;
   // encoder
@@ -46,13 +47,10 @@ struct facppg_taco {
   // decoder (k-major, rows padded to a multiple of 4)
   float *dp0_t, *dp1_t, *att_t, *att_b, *dec_t, *dec_b, *q_t, *proj_t, *proj_b;
   float *loc_conv, *loc_dense, *v;
-  // per-workgroup LSTM slices [NWG][K][4U] for k_decoder_coop, packed for three slice widths:
-  // U = 8 (38 workgroups/utterance, B <= 6), 20 (15, B <= 16), 40 (8, B <= 30), 75 (4, B <= 60), 150 (2, B <= 120)
+  // per-workgroup LSTM slices [NWG][K][4U] for k_decoder_coop, packed for the five slice widths g.coop_U
   float *att_coop[5], *dec_coop[5];
-  int coop_U[5], coop_nwg[5];
   float *att_w4, *dec_w4;          // 4-unit slices for k_decoder_split's workers
   float *w1p_t, *b1p;              // prenet layer 1 composed with the projection: [D+E][Pp] k-major, [Pp]
-  int split_nwk;
   // postnet
   float4* post[8];
   float *post_b[8], *post_scale[8], *post_shift[8];
@@ -64,19 +62,7 @@ struct facppg_taco {
 
 namespace {
 
-// The cooperating kernels (decoder, BiLSTM) need all their workgroups co-resident; hipLaunchCooperativeKernel checks that the grid
-// fits and the launches below size their grids from the occupancy calculator.  FACPPG_COOP_PLAIN=1 launches the SAME kernels with
-// the same grids as ordinary launches (read per call): rocprofv3 on this stack dies on cooperative launches, and an ordinary
-// launch of a grid that fits an otherwise idle GPU is co-resident all the same (every poll is bounded in wall-clock time:
-// a launch that did not fit traps instead of hanging) -- the profiling mode of tools/profile_coop.sh, not a production setting.
-hipError_t launch_coop(const void* fn, dim3 grid, dim3 block, void** args, size_t smem, hipStream_t s) {
-  const char* plain = getenv("FACPPG_COOP_PLAIN");
-  if (plain && atoi(plain) != 0) return hipLaunchKernel(fn, grid, block, args, smem, s);
-  return hipLaunchCooperativeKernel(fn, grid, block, args, smem, s);
-}
-
 constexpr int NT = 1024;  // threads of the one-workgroup-per-utterance persistent kernels (16 waves, <= 128 VGPRs)
-constexpr int NTC = 512;  // threads of a cooperative decoder workgroup (8 waves, <= 256 VGPRs: no spills, deeper loads in flight)
 
 __device__ __forceinline__ float sigm(float x) { return 1.0f / (1.0f + expf(-x)); }
 // tanh through one hardware exponential and one reciprocal (relative error ~1e-6; |x| > 9.02 is +-1 in
@@ -511,14 +497,6 @@ struct DecLds {
   float *in_att, *in_dec, *in_proj, *ac, *dc, *xin, *p1, *pq, *part, *feat, *lconv, *ldense, *vv, *wprev, *wcum, *en;
   int KA, KD, KP, ADp, NFp, Pp, G, AD32;
 };
-
-__host__ __device__ inline size_t dec_lds_floats(int P, int E, int A, int D, int NF, int AD, int NFIL, int KSZ, int Tin) {
-  // feat [32][64], lconv^T [2*KSZ (even)][32], ldense [32][ADp32], v / processed query [ADp32]
-  (void)NFIL;
-  const size_t ADp32 = round_up(AD, 32);
-  return (size_t)(P + E + A) + (A + E + D) + (D + E) + A + D + round_up(NF, 4) + round_up(P, 4) + ADp32 + 4096 +
-         64 * 32 + (size_t)round_up(2 * KSZ, 2) * 32 + 32 * ADp32 + ADp32 + 3 * (size_t)Tin;
-}
 
 __device__ __forceinline__ void dec_carve(const DecArgs& p, float* sm, DecLds& L) {
   L.G = 4 * p.A;
@@ -1296,8 +1274,7 @@ __global__ __launch_bounds__(NTC) void k_decoder_coop(DecArgs p) {
 // fast wave cannot overwrite what a slow one still reads.  The exchange words are untouched: same words, tags and publishers,
 // and a writer still reaches frame t+1 only through gathers of everything its readers publish behind consuming frame t.
 // ------------------------------------------------------------------------------------------
-constexpr int SU = 4, SSC = 4 * SU, SKP = NTC / SSC;   // 16 rows x 32 K parts per workgroup
-constexpr int SKR_LSTM = 40, SKR_PROJ = 32, SKR_P1 = 4, SKR_P2 = 12;   // columns per thread: K <= 1280 / 1024 / 128 / 384
+// (SU, SSC, SKP: 16 rows x 32 K parts per workgroup, and the SKR_* columns per thread: facppg_taco_plan.h)
 
 __device__ __forceinline__ void xpub(unsigned long long* w, float v, unsigned tag) {
   __hip_atomic_store(w, ((unsigned long long)tag << 32) | __float_as_uint(v), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -1350,29 +1327,7 @@ __device__ __forceinline__ void stat_mv16(const float (&w)[KRM], int K, const fl
   __syncthreads();
 }
 
-constexpr int SNU = 4;   // max utterances sharing one set of workers
-// A worker that has published its rows stays off the exchange words for SPLIT_PAUSE x 128 cycles (0.85 us at 2.4 GHz) before it
-// starts to poll them -- ahead of the gate / X1, X2, AH and DH gathers.  The words of one exchange are a few KB in a few L2 channels,
-// and 75 workgroups poll them with their eight waves: polls that start the moment the matvec ends (no barrier holds the waves back
-// any more) queue ahead of the very stores they wait for and of the main workgroup's query-weight stream.  Without the pause the
-// one-barrier stages make the FRAME slower than the legacy ones; with it they are faster, and faster than the legacy stages with
-// the same pause, in every launch shape (Tacotron2.inference alone, 200 frames, ms, medians of 12, two alternating rounds each,
-// round-to-round spread <= 0.03; `legacy` is the parent's code; profiles/r20_decoder_ab.txt section 7):
-//   B, NU, workgroups      legacy   legacy + pause 16   one-barrier, no pause   one-barrier + pause 16   + pause 24
-//   1, 1,  76               4.84         4.77                  4.93                    4.59                4.75
-//   2, 1, 152               5.05         4.89                  5.21                    4.73                4.86
-//   3, 1, 228               5.23         4.99                  5.40                    4.82                4.93
-//   2, 2,  77               6.40         6.34                  6.46                    6.31                6.35
-//   3, 3,  78               8.79         8.71                  8.42                    8.34                8.25
-//   8, 3, 234 (3 groups)    9.34         9.23                  9.02                    8.94                8.78
-// (legacy + pause 12 / 20 at B = 1: 4.76 / 4.88.)  The length was scanned at B = 1 only: no pause 4.85-4.93, 0.43 us 4.84, 0.53 us
-// 4.76, 0.64 us 4.55-4.69, 0.75 us 4.50-4.61, 0.85 us 4.51-4.59, 0.96 us 4.53-4.60, 1.07 us 4.55-4.65, 1.28 us 4.63-4.75, 1.7 us 4.87,
-// 2.6 us 5.37; each of the four pauses contributes (leaving one out: 4.54-4.77); a pause ahead of the context gather as well changes
-// nothing.  With NU = 3 a longer pause would gain another 1 %; one constant serves all shapes.  The batch-1 bench runs the streamed
-// path (the vocoder's seed passes under the decoder) and is the headline figure.  FACPPG_DECODER_PAUSE=n overrides (A/B runs; it
-// also gives the legacy stages, which have none by default, the same pauses).
-constexpr int SPLIT_PAUSE = 16;
-constexpr int SPLIT_QR = 24;   // query-weight rows (float4) a thread of the main workgroup holds per frame
+// (SNU, SPLIT_PAUSE with its measurements, SPLIT_QR: facppg_taco_plan.h)
 
 // The same for up to NU input vectors at once (in0 + u * ustride, utterances with their `alive` bit set): one
 // pass over the register-resident weights, one pair of barriers; row sums land in part[512 + 16 u .. ].
@@ -1427,15 +1382,8 @@ __device__ __forceinline__ float stat_row_sum(float acc, int tid) {
   for (int j = 0; j < SKP / 4; ++j) s += __shfl(acc, (tid & 32) + 4 * j);
   return s;
 }
-// In the wave layout the 32 K parts of an operand vector are distinct addresses of one LDS read, so the vector is kept with K part kp
-// at kp * KRS floats: KRS = KR rounded up to a multiple of 4 whose quarter is odd.  A part is then read as float4 (a quarter of the
-// reads of the legacy stage, which is bound by their latency), and the 16 lanes of a ds_read_b128 lane group -- 16 K parts that are
-// distinct modulo 16 -- fall on 16 distinct 16-byte slots of the 256-byte bank row.  The padding stays zero.
+// The wave layout of an operand vector (stat_krs, facppg_taco_plan.h): K part kp at kp * KRS floats.
 struct StatVec { int KR, KRS, M; };
-__host__ __device__ inline int stat_krs(int K) {
-  const int k4 = round_up((K + SKP - 1) / SKP, 4);
-  return (k4 >> 2) & 1 ? k4 : k4 + 4;
-}
 __device__ __forceinline__ StatVec stat_vec(int K) {
   StatVec v;
   v.KR = (K + SKP - 1) / SKP; v.KRS = stat_krs(K);
@@ -1444,12 +1392,6 @@ __device__ __forceinline__ StatVec stat_vec(int K) {
 }
 // where element i of the vector is kept
 __device__ __forceinline__ int stat_slot(const StatVec& v, int i) { return i + ((i * v.M) >> 16) * (v.KRS - v.KR); }
-
-// floats of a worker's operand vectors per utterance (legacy: plain, with the unused xin; else padded)
-__host__ __device__ inline int split_ustride(int P, int E, int A, int D, int NF, bool legacy) {
-  return legacy ? (P + E + A) + (A + E + D) + (D + E) + round_up(NF, 4) + round_up(P, 4)
-                : SKP * (stat_krs(P + E + A) + stat_krs(A + E + D) + stat_krs(D + E) + stat_krs(P));
-}
 
 // stat_mv16n in the wave layout: s[u] = the sum of this thread's row for utterance u (0 for one that is not alive, NU > 2).  The
 // products and their order are stat_mv16's: one accumulator, ascending k (columns beyond KR meet zero weights, as there).
@@ -1927,7 +1869,6 @@ __device__ __forceinline__ void forced_att_slice(const float* __restrict__ Wslic
 // REGW (up to 2 utterances): the chain workgroups are split_nwk = A / 4 of 4 units each and keep their attention-LSTM slice --
 // 16 gate rows x (E + A) / 32 columns per thread, k_decoder_split's worker layout (att_w4, stat_load / stat_mv16) -- IN REGISTERS
 // for the whole utterance: the chain's matvec streams nothing.
-constexpr int SKR_FA = 32;   // columns per thread: E + A <= 1024
 template <bool REGW>
 __global__ __launch_bounds__(NTC) void k_decoder_forced(DecArgs p, const float* __restrict__ xa /*[B][T][4A]*/,
                                                         float* __restrict__ hc /*[B][D + E][T]*/,
@@ -2160,7 +2101,7 @@ extern "C" int facppg_taco_create(const facppg_taco_config* cfg, const float* ws
       per_cu = std::min(per_cu, nb);
     }
     const int resident = n_cu * per_cu;
-    h->coop_limit = resident - resident / 16;
+    h->g = taco_geometry(*cfg, resident - resident / 16);
     // hipMemcpyToSymbol writes the CURRENT device's copy of the constant only, so the bound is uploaded once PER DEVICE (a
     // process-wide "done" flag left every later GPU of a multi-GPU process at 0 = unbounded); the set is mutex-guarded
     // because handles may be created from several host threads
@@ -2170,11 +2111,7 @@ extern "C" int facppg_taco_create(const facppg_taco_config* cfg, const float* ws
       std::lock_guard<std::mutex> lock(poll_mu);
       const bool known = device < 64 && ((poll_devices >> device) & 1ull);
       if (!known) {
-        const char* pl = getenv("FACPPG_POLL_LIMIT");
-        const double seconds = pl ? strtod(pl, nullptr) : 20.0;
-        int khz = 0;
-        FACPPG_HIP_CHECK(hipDeviceGetAttribute(&khz, hipDeviceAttributeWallClockRate, device));
-        const unsigned long long ticks = seconds > 0 && khz > 0 ? (unsigned long long)(seconds * 1e3 * khz) : 0ull;
+        const unsigned long long ticks = poll_limit_ticks(device);
         FACPPG_HIP_CHECK(hipMemcpyToSymbol(HIP_SYMBOL(g_poll_limit_ticks), &ticks, sizeof(ticks)));
         if (device < 64) poll_devices |= 1ull << device;
       }
@@ -2209,12 +2146,11 @@ extern "C" int facppg_taco_create(const facppg_taco_config* cfg, const float* ws
   o.dec = take((size_t)(A + E + D) * G * 4); o.dec_b = take((size_t)G * 4);
   o.q = take((size_t)A * ADp * 4);
   o.proj = take((size_t)(D + E) * NFp * 4); o.proj_b = take((size_t)NFp * 4);
-  const int CUs[5] = {8, 20, 40, 75, 150};
   for (int v = 0; v < 5; ++v) {
-    const int nwg = (A + CUs[v] - 1) / CUs[v];
-    o.attc[v] = take((size_t)nwg * (P + E + A) * 4 * CUs[v] * 4); o.decc[v] = take((size_t)nwg * (A + E + D) * 4 * CUs[v] * 4);
+    const int U = h->g.coop_U[v], nwg = h->g.coop_nwg[v];
+    o.attc[v] = take((size_t)nwg * (P + E + A) * 4 * U * 4); o.decc[v] = take((size_t)nwg * (A + E + D) * 4 * U * 4);
   }
-  const int nwk = (A + 3) / 4;   // k_decoder_split workers: 4 units each
+  const int nwk = h->g.split_nwk;   // k_decoder_split workers: 4 units each
   o.att4 = take((size_t)nwk * (P + E + A) * 16 * 4); o.dec4 = take((size_t)nwk * (A + E + D) * 16 * 4);
   o.w1p = take((size_t)(D + E) * Pp * 4); o.b1p = take((size_t)Pp * 4);
   o.lc = take((size_t)NFIL * 2 * KSZ * 4); o.ld = take((size_t)AD * NFIL * 4); o.v = take((size_t)AD * 4);
@@ -2294,14 +2230,14 @@ extern "C" int facppg_taco_create(const facppg_taco_config* cfg, const float* ws
   tr(src, h->dec_t, G, D, G, A + E); src += (size_t)G * D;
   k_add2<<<(G + 255) / 256, 256, 0, s>>>(src, src + G, h->dec_b, G); src += 2 * (size_t)G;
   for (int v = 0; v < 5; ++v) {
-    const int U = CUs[v], nwg = (A + U - 1) / U;
-    h->att_coop[v] = F(o.attc[v]); h->dec_coop[v] = F(o.decc[v]); h->coop_U[v] = U; h->coop_nwg[v] = nwg;
+    const int U = h->g.coop_U[v], nwg = h->g.coop_nwg[v];
+    h->att_coop[v] = F(o.attc[v]); h->dec_coop[v] = F(o.decc[v]);
     const size_t na = (size_t)nwg * (P + E + A) * 4 * U, nd = (size_t)nwg * (A + E + D) * 4 * U;
     k_pack_coop<<<(unsigned)((na + 255) / 256), 256, 0, s>>>(h->att_t, h->att_coop[v], P + E + A, A, U, nwg);
     k_pack_coop<<<(unsigned)((nd + 255) / 256), 256, 0, s>>>(h->dec_t, h->dec_coop[v], A + E + D, D, U, nwg);
   }
   {
-    h->att_w4 = F(o.att4); h->dec_w4 = F(o.dec4); h->split_nwk = nwk;
+    h->att_w4 = F(o.att4); h->dec_w4 = F(o.dec4);
     const size_t na = (size_t)nwk * (P + E + A) * 16, nd = (size_t)nwk * (A + E + D) * 16;
     k_pack_coop<<<(unsigned)((na + 255) / 256), 256, 0, s>>>(h->att_t, h->att_w4, P + E + A, A, 4, nwk);
     k_pack_coop<<<(unsigned)((nd + 255) / 256), 256, 0, s>>>(h->dec_t, h->dec_w4, A + E + D, D, 4, nwk);
@@ -2348,6 +2284,66 @@ extern "C" void facppg_taco_destroy(facppg_taco* h) {
 extern "C" size_t facppg_taco_workspace_bytes(const facppg_taco* h, int B, int Tin) {
   if (!h || B <= 0 || Tin <= 0) return 0;
   return tws_layout(h->c, B, Tin).total;
+}
+
+extern "C" int facppg_taco_coop_limit(const facppg_taco* h) { return h ? h->g.coop_limit : 0; }
+
+namespace {
+// plan -> kernel
+const void* bilstm_kernel(const BilstmPlan& p) {
+  static const void* const k[2][2] = {{(const void*)k_bilstm_coop<32, 96, false>, (const void*)k_bilstm_coop<32, 96, true>},
+                                      {(const void*)k_bilstm_coop<64, 152, false>, (const void*)k_bilstm_coop<64, 152, true>}};
+  return k[p.kind == BILSTM_COOP64][!p.legacy];
+}
+const void* split_kernel(const DecodePlan& p) {
+  static const void* const k[2][SNU] = {
+      {(const void*)k_decoder_split<1, true>, (const void*)k_decoder_split<2, true>, (const void*)k_decoder_split<3, true>,
+       (const void*)k_decoder_split<4, true>},
+      {(const void*)k_decoder_split<1, false>, (const void*)k_decoder_split<2, false>, (const void*)k_decoder_split<3, false>,
+       (const void*)k_decoder_split<4, false>}};
+  return k[p.step == 1][p.NU - 1];
+}
+}  // namespace
+
+// What the three entry points below would launch, from the same planning functions, without a handle or a device.
+extern "C" int facppg_taco_launch_plan(const facppg_taco_config* cfg, int coop_limit, int what, int B, int Tin, int steps,
+                                       int max_workgroups, facppg_taco_launch_report* out) {
+  if (int rc = taco_check(cfg)) return rc;
+  FACPPG_REQUIRE(out, FACPPG_EINVAL, "NULL argument");
+  FACPPG_REQUIRE(what >= FACPPG_TACO_PLAN_ENCODE && what <= FACPPG_TACO_PLAN_FORCED, FACPPG_EINVAL, "unknown call %d", what);
+  FACPPG_REQUIRE(B > 0 && Tin > 0 && steps > 0 && coop_limit >= 0 && max_workgroups >= 0, FACPPG_EINVAL,
+                 "bad B/Tin/steps/coop_limit/max_workgroups");
+  FACPPG_REQUIRE(Tin <= 8192 || what == FACPPG_TACO_PLAN_ENCODE, FACPPG_EUNSUPPORTED, "Tin > 8192 does not fit the decoder's LDS state");
+  const TacoGeometry g = taco_geometry(*cfg, coop_limit);
+  const TacoTuning t = taco_tuning_from_env();
+  facppg_taco_launch_report r = {};
+  r.launches = 1;
+  if (what == FACPPG_TACO_PLAN_ENCODE) {
+    const BilstmPlan p = plan_bilstm(g, B, t);
+    r.workgroups = p.grid[0] * p.grid[1] * p.grid[2]; r.first_utts = r.last_utts = B;
+    r.bilstm_kind = p.kind; r.bilstm_legacy = p.legacy;
+  } else if (what == FACPPG_TACO_PLAN_DECODE) {
+    const DecodePlan p = plan_decode(g, B, Tin, steps, max_workgroups, true, t);
+    FACPPG_REQUIRE(p.rc == FACPPG_OK, p.rc, "%s", p.msg);
+    r.mode = p.mode; r.workgroups = p.workgroups(); r.launches = p.launches; r.step = p.step; r.nu = p.NU;
+    r.first_utts = p.launches > 1 ? p.chunk : B; r.last_utts = p.last_nb;
+    for (int j = 0; j < 2; ++j) {
+      r.first_u[j] = p.mode == 2 ? SU : p.mode == 1 ? g.coop_U[p.v_full] : 0;
+      r.last_u[j] = p.mode == 2 ? SU : p.mode == 1 ? g.coop_U[p.v_last] : 0;
+    }
+    r.q_res = p.q_res; r.pause = p.pause; r.dbg_flags = p.dbg_flags; r.prof = p.prof;
+    r.lds_bytes = (int32_t)(p.mode == 2 ? p.lds_split : p.lds_state); r.streamed_possible = p.publish;
+  } else {
+    const ForcedPlan p = plan_forced(g, B, Tin, max_workgroups, t);
+    FACPPG_REQUIRE(p.rc == FACPPG_OK, p.rc, "%s", p.msg);
+    r.mode = 1; r.workgroups = p.workgroups(); r.launches = p.launches; r.regw = p.regw;
+    r.first_utts = p.launches > 1 ? p.chunk : B; r.last_utts = p.last_nb;
+    r.first_u[0] = p.regw ? SU : g.coop_U[p.vc]; r.first_u[1] = g.coop_U[p.vd];
+    r.last_u[0] = p.regw ? SU : g.coop_U[p.vc_last]; r.last_u[1] = g.coop_U[p.vd_last];
+    r.prof = p.prof; r.lds_bytes = (int32_t)p.lds;
+  }
+  *out = r;
+  return FACPPG_OK;
 }
 
 // Encoder.inference (model.py:237-249) + Attention.memory_layer (model.py:334); padded_batch: Encoder.forward (model.py:215-235),
@@ -2401,27 +2397,17 @@ static int taco_encode_impl(const facppg_taco* h, const float* ppg_dev, const in
   p.B = B; p.N = Tin; p.n_valid = lengths_dev; p.A = h->wih; p.M = 8 * H; p.Cin = E; p.X = cur; p.x_bs = (long)E * Tin; p.ldx = Tin;
   p.bias = h->lstm_b; p.C = xproj; p.c_bs = (long)Tin * 8 * H; p.ldc = 8 * H; p.c_transposed = 1;
   if (int rc = gemm_launch(p, s)) return rc;
-  // latency shapes: W_hh register-resident, sliced over co-resident workgroups per (utterance, direction):
-  // 32 units per workgroup (4 K parts of <= 96 columns) while they fit, else 64 units (2 K parts of <= 152)
-  const char* bilstm_mode = getenv("FACPPG_BILSTM_MODE");   // "single" forces the one-workgroup kernel, "wide" the 64-unit slices
-  const bool no_coop = bilstm_mode && !strcmp(bilstm_mode, "single");
-  const bool fit32 = (long)B * 2 * ((H + 31) / 32) <= h->coop_limit && (H + 3) / 4 <= 96 && !(bilstm_mode && !strcmp(bilstm_mode, "wide"));
-  const bool fit64 = (long)B * 2 * ((H + 63) / 64) <= h->coop_limit && (H + 1) / 2 <= 152;
-  if (!no_coop && (fit32 || fit64)) {
+  const BilstmPlan bp = plan_bilstm(h->g, B, taco_tuning_from_env());
+  if (bp.kind != BILSTM_SINGLE) {
     unsigned long long* xchg = (unsigned long long*)(ws + w.xchg);
     FACPPG_HIP_CHECK(hipMemsetAsync(xchg, 0, (size_t)B * 2 * 2 * H * 8, s));
-    // FACPPG_BILSTM_STEP=legacy: the three-barrier step (read per call: the tests flip it)
-    const char* step_env = getenv("FACPPG_BILSTM_STEP");
-    const bool legacy = step_env && !strcmp(step_env, "legacy");
     BilstmCoopArgs ba{xproj, h->whh_t[0], h->whh_t[1], lengths_dev, Tin, H, xchg, memory_dev, mem_cm};
     void* args[] = {(void*)&ba};
-    const void* fn = fit32 ? (legacy ? (const void*)k_bilstm_coop<32, 96, false> : (const void*)k_bilstm_coop<32, 96, true>)
-                           : (legacy ? (const void*)k_bilstm_coop<64, 152, false> : (const void*)k_bilstm_coop<64, 152, true>);
-    FACPPG_HIP_CHECK(launch_coop(fn, fit32 ? dim3((H + 31) / 32, 2, B) : dim3((H + 63) / 64, 2, B), dim3(NTC), args, 0, s));
+    FACPPG_HIP_CHECK(launch_coop(bilstm_kernel(bp), dim3(bp.grid[0], bp.grid[1], bp.grid[2]), dim3(NTC), args, 0, s));
   } else {
     const int KS = NT / H < H ? NT / H : H;
     const size_t smem = (size_t)(2 * H + (KS > 0 ? KS : 1) * 4 * H) * 4;
-    k_bilstm<<<dim3(2, B), NT, smem, s>>>(xproj, h->whh_t[0], h->whh_t[1], lengths_dev, Tin, H, memory_dev, mem_cm);
+    k_bilstm<<<dim3(bp.grid[0], bp.grid[1]), NT, smem, s>>>(xproj, h->whh_t[0], h->whh_t[1], lengths_dev, Tin, H, memory_dev, mem_cm);
   }
   // processed_memory = memory_layer(memory), time-major [B][Tin][AD]
   GemmArgs m;
@@ -2515,6 +2501,53 @@ extern "C" int facppg_attention_window_mask(const int32_t* lengths_dev, int B, i
   return FACPPG_OK;
 }
 
+namespace {
+// the DecArgs fields facppg_taco_decode and facppg_taco_decode_forced have in common; every other field zero
+DecArgs dec_args_common(const facppg_taco* h, const float* memory_dev, const float* pm_dev, const int32_t* lengths_dev,
+                        float* align_dev, int B, int Tin, int max_steps, long long* prof) {
+  const TacoGeometry& g = h->g;
+  DecArgs a = {};
+  a.dec_b = h->dec_b; a.q_t = h->q_t; a.loc_conv = h->loc_conv; a.loc_dense = h->loc_dense; a.v = h->v;
+  a.memory = memory_dev; a.pm = pm_dev; a.lengths = lengths_dev; a.align = align_dev; a.prof = prof;
+  a.B = B; a.Tin = Tin; a.E = g.E; a.P = g.P; a.A = g.A; a.D = g.D; a.AD = g.AD; a.NF = g.NF; a.NFIL = g.NFIL; a.KSZ = g.KSZ;
+  a.window = h->c.attention_window_size; a.max_steps = max_steps; a.gate_thr = h->c.gate_threshold;
+  return a;
+}
+
+// FACPPG_DECODER_PROF: the phase cycle counters a launch left behind, printed once it has ended
+int read_prof(const long long* prof_dev, long long* pr, int n, hipStream_t s) {
+  FACPPG_HIP_CHECK(hipMemcpyAsync(pr, prof_dev, n * sizeof(long long), hipMemcpyDeviceToHost, s));
+  FACPPG_HIP_CHECK(hipStreamSynchronize(s));
+  return FACPPG_OK;
+}
+int print_split_prof(const DecArgs& a, bool legacy_step, hipStream_t s) {
+  long long pr[32];
+  if (int rc = read_prof(a.prof, pr, 32, s)) return rc;
+  fprintf(stderr, "[facppg split decoder prof (main), shader cycles] location features %lld energy_pre %lld entering row %lld query weights requested %lld wait_gate %lld wait_ah %lld attention %lld | att: query %lld energy %lld softmax %lld update %lld context %lld\n",
+          pr[6], pr[7], pr[14], pr[2], pr[0], pr[3], pr[5], pr[8], pr[10], pr[11], pr[12], pr[13]);
+  // (with a pause, every gather phase but CTX's begins with it; with the one-barrier stages "att LSTM" and "dec LSTM" include barriers C and E)
+  const char* pz = a.pause ? "pause+" : "";
+  fprintf(stderr, "[facppg split decoder prof (worker 0, %s stages, pause %d x 128 cycles), shader cycles] proj+prenet1 %lld | %sgather gate,X1 %lld | prenet2 %lld | %sgather X2 %lld | "
+          "att LSTM %lld | %sgather AH %lld | gather CTX %lld | dec LSTM + %sgather DH %lld | barrier %lld\n",
+          legacy_step ? "legacy" : "one-barrier", a.pause, pr[16], pz, pr[17], pr[18], pz, pr[19], pr[20], pz, pr[21], pr[22], pz, pr[23], pr[24]);
+  return FACPPG_OK;
+}
+int print_coop_prof(const DecArgs& a, hipStream_t s) {
+  long long pr[16];
+  if (int rc = read_prof(a.prof, pr, 16, s)) return rc;
+  fprintf(stderr, "[facppg decoder prof, shader cycles] project %lld prenet %lld att_slice %lld sync1 %lld gather %lld attention %lld dec_slice %lld sync2 %lld | att: query %lld feat %lld energy %lld softmax %lld update %lld context %lld\n",
+          pr[0], pr[1], pr[2], pr[3], pr[4], pr[5], pr[6], pr[7], pr[8], pr[9], pr[10], pr[11], pr[12], pr[13]);
+  return FACPPG_OK;
+}
+int print_forced_prof(const DecArgs& a, hipStream_t s) {
+  long long pr[16];
+  if (int rc = read_prof(a.prof, pr, 16, s)) return rc;
+  fprintf(stderr, "[facppg teacher-forced decoder prof (chain workgroup 0), shader cycles] features+energy_pre %lld gather_ah %lld attention %lld att_slice %lld | att: query %lld feat %lld energy %lld softmax %lld update %lld context %lld\n",
+          pr[0], pr[1], pr[2], pr[3], pr[8], pr[9], pr[10], pr[11], pr[12], pr[13]);
+  return FACPPG_OK;
+}
+}  // namespace
+
 // Decoder.inference (model.py:489-535).
 extern "C" int facppg_taco_decode(const facppg_taco* h, const float* memory_dev, const float* pm_dev, const int32_t* lengths_dev,
                                   const int32_t* step_limits_dev, const uint8_t* masks_dev, uint64_t seed, int B, int Tin, int max_steps, float* mel_dev,
@@ -2535,132 +2568,46 @@ extern "C" int facppg_taco_decode(const facppg_taco* h, const float* memory_dev,
     k_random_mask<<<(unsigned)((nmask + 255) / 256), 256, 0, s>>>((uint8_t*)(ws + w.mask), nmask, seed ^ 0xD1B54A32D192ED03ull);
     masks = (const uint8_t*)(ws + w.mask);
   }
-  DecArgs a;
-  a.melx = nullptr;
-  a.dp0_t = h->dp0_t; a.dp1_t = h->dp1_t; a.att_t = h->att_t; a.att_b = h->att_b; a.dec_t = h->dec_t; a.dec_b = h->dec_b;
-  a.q_t = h->q_t; a.proj_t = h->proj_t; a.proj_b = h->proj_b; a.loc_conv = h->loc_conv; a.loc_dense = h->loc_dense; a.v = h->v;
+  // which kernel, in what shape: facppg_taco_plan.h
+  unsigned long long* words = opts ? (unsigned long long*)opts->frame_words_dev : nullptr;
+  const DecodePlan pl = plan_decode(h->g, B, Tin, max_steps, opts ? opts->max_workgroups : 0,
+                                    words && opts->frame_words_frames >= max_steps, taco_tuning_from_env());
+  FACPPG_REQUIRE(pl.rc == FACPPG_OK, pl.rc, "%s", pl.msg);
+  DecArgs a = dec_args_common(h, memory_dev, pm_dev, lengths_dev, align_dev, B, Tin, max_steps, pl.prof ? (long long*)(ws + w.prof) : nullptr);
+  a.dp0_t = h->dp0_t; a.dp1_t = h->dp1_t; a.att_t = h->att_t; a.att_b = h->att_b; a.dec_t = h->dec_t; a.proj_t = h->proj_t; a.proj_b = h->proj_b;
   a.xchg = (unsigned long long*)(ws + w.xchg);
-  a.prof = getenv("FACPPG_DECODER_PROF") ? (long long*)(ws + w.prof) : nullptr;
-  a.memory = memory_dev; a.pm = pm_dev; a.lengths = lengths_dev; a.step_limits = step_limits_dev; a.masks = masks; a.mel = mel_dev; a.gate = gate_dev;
-  a.align = align_dev; a.out_len = out_lengths_dev;
-  a.B = B; a.Tin = Tin; a.E = c.encoder_embedding_dim; a.P = c.prenet_dim; a.A = c.attention_rnn_dim; a.D = c.decoder_rnn_dim;
-  a.AD = c.attention_dim; a.NF = c.n_acoustic_feat_dims; a.NFIL = c.attention_location_n_filters;
-  a.KSZ = c.attention_location_kernel_size; a.window = c.attention_window_size; a.max_steps = max_steps;
-  a.gate_thr = c.gate_threshold;
-  const size_t smem = dec_lds_floats(a.P, a.E, a.A, a.D, a.NF, a.AD, a.NFIL, a.KSZ, Tin) * 4;
-  FACPPG_REQUIRE(smem <= 160 * 1024 - 1024, FACPPG_EUNSUPPORTED, "decoder state (%zu bytes) exceeds LDS", smem);
-  // latency mode (few utterances): NWG cooperating workgroups per utterance; throughput mode: one each
-  // slice width: the narrowest (most workgroups per utterance) that keeps B * NWG co-resident (coop_limit)
-  // the decoder holds a CU's whole LDS per workgroup: a caller that runs it UNDER another stream's kernels (the vocoder of
-  // the previous batch, facppg.pipeline.synthesize_stream) bounds the CUs it takes away from them
-  const int max_wgs = opts ? opts->max_workgroups : 0;
-  const int wg_limit = max_wgs > 0 && max_wgs < h->coop_limit ? max_wgs : h->coop_limit;
-  int launch_step = 0;                   // split launch: 1 = one-barrier worker stages, 2 = FACPPG_DECODER_STEP=legacy
-  int launch_mode = 0, launch_wgs = B;   // reported in opts: 0 k_decoder (one workgroup per utterance), 1 k_decoder_coop, 2 k_decoder_split
-  const char* mode = getenv("FACPPG_DECODER_MODE");
-  int variant = -1;
-  const char* force_u = getenv("FACPPG_DECODER_COOP_U");   // tests / tuning: a specific slice width
-  for (int v = 0; v < 5 && variant < 0; ++v)
-    if ((long)B * h->coop_nwg[v] <= wg_limit && (!force_u || atoi(force_u) == h->coop_U[v])) variant = v;
-  // beyond that the widest slices run the batch in chunks of co-resident utterances, one cooperative launch
-  // after the other (0.31 ms per utterance at 200 frames; the one-workgroup kernel needs 0.45)
-  int chunk = B;
-  if (variant < 0 && !force_u && wg_limit / h->coop_nwg[4] >= 1) { variant = 4; chunk = wg_limit / h->coop_nwg[4]; }
-  bool coop = variant >= 0;
-  if (mode && !strcmp(mode, "single")) coop = false;
-  if (mode && !strcmp(mode, "coop")) FACPPG_REQUIRE(coop, FACPPG_EUNSUPPORTED, "coop decoder needs B <= 120");
-  if (coop) {
-    a.att_coop = h->att_coop[variant]; a.dec_coop = h->dec_coop[variant]; a.U = h->coop_U[variant];
-  }
-  // split shape: split_nwk register-resident dense-layer workers serve NU utterances, each with its own main
-  // (attention) workgroup.  NU = the fewest utterances per worker set that keeps every workgroup co-resident;
-  // a worker's per-frame work grows with NU, so beyond SPLIT_MAX_NU the cooperative kernel wins.
-  static const char* no_split = getenv("FACPPG_DECODER_NO_SPLIT");
-  const char* max_nu_env = getenv("FACPPG_DECODER_SPLIT_MAX_NU");
-  const int max_nu = max_nu_env ? atoi(max_nu_env) : 3;   // 4 utterances per worker set only ties with the cooperative kernel (12.5 vs 12.4 ms at B = 12)
-  // (the larger of the two worker layouts, so that NU does not depend on FACPPG_DECODER_STEP)
-  const size_t ustride = std::max(split_ustride(a.P, a.E, a.A, a.D, a.NF, true), split_ustride(a.P, a.E, a.A, a.D, a.NF, false));
-  int NU = 0;
-  for (int nu = 1; nu <= SNU && nu <= max_nu && !NU; ++nu)
-    if ((long)((B + nu - 1) / nu) * (h->split_nwk + nu) <= wg_limit && (nu * ustride + 1024) * 4 <= 150 * 1024) NU = nu;
-  const bool split = coop && !no_split && NU > 0 && a.P + a.E + a.A <= SKP * SKR_LSTM &&
-                     a.A + a.E + a.D <= SKP * SKR_LSTM && a.D + a.E <= SKP * SKR_PROJ && a.NF <= SKP * SKR_P1 &&
-                     a.P <= SKP * SKR_P2 && a.NF + 1 <= h->split_nwk * SSC && a.P <= h->split_nwk * SSC &&
-                     !(mode && !strcmp(mode, "coop"));
-  if (mode && !strcmp(mode, "split")) FACPPG_REQUIRE(split, FACPPG_EUNSUPPORTED, "split decoder needs a small batch and the reference's layer widths");
-  if (split) {
+  a.step_limits = step_limits_dev; a.masks = masks; a.mel = mel_dev; a.gate = gate_dev; a.out_len = out_lengths_dev;
+  if (pl.mode != 0) { a.att_coop = h->att_coop[pl.variant]; a.dec_coop = h->dec_coop[pl.variant]; a.U = h->g.coop_U[pl.variant]; }
+  void* args[] = {(void*)&a};
+  if (pl.mode == 2) {
     a.att_w4 = h->att_w4; a.dec_w4 = h->dec_w4; a.xsplit = (unsigned long long*)(ws + w.xsplit);
     a.w1p_t = h->w1p_t; a.b1p = h->b1p;
     FACPPG_HIP_CHECK(hipMemsetAsync(ws + w.xchg, 0, w.total - w.xchg, s));
-    size_t ssm = (NU * ustride + 1024) * 4;
-    size_t main_smem = (round_up((int)(smem / 4), 4) + (size_t)8 * NTC * 4) * 4;   // + attn_energy_pre's stash
-    // FACPPG_DECODER_STEP=legacy: the worker stages up to round 19 (read per call: the tests flip it)
-    const char* step_env = getenv("FACPPG_DECODER_STEP");
-    const bool legacy_step = step_env && !strcmp(step_env, "legacy");
-    launch_step = legacy_step ? 2 : 1;
-    const void* fn = legacy_step ? (NU == 1 ? (const void*)k_decoder_split<1, true> : NU == 2 ? (const void*)k_decoder_split<2, true>
-                                    : NU == 3 ? (const void*)k_decoder_split<3, true> : (const void*)k_decoder_split<4, true>)
-                                 : (NU == 1 ? (const void*)k_decoder_split<1, false> : NU == 2 ? (const void*)k_decoder_split<2, false>
-                                    : NU == 3 ? (const void*)k_decoder_split<3, false> : (const void*)k_decoder_split<4, false>);
-    // ... + as many of the main workgroup's query-weight rows (one float4 per thread each) as the rest of the LDS holds
-    const size_t lds_cap = 160 * 1024 - 1024, q_row = (size_t)NTC * 16;
-    const char* qres_env = getenv("FACPPG_DECODER_QRES");   // A/B runs: at most this many
-    a.q_res = legacy_step || main_smem > lds_cap ? 0 : (int)std::min<size_t>(SPLIT_QR, (lds_cap - main_smem) / q_row);
-    if (qres_env) a.q_res = std::max(0, std::min(a.q_res, atoi(qres_env)));
-    main_smem += a.q_res * q_row;
-    if (ssm < main_smem) ssm = main_smem;
-    FACPPG_HIP_CHECK(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)ssm));
-    void* args[] = {(void*)&a};
-    const int groups = (B + NU - 1) / NU;
-    a.nwk = h->split_nwk;
-    unsigned long long* words = opts ? (unsigned long long*)opts->frame_words_dev : nullptr;
-    a.melx = (B == 1 && words && opts->frame_words_frames >= max_steps) ? words : nullptr;
-    a.dbg_flags = getenv("FACPPG_DECODER_NO_ROWS") ? 1 : 0;
-    const char* pause_env = getenv("FACPPG_DECODER_PAUSE");   // A/B runs: units of 128 cycles, 0 = none
-    a.pause = pause_env ? std::max(0, std::min(255, atoi(pause_env))) : legacy_step ? 0 : SPLIT_PAUSE;
-    FACPPG_HIP_CHECK(launch_coop(fn, dim3(h->split_nwk + NU, groups), dim3(NTC), args, ssm, s));
-    launch_mode = 2; launch_wgs = (h->split_nwk + NU) * groups;
-    if (a.prof) {
-      long long pr[32];
-      FACPPG_HIP_CHECK(hipMemcpyAsync(pr, a.prof, sizeof(pr), hipMemcpyDeviceToHost, s));
-      FACPPG_HIP_CHECK(hipStreamSynchronize(s));
-      fprintf(stderr, "[facppg split decoder prof (main), shader cycles] location features %lld energy_pre %lld entering row %lld query weights requested %lld wait_gate %lld wait_ah %lld attention %lld | att: query %lld energy %lld softmax %lld update %lld context %lld\n",
-              pr[6], pr[7], pr[14], pr[2], pr[0], pr[3], pr[5], pr[8], pr[10], pr[11], pr[12], pr[13]);
-      // (with a pause, every gather phase but CTX's begins with it; with the one-barrier stages "att LSTM" and "dec LSTM" include barriers C and E)
-      const char* pz = a.pause ? "pause+" : "";
-      fprintf(stderr, "[facppg split decoder prof (worker 0, %s stages, pause %d x 128 cycles), shader cycles] proj+prenet1 %lld | %sgather gate,X1 %lld | prenet2 %lld | %sgather X2 %lld | "
-              "att LSTM %lld | %sgather AH %lld | gather CTX %lld | dec LSTM + %sgather DH %lld | barrier %lld\n",
-              legacy_step ? "legacy" : "one-barrier", a.pause, pr[16], pz, pr[17], pr[18], pz, pr[19], pr[20], pz, pr[21], pr[22], pz, pr[23], pr[24]);
-    }
-  } else
-  if (coop) {
+    const void* fn = split_kernel(pl);
+    FACPPG_HIP_CHECK(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)pl.lds_split));
+    a.nwk = h->g.split_nwk; a.q_res = pl.q_res; a.dbg_flags = pl.dbg_flags; a.pause = pl.pause;
+    a.melx = pl.publish ? words : nullptr;
+    FACPPG_HIP_CHECK(launch_coop(fn, dim3(pl.grid[0], pl.grid[1]), dim3(NTC), args, pl.lds_split, s));
+    if (a.prof)
+      if (int rc = print_split_prof(a, pl.step == 2, s)) return rc;
+  } else if (pl.mode == 1) {
     FACPPG_HIP_CHECK(hipMemsetAsync(ws + w.xchg, 0, w.total - w.xchg, s));
     const void* fn = (const void*)k_decoder_coop;
-    FACPPG_HIP_CHECK(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem));
-    for (int b0 = 0; b0 < B; b0 += chunk) {
-      const int nb = B - b0 < chunk ? B - b0 : chunk;
-      int cv = variant;   // the last chunk may be small enough for narrower slices
-      if (!force_u)
-        for (int v = 0; v < variant; ++v)
-          if ((long)nb * h->coop_nwg[v] <= wg_limit) { cv = v; break; }
-      a.b0 = b0; a.att_coop = h->att_coop[cv]; a.dec_coop = h->dec_coop[cv]; a.U = h->coop_U[cv];
-      void* args[] = {(void*)&a};
-      FACPPG_HIP_CHECK(launch_coop(fn, dim3(h->coop_nwg[cv], nb), dim3(NTC), args, smem, s));
-      launch_mode = 1; launch_wgs = h->coop_nwg[cv] * nb;
+    FACPPG_HIP_CHECK(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)pl.lds_state));
+    for (int i = 0; i < pl.launches; ++i) {
+      const bool last = i == pl.launches - 1;
+      const int nb = last ? pl.last_nb : pl.chunk, cv = last ? pl.v_last : pl.v_full;
+      a.b0 = i * pl.chunk; a.att_coop = h->att_coop[cv]; a.dec_coop = h->dec_coop[cv]; a.U = h->g.coop_U[cv];
+      FACPPG_HIP_CHECK(launch_coop(fn, dim3(h->g.coop_nwg[cv], nb), dim3(NTC), args, pl.lds_state, s));
     }
-    if (a.prof) {
-      long long pr[16];
-      FACPPG_HIP_CHECK(hipMemcpyAsync(pr, a.prof, sizeof(pr), hipMemcpyDeviceToHost, s));
-      FACPPG_HIP_CHECK(hipStreamSynchronize(s));
-      fprintf(stderr, "[facppg decoder prof, shader cycles] project %lld prenet %lld att_slice %lld sync1 %lld gather %lld attention %lld dec_slice %lld sync2 %lld | att: query %lld feat %lld energy %lld softmax %lld update %lld context %lld\n",
-              pr[0], pr[1], pr[2], pr[3], pr[4], pr[5], pr[6], pr[7], pr[8], pr[9], pr[10], pr[11], pr[12], pr[13]);
-    }
+    if (a.prof)
+      if (int rc = print_coop_prof(a, s)) return rc;
   } else {
-    FACPPG_HIP_CHECK(hipFuncSetAttribute((const void*)k_decoder, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem));
-    k_decoder<<<B, NT, smem, s>>>(a);
+    FACPPG_HIP_CHECK(hipFuncSetAttribute((const void*)k_decoder, hipFuncAttributeMaxDynamicSharedMemorySize, (int)pl.lds_state));
+    k_decoder<<<B, NT, pl.lds_state, s>>>(a);
   }
   FACPPG_HIP_CHECK(hipGetLastError());
-  if (opts) { opts->mode = launch_mode; opts->workgroups = launch_wgs; opts->streamed = a.melx != nullptr; opts->step = launch_step; }
+  if (opts) { opts->mode = pl.mode; opts->workgroups = pl.workgroups(); opts->streamed = a.melx != nullptr; opts->step = pl.step; }
   return FACPPG_OK;
 }
 
@@ -2741,66 +2688,27 @@ extern "C" int facppg_taco_decode_forced(const facppg_taco* h, const float* memo
   x.B = B; x.N = T; x.A = h->tf_attx; x.M = G; x.Cin = P; x.X = p2; x.x_bs = (long)P * T; x.ldx = T; x.bias = h->att_b;
   x.C = xa; x.c_bs = (long)T * G; x.ldc = G; x.c_transposed = 1;
   if (int rc = gemm_launch(x, s)) return rc;
-  // the recurrence: one launch per chunk of co-resident utterances (one launch whenever B * workgroups-per-utterance fit)
-  DecArgs a = {};
-  a.dec_b = h->dec_b; a.q_t = h->q_t; a.loc_conv = h->loc_conv; a.loc_dense = h->loc_dense; a.v = h->v;
-  a.memory = memory_dev; a.pm = pm_dev; a.lengths = lengths_dev; a.align = align_dev;
-  a.B = B; a.Tin = Tin; a.E = E; a.P = P; a.A = A; a.D = D; a.AD = c.attention_dim; a.NF = NF;
-  a.NFIL = c.attention_location_n_filters; a.KSZ = c.attention_location_kernel_size; a.window = c.attention_window_size;
-  a.max_steps = T; a.gate_thr = c.gate_threshold;
-  // chain workgroups: the decoder's LDS state + attn_energy_pre's stash ([8][NTC] float4)
-  const size_t smem = (round_up((int)dec_lds_floats(a.P, a.E, a.A, a.D, a.NF, a.AD, a.NFIL, a.KSZ, Tin), 4) + (size_t)8 * NTC * 4) * 4;
-  FACPPG_REQUIRE(smem <= 160 * 1024 - 1024, FACPPG_EUNSUPPORTED, "decoder state (%zu bytes) exceeds LDS", smem);
-  const int max_wgs = opts ? opts->max_workgroups : 0;
-  const int wg_limit = max_wgs > 0 && max_wgs < h->coop_limit ? max_wgs : h->coop_limit;
-  FACPPG_REQUIRE(wg_limit >= 2 * h->coop_nwg[4], FACPPG_EUNSUPPORTED, "the teacher-forced decoder needs %d co-resident workgroups, %d allowed",
-                 2 * h->coop_nwg[4], wg_limit);
-  // Slice widths: the narrowest chain slices (the dependent chain) whose workgroups, with decoder-LSTM workgroups of the same
-  // or the next width (they have a frame's slack), stay co-resident for nb utterances; FACPPG_DECODER_COOP_U (tests / tuning)
-  // forces one width for both roles.
-  const char* force_u = getenv("FACPPG_DECODER_COOP_U");
-  auto pick = [&](int nb, int* vc, int* vd) {
-    for (int c2 = 0; c2 < 5; ++c2) {
-      if (force_u && atoi(force_u) != h->coop_U[c2]) continue;
-      for (int d2 = c2; d2 <= (force_u ? c2 : std::min(c2 + 1, 4)); ++d2)
-        if ((long)nb * (h->coop_nwg[c2] + h->coop_nwg[d2]) <= wg_limit) { *vc = c2; *vd = d2; return true; }
-    }
-    return false;
-  };
-  // up to 2 utterances: register-resident attention-LSTM slices of 4 units (k_decoder_forced<true>) next to the narrowest decoder slices
-  const bool regw = !force_u && !getenv("FACPPG_FORCED_NO_REGW") && (long)B * (h->split_nwk + h->coop_nwg[0]) <= wg_limit &&
-                    E + A <= SKP * SKR_FA && A <= h->split_nwk * SU;
-  int vc = 4, vd = 4, chunk = B;
-  if (regw) { vc = vd = 0; }
-  else if (!pick(B, &vc, &vd)) {   // beyond that the widest slices run the batch in chunks of co-resident utterances
-    FACPPG_REQUIRE(!force_u, FACPPG_EUNSUPPORTED, "FACPPG_DECODER_COOP_U=%s does not fit B = %d", force_u, B);
-    vc = vd = 4; chunk = wg_limit / (2 * h->coop_nwg[4]);
-  }
+  // the recurrence: one launch per chunk of co-resident utterances, in the shape facppg_taco_plan.h picks
+  const TacoGeometry& geom = h->g;
+  const ForcedPlan pl = plan_forced(geom, B, Tin, opts ? opts->max_workgroups : 0, taco_tuning_from_env());
+  FACPPG_REQUIRE(pl.rc == FACPPG_OK, pl.rc, "%s", pl.msg);
   unsigned long long* xw = (unsigned long long*)(ws + w.xchg);
   FACPPG_HIP_CHECK(hipMemsetAsync(xw, 0, w.prof + 32 * 8 - w.xchg, s));   // the exchange words and the phase counters behind them
-  a.prof = getenv("FACPPG_DECODER_PROF") ? (long long*)(ws + w.prof) : nullptr;
-  const void* fn = regw ? (const void*)k_decoder_forced<true> : (const void*)k_decoder_forced<false>;
-  FACPPG_HIP_CHECK(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem));
+  DecArgs a = dec_args_common(h, memory_dev, pm_dev, lengths_dev, align_dev, B, Tin, T, pl.prof ? (long long*)(ws + w.prof) : nullptr);
   a.att_w4 = h->att_w4;
-  int launch_wgs = 0;
-  for (int b0 = 0; b0 < B; b0 += chunk) {
-    const int nb = B - b0 < chunk ? B - b0 : chunk;
-    int cv = vc, dv = vd;   // the last chunk may be small enough for narrower slices
-    if (nb < chunk && !force_u && !regw) pick(nb, &cv, &dv);
-    a.b0 = b0; a.att_coop = h->att_coop[cv]; a.dec_coop = h->dec_coop[dv]; a.U = h->coop_U[cv];
+  const void* fn = pl.regw ? (const void*)k_decoder_forced<true> : (const void*)k_decoder_forced<false>;
+  FACPPG_HIP_CHECK(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)pl.lds));
+  for (int i = 0; i < pl.launches; ++i) {
+    const bool last = i == pl.launches - 1;
+    const int nb = last ? pl.last_nb : pl.chunk, cv = last ? pl.vc_last : pl.vc, dv = last ? pl.vd_last : pl.vd;
+    a.b0 = i * pl.chunk; a.att_coop = h->att_coop[cv]; a.dec_coop = h->dec_coop[dv]; a.U = geom.coop_U[cv];
     const float* xa_c = xa;
-    int NA = regw ? h->split_nwk : h->coop_nwg[cv], UD = h->coop_U[dv];
+    int NA = forced_chain_wgs(geom, pl, cv), UD = geom.coop_U[dv];
     void* args[] = {(void*)&a, (void*)&xa_c, (void*)&hc, (void*)&xw, (void*)&NA, (void*)&UD};
-    FACPPG_HIP_CHECK(launch_coop(fn, dim3(NA + h->coop_nwg[dv], nb), dim3(NTC), args, smem, s));
-    launch_wgs = (NA + h->coop_nwg[dv]) * nb;
+    FACPPG_HIP_CHECK(launch_coop(fn, dim3(NA + geom.coop_nwg[dv], nb), dim3(NTC), args, pl.lds, s));
   }
-  if (a.prof) {
-    long long pr[16];
-    FACPPG_HIP_CHECK(hipMemcpyAsync(pr, a.prof, sizeof(pr), hipMemcpyDeviceToHost, s));
-    FACPPG_HIP_CHECK(hipStreamSynchronize(s));
-    fprintf(stderr, "[facppg teacher-forced decoder prof (chain workgroup 0), shader cycles] features+energy_pre %lld gather_ah %lld attention %lld att_slice %lld | att: query %lld feat %lld energy %lld softmax %lld update %lld context %lld\n",
-            pr[0], pr[1], pr[2], pr[3], pr[8], pr[9], pr[10], pr[11], pr[12], pr[13]);
-  }
+  if (a.prof)
+    if (int rc = print_forced_prof(a, s)) return rc;
   // linear_projection + gate_layer of every frame (model.py:436-441) on [decoder_hidden | context]
   GemmArgs q;
   q.splitk_ws = (float*)(ws + w.splitk); q.splitk_ws_bytes = w.splitk_bytes;
@@ -2812,7 +2720,7 @@ extern "C" int facppg_taco_decode_forced(const facppg_taco* h, const float* memo
     k_forced_outputs<<<(unsigned)((n + 255) / 256), 256, 0, s>>>(mg, mel_dev, gate_dev, B, NF, T);
   }
   FACPPG_HIP_CHECK(hipGetLastError());
-  if (opts) { opts->mode = 1; opts->workgroups = launch_wgs; opts->streamed = 0; opts->step = 0; }
+  if (opts) { opts->mode = 1; opts->workgroups = pl.workgroups(); opts->streamed = 0; opts->step = 0; }
   return FACPPG_OK;
 }
 

@@ -44,6 +44,14 @@ class TacoDecodeOpts(ctypes.Structure):
                 ("mode", ctypes.c_int32), ("workgroups", ctypes.c_int32), ("streamed", ctypes.c_int32), ("step", ctypes.c_int32)]
 
 
+class TacoLaunchReport(ctypes.Structure):
+    """facppg_taco_launch_report (include/facppg.h): what facppg_taco_launch_plan says a call would launch."""
+    _fields_ = [(n, ctypes.c_int32) for n in ("mode", "workgroups", "launches", "step", "nu", "first_utts", "last_utts")] + \
+        [("first_u", ctypes.c_int32 * 2), ("last_u", ctypes.c_int32 * 2)] + \
+        [(n, ctypes.c_int32) for n in ("regw", "q_res", "pause", "dbg_flags", "prof", "lds_bytes", "streamed_possible",
+                                       "bilstm_kind", "bilstm_legacy")]
+
+
 class TacoAttentionBackwardArgs(ctypes.Structure):
     """facppg_taco_attention_backward_args (include/facppg.h): twelve inputs, four outputs, all device pointers."""
     _fields_ = [(n, ctypes.c_void_p) for n in (
@@ -195,6 +203,9 @@ def _declare(lib):
         "facppg_taco_encode": (c.c_int, [vp, vp, vp, vp, u64, c.c_int, c.c_int, vp, vp, vp, sz, vp]),
         "facppg_taco_decode": (c.c_int, [vp, vp, vp, vp, vp, vp, u64, c.c_int, c.c_int, c.c_int, vp, vp, vp, vp, vp, sz,
                                          c.POINTER(TacoDecodeOpts), vp]),
+        "facppg_taco_launch_plan": (c.c_int, [c.POINTER(TacoConfig), c.c_int, c.c_int, c.c_int, c.c_int, c.c_int, c.c_int,
+                                              c.POINTER(TacoLaunchReport)]),
+        "facppg_taco_coop_limit": (c.c_int, [vp]),
         "facppg_taco_draw_dropout": (c.c_int, [vp, vp, c.c_int, c.c_int, c.c_int, vp, vp, vp]),
         "facppg_taco_encode_padded": (c.c_int, [vp, vp, vp, vp, vp, u64, c.c_int, c.c_int, vp, vp, vp, sz, vp]),
         "facppg_taco_decode_forced_workspace_bytes": (sz, [vp, c.c_int, c.c_int]),

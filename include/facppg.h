@@ -589,11 +589,13 @@ int facppg_taco_encode(const facppg_taco* h, const float* ppg_dev, const int32_t
  * own max_decoder_steps, e.g. = their PPG length).  masks_dev NULL or uint8 [max_steps][2][B][prenet_dim].
  * Outputs: mel_dev [B][n_feat][max_steps], gate_dev [B][max_steps], align_dev NULL or
  * [B][max_steps][Tin], out_lengths_dev [B] (= Tout per utterance; columns beyond it untouched).
- * One launch for the whole loop.  The launch shape follows B: up to 9 utterances run as one attention
- * workgroup each plus register-resident dense-layer workers shared by 1-3 of them, up to 120 as 2-38 cooperating workgroups
- * (larger batches in chunks of 120), one workgroup per utterance as the fallback; the first two use hipLaunchCooperativeKernel (the workgroups
- * of an utterance must be co-resident) and every shape returns the same values to fp32 round-off.
- * FACPPG_DECODER_MODE=split|coop|single forces one (FACPPG_EUNSUPPORTED if B does not allow it).
+ * One launch for the whole loop.  The launch shape follows B and the workgroups that may be co-resident (the device's, 240 on
+ * an MI355X, or max_workgroups if that is less); facppg_taco_launch_plan answers for any batch.  At 240 and the reference's
+ * layer widths: up to 9 utterances run as one attention workgroup each plus 75 register-resident dense-layer workers shared by
+ * 1-3 of them (1 while B <= 3, 2 up to 6, 3 up to 9), up to 120 as 2-38 cooperating workgroups each (larger batches in chunks
+ * of 120 and a rest), one workgroup per utterance as the fallback when nothing may be co-resident; the first two use
+ * hipLaunchCooperativeKernel (the workgroups of an utterance must be co-resident) and every shape returns the same values to
+ * fp32 round-off.  FACPPG_DECODER_MODE=split|coop|single forces one (FACPPG_EUNSUPPORTED if the batch does not allow it).
  * opts NULL, or the call's own options and launch report (the handle holds no per-call state):
  *   max_workgroups bounds the workgroups (= CUs: a decoder workgroup holds a CU's whole LDS) the launch may occupy; 0 = no bound
  *     beyond the device's.  No reference counterpart (the reference decodes one utterance at a time on the whole device): it
@@ -624,6 +626,38 @@ int facppg_taco_decode(const facppg_taco* h, const float* memory_dev, const floa
                        int Tin, int max_steps, float* mel_dev, float* gate_dev, float* align_dev,
                        int32_t* out_lengths_dev, void* workspace_dev, size_t workspace_bytes,
                        facppg_taco_decode_opts* opts, void* stream);
+/* What facppg_taco_encode (its BiLSTM recurrence), facppg_taco_decode or facppg_taco_decode_forced would launch for a batch:
+ * the host-side decision alone, from the very functions the calls plan with (csrc/facppg_taco_plan.h) -- no handle, no
+ * device, no reference counterpart.  coop_limit: the co-resident workgroups of the device, facppg_taco_coop_limit(h) of a
+ * handle (240 on an MI355X; 0: no cooperative launch).  steps: max_steps (decode) or T_out (forced).  The environment
+ * switches count as in the calls.  Returns what the call would return for the plan: FACPPG_OK, or FACPPG_EUNSUPPORTED with the
+ * call's message (facppg_last_error). */
+#define FACPPG_TACO_PLAN_ENCODE 0
+#define FACPPG_TACO_PLAN_DECODE 1
+#define FACPPG_TACO_PLAN_FORCED 2
+typedef struct facppg_taco_launch_report {
+  int32_t mode;              /* decode, forced: as facppg_taco_decode_opts.mode; encode: 0 */
+  int32_t workgroups;        /* of the last launch, as facppg_taco_decode_opts.workgroups */
+  int32_t launches;          /* > 1: a batch that runs in chunks of co-resident utterances */
+  int32_t step;              /* as facppg_taco_decode_opts.step */
+  int32_t nu;                /* split decoder: utterances per worker set, else 0 */
+  int32_t first_utts;        /* utterances of the first launch ... */
+  int32_t last_utts;         /* ... and of the last */
+  int32_t first_u[2];        /* LSTM units per workgroup in the first launch: {attention LSTM, decoder LSTM}; one-workgroup kernel: 0 */
+  int32_t last_u[2];         /* ... in the last launch */
+  int32_t regw;              /* forced: register-resident attention-LSTM slices */
+  int32_t q_res;             /* split decoder: query-weight rows kept in LDS */
+  int32_t pause;             /* split decoder: units of 128 cycles a worker pauses before polling */
+  int32_t dbg_flags;         /* split decoder: bit 0 FACPPG_DECODER_NO_ROWS */
+  int32_t prof;              /* FACPPG_DECODER_PROF is set */
+  int32_t lds_bytes;         /* dynamic LDS per workgroup (decode, forced) */
+  int32_t streamed_possible; /* decode: frame words would be published if the caller passed enough of them */
+  int32_t bilstm_kind;       /* encode: 0 k_bilstm, 1 k_bilstm_coop on 32-unit slices, 2 on 64-unit slices */
+  int32_t bilstm_legacy;     /* encode: FACPPG_BILSTM_STEP=legacy applies */
+} facppg_taco_launch_report;
+int facppg_taco_launch_plan(const facppg_taco_config* cfg, int coop_limit, int what, int B, int Tin, int steps,
+                            int max_workgroups, facppg_taco_launch_report* out);
+int facppg_taco_coop_limit(const facppg_taco* h);
 /* ---- the teacher-forced pass (Tacotron2.forward, model.py:580-595, eval mode): encode_padded -> decode_forced ->
  * facppg_taco_postnet(out_lengths_dev = NULL); the parse_output masking (model.py:566-578) is the caller's.
  *
