@@ -2,6 +2,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include <atomic>
 #include <cstdarg>
 #include <cstdio>
 #include <cstdlib>
@@ -57,6 +58,21 @@ inline unsigned long long poll_limit_ticks(int device) {
   int khz = 0;
   (void)hipDeviceGetAttribute(&khz, hipDeviceAttributeWallClockRate, device);
   return seconds > 0 && khz > 0 ? (unsigned long long)(seconds * 1e3 * khz) : 0ull;
+}
+
+// A kernel that asks for more than 64 KB of dynamic LDS needs hipFuncAttributeMaxDynamicSharedMemorySize once on EVERY device it
+// runs on.  `devices` is the call site's (or the kernel's) own static, one bit per device: a set bit means no HIP call beyond
+// hipGetDevice (so nothing but that query runs while a stream is being captured, once the eager warm-up has set the bit); a
+// second thread setting the attribute again is harmless; devices >= 64 set it on every call.  fn2: a second instantiation
+// launched from the same site (the stamped debugging build), set together with the first.
+inline int ensure_dynamic_lds(std::atomic<unsigned long long>& devices, size_t bytes, const void* fn, const void* fn2 = nullptr) {
+  int dev = 0;
+  FACPPG_HIP_CHECK(hipGetDevice(&dev));
+  if (dev < 64 && ((devices.load(std::memory_order_relaxed) >> dev) & 1ull)) return FACPPG_OK;
+  FACPPG_HIP_CHECK(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes));
+  if (fn2) FACPPG_HIP_CHECK(hipFuncSetAttribute(fn2, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes));
+  if (dev < 64) devices.fetch_or(1ull << dev, std::memory_order_relaxed);
+  return FACPPG_OK;
 }
 
 // Frame / sample offsets of a batch of utterances laid end to end (host copy): B + 1 values, off[0] = 0, strictly increasing

@@ -29,6 +29,7 @@
 
 #include "facppg_common.h"
 #include "facppg_gemm.h"
+#include "facppg_train_plan.h"
 
 namespace facppg {
 namespace {
@@ -41,13 +42,9 @@ __device__ __forceinline__ uint4 nt_load16(const void* p) {
   return make_uint4(v.x, v.y, v.z, v.w);
 }
 
-constexpr int C = 256, NCOND = 640, HALO = 128;
-constexpr int BM = 128, BN = 128, KC = 64;     // k_bgemm tile and K chunk
+// (C, NCOND, HALO, the tile constants and pad_len: facppg_train_plan.h)
 constexpr int LDB = KC + 8;                    // LDS row pitch in bf16 (144 B: conflict-free ds_read_b128)
 constexpr int MAXSEG = 8;
-// padded positions per batch item: a multiple of the 128-column GEMM tile, so a tile's staging loads never leave the
-// batch item's rows (rows >= L are zero)
-__host__ __device__ inline int pad_len(int L) { return round_up(L, BN); }
 
 // fp32 -> bf16, round to nearest even: v_cvt_pk_bf16_f32 (gfx950), one instruction per PAIR (the integer sequence -- bfe, add3,
 // and, perm -- was a fifth of the gate epilogue's instructions)
@@ -382,21 +379,13 @@ __global__ __launch_bounds__(256) void k_bgemm(BGemmArgs p) {
 }
 
 template <int MODE>
-void bgemm_dispatch(const BGemmArgs& a, hipStream_t s) {
-  const int nm = (a.M + BM - 1) / BM;
-  const long wide = (long)((a.N + 127) / 128) * nm * a.B;
-  // 128-column tiles once they give >= 1.5 workgroups per CU, else 64-column tiles (twice the workgroups).  A 256 x 128 /
-  // 8-wave tile with both operands through LDS was built and measured slower in every mode (profiles/r02_experiments.txt).
-  if (wide >= 384) {
-    const int ct = ((a.N + 127) / 128) * a.B;
-    k_bgemm<MODE, 4><<<dim3(8 * nm * ((ct + 7) / 8)), 256, 0, s>>>(a);
-  } else {
-    const int ct = ((a.N + 63) / 64) * a.B;
-    k_bgemm<MODE, 2><<<dim3(8 * nm * ((ct + 7) / 8)), 256, 0, s>>>(a);
-  }
+void bgemm_dispatch(const BGemmArgs& a, const BgemmShape& shape, hipStream_t s) {
+  if (shape.cols == 128) k_bgemm<MODE, 4><<<dim3(shape.grid), 256, 0, s>>>(a);
+  else k_bgemm<MODE, 2><<<dim3(shape.grid), 256, 0, s>>>(a);
 }
 
-int bgemm_launch(const BGemmArgs& a, hipStream_t s) {
+// shape: plan_bgemm(a.M, a.N, a.B), as the stack's plan holds it for each launch of the layer loop
+int bgemm_launch(const BGemmArgs& a, const BgemmShape& shape, hipStream_t s) {
   int K = 0;
   for (int i = 0; i < a.nseg; ++i) {
     FACPPG_REQUIRE(a.seg[i].nch % KC == 0 && a.seg[i].nch > 0, FACPPG_EINVAL, "bgemm: segment of %d channels", a.seg[i].nch);
@@ -404,11 +393,11 @@ int bgemm_launch(const BGemmArgs& a, hipStream_t s) {
   }
   FACPPG_REQUIRE(K == a.KG * 16 && a.M % 32 == 0 && a.nseg >= 1 && a.nseg <= MAXSEG, FACPPG_EINVAL, "bgemm: bad shape K=%d KG=%d M=%d", K, a.KG, a.M);
   switch (a.mode) {
-    case EP_GATE: bgemm_dispatch<EP_GATE>(a, s); break;
-    case EP_RESSKIP: bgemm_dispatch<EP_RESSKIP>(a, s); break;
-    case EP_BWD_GATE: bgemm_dispatch<EP_BWD_GATE>(a, s); break;
-    case EP_BWD_CONV: bgemm_dispatch<EP_BWD_CONV>(a, s); break;
-    default: bgemm_dispatch<EP_ACC_F32>(a, s); break;
+    case EP_GATE: bgemm_dispatch<EP_GATE>(a, shape, s); break;
+    case EP_RESSKIP: bgemm_dispatch<EP_RESSKIP>(a, shape, s); break;
+    case EP_BWD_GATE: bgemm_dispatch<EP_BWD_GATE>(a, shape, s); break;
+    case EP_BWD_CONV: bgemm_dispatch<EP_BWD_CONV>(a, shape, s); break;
+    default: bgemm_dispatch<EP_ACC_F32>(a, shape, s); break;
   }
   FACPPG_HIP_CHECK(hipGetLastError());
   return FACPPG_OK;
@@ -449,8 +438,7 @@ int dump_stamps(const char* path, const char* what, const unsigned long long* de
   return FACPPG_OK;
 }
 
-constexpr int FKC = 128, FLDB = FKC + 8, FLDA = C + 8, FLDT = 2 * C + 8, FLDO = 2 * C + 4;
-// LDS of k_wn_fwd: TN * FLDO * 4 bytes: staging (TN * 544) -> gated + tanh|sigmoid tiles (TN * 1568) -> fp32 res/skip tile (TN * 2064)
+// (FKC and the LDS pitches FLDB / FLDA / FLDT / FLDO, and the LDS of k_wn_fwd, wn_fwd_lds: facppg_train_plan.h)
 constexpr int FNCH = (3 * C + NCOND) / FKC;   // 11 chunks
 #ifndef FACPPG_FWD_RING
 #define FACPPG_FWD_RING 8
@@ -690,50 +678,28 @@ __global__ __launch_bounds__(512) void k_wn_fwd(WnFwdArgs p) {
 }
 
 template <int TN>
-int wn_fwd_launch_t(WnFwdArgs& a, hipStream_t s) {
-  constexpr size_t ldsb = (size_t)TN * FLDO * 4;     // 132 096 B (64 positions) / 66 048 B (32)
-  a.ntiles = ((a.L + TN - 1) / TN) * a.B;
-  const int per = (a.ntiles + 7) / 8;
-  {
-    // > 64 KB of dynamic LDS needs the attribute on every device the kernel runs on (see k_wgrad)
-    static std::atomic<unsigned long long> attr_devices{0};
-    int dev = 0;
-    FACPPG_HIP_CHECK(hipGetDevice(&dev));
-    if (dev >= 64 || !((attr_devices.load(std::memory_order_relaxed) >> dev) & 1ull)) {
-      FACPPG_HIP_CHECK(hipFuncSetAttribute((const void*)k_wn_fwd<TN, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)ldsb));
-      FACPPG_HIP_CHECK(hipFuncSetAttribute((const void*)k_wn_fwd<TN, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)ldsb));
-      if (dev < 64) attr_devices.fetch_or(1ull << dev, std::memory_order_relaxed);
-    }
-  }
+int wn_fwd_launch_t(WnFwdArgs& a, const WnStackPlan& p, hipStream_t s) {
+  const size_t ldsb = p.fwd_lds;
+  const dim3 grid(p.fused_grid);
+  a.ntiles = p.ntiles;
+  static std::atomic<unsigned long long> lds_devices{0};
+  if (int rc = ensure_dynamic_lds(lds_devices, ldsb, (const void*)k_wn_fwd<TN, false>, (const void*)k_wn_fwd<TN, true>)) return rc;
   if (const char* path = stamps_path("FACPPG_WN_FWD_STAMPS", s)) {   // debugging aid: per-phase stamps of every tile, appended to `path`
     unsigned long long* d = nullptr;
     FACPPG_HIP_CHECK(hipMalloc(&d, (size_t)a.ntiles * 16 * 8));
     FACPPG_HIP_CHECK(hipMemsetAsync(d, 0, (size_t)a.ntiles * 16 * 8, s));
     a.stamps = d;
-    k_wn_fwd<TN, true><<<dim3(8 * per), 512, ldsb, s>>>(a);
+    k_wn_fwd<TN, true><<<grid, 512, ldsb, s>>>(a);
     const int rc = dump_stamps(path, "fwd", d, a.ntiles, 16, a.d, s);
     FACPPG_HIP_CHECK(hipFree(d));
     return rc;
   }
-  k_wn_fwd<TN, false><<<dim3(8 * per), 512, ldsb, s>>>(a);
+  k_wn_fwd<TN, false><<<grid, 512, ldsb, s>>>(a);
   FACPPG_HIP_CHECK(hipGetLastError());
   return FACPPG_OK;
 }
-// 64-position tiles once they give 160 workgroups, else 32-position tiles (FACPPG_TRAIN_TILE=64 / 32 forces one)
-int tile_positions(int B, int L) {
-  if (const char* e = getenv("FACPPG_TRAIN_TILE")) return atoi(e) == 32 ? 32 : 64;
-  return (long)((L + 63) / 64) * B >= 160 ? 64 : 32;
-}
-int wn_fwd_launch(WnFwdArgs& a, hipStream_t s) {
-  return tile_positions(a.B, a.L) == 64 ? wn_fwd_launch_t<64>(a, s) : wn_fwd_launch_t<32>(a, s);
-}
-// One launch per layer once its tiles fill most of the chip (a tile streams ALL of the layer's weights into its CU: with few
-// tiles the two-launch layer, which deals the weight rows over four times as many workgroups, is as fast or faster).  Measured,
-// whole step, segment 10 000: batch 3 (120 tiles of 32 positions) 10.25 ms fused / 10.20 two launches; batch 6 (240 of 32) 12.7 /
-// 13.6; batch 12 (240 of 64) 18.5 / 20.4.  FACPPG_TRAIN_FUSED_FWD=1 / 0 forces either path (the bit-equality test and A/B timing).
-bool fused_fwd_enabled(int B, int L) {
-  if (const char* e = getenv("FACPPG_TRAIN_FUSED_FWD")) return e[0] != '0';
-  return (long)((L + 31) / 32) * B >= 160;
+int wn_fwd_launch(WnFwdArgs& a, const WnStackPlan& p, hipStream_t s) {
+  return p.tile == 64 ? wn_fwd_launch_t<64>(a, p, s) : wn_fwd_launch_t<32>(a, p, s);
 }
 
 // ------------------------------------------------------------------------------------------------------------
@@ -937,43 +903,28 @@ __global__ __launch_bounds__(512) void k_wn_bwd(WnBwdArgs p) {
 }
 
 template <int TN>
-int wn_bwd_launch_t(WnBwdArgs& a, hipStream_t s) {
-  constexpr size_t ldsb = ((size_t)2 * TN * FLDB + (size_t)TN * FLDA + (size_t)TN * FLDT) * 2;   // 135 168 B (64 positions) / 67 584 B (32)
-  a.ntiles = ((a.L + TN - 1) / TN) * a.B;
-  const int per = (a.ntiles + 7) / 8;
-  {
-    static std::atomic<unsigned long long> attr_devices{0};
-    int dev = 0;
-    FACPPG_HIP_CHECK(hipGetDevice(&dev));
-    if (dev >= 64 || !((attr_devices.load(std::memory_order_relaxed) >> dev) & 1ull)) {
-      FACPPG_HIP_CHECK(hipFuncSetAttribute((const void*)k_wn_bwd<TN, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)ldsb));
-      FACPPG_HIP_CHECK(hipFuncSetAttribute((const void*)k_wn_bwd<TN, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)ldsb));
-      if (dev < 64) attr_devices.fetch_or(1ull << dev, std::memory_order_relaxed);
-    }
-  }
+int wn_bwd_launch_t(WnBwdArgs& a, const WnStackPlan& p, hipStream_t s) {
+  const size_t ldsb = p.bwd_lds;
+  const dim3 grid(p.fused_grid);
+  a.ntiles = p.ntiles;
+  static std::atomic<unsigned long long> lds_devices{0};
+  if (int rc = ensure_dynamic_lds(lds_devices, ldsb, (const void*)k_wn_bwd<TN, false>, (const void*)k_wn_bwd<TN, true>)) return rc;
   if (const char* path = stamps_path("FACPPG_WN_BWD_STAMPS", s)) {
     unsigned long long* d = nullptr;
     FACPPG_HIP_CHECK(hipMalloc(&d, (size_t)a.ntiles * 24 * 8));
     FACPPG_HIP_CHECK(hipMemsetAsync(d, 0, (size_t)a.ntiles * 24 * 8, s));
     a.stamps = d;
-    k_wn_bwd<TN, true><<<dim3(8 * per), 512, ldsb, s>>>(a);
+    k_wn_bwd<TN, true><<<grid, 512, ldsb, s>>>(a);
     const int rc = dump_stamps(path, "bwd", d, a.ntiles, 24, a.d, s);
     FACPPG_HIP_CHECK(hipFree(d));
     return rc;
   }
-  k_wn_bwd<TN, false><<<dim3(8 * per), 512, ldsb, s>>>(a);
+  k_wn_bwd<TN, false><<<grid, 512, ldsb, s>>>(a);
   FACPPG_HIP_CHECK(hipGetLastError());
   return FACPPG_OK;
 }
-int wn_bwd_launch(WnBwdArgs& a, hipStream_t s) {
-  return tile_positions(a.B, a.L) == 64 ? wn_bwd_launch_t<64>(a, s) : wn_bwd_launch_t<32>(a, s);
-}
-// FACPPG_TRAIN_FUSED_BWD=1 / 0 forces either path.  The backward pair is worth one launch much earlier than the forward pair (its
-// tiles stream 1 MB of weights, not 1.7, and the two launches it replaces are the more latency-bound ones): batch 3, whole step,
-// 10.8 ms two launches / 10.5 fused with 64-position tiles / 10.2 with 32.
-bool fused_bwd_enabled(int B, int L) {
-  if (const char* e = getenv("FACPPG_TRAIN_FUSED_BWD")) return e[0] != '0';
-  return (long)((L + 31) / 32) * B >= 40;
+int wn_bwd_launch(WnBwdArgs& a, const WnStackPlan& p, hipStream_t s) {
+  return p.tile == 64 ? wn_bwd_launch_t<64>(a, p, s) : wn_bwd_launch_t<32>(a, p, s);
 }
 
 // ------------------------------------------------------------------------------------------------------------
@@ -984,8 +935,7 @@ bool fused_bwd_enabled(int B, int L) {
 // (1 280 contiguous bytes per position).  Replaces k_bgemm<EP_ACC_F32> here (128 x 128 tiles, 4 waves, lane-per-position
 // float4 read-modify-writes): 136 -> see DESIGN.md us per flow at batch 12.  Same K order, same bits.
 // ------------------------------------------------------------------------------------------------------------
-constexpr int DLDO = NCOND / 2 + 4;     // fp32 tile pitch
-constexpr size_t kDspectLds = (size_t)64 * DLDO * 4;   // 82 944 B (staging 34 816 B first)
+// (the fp32 tile pitch DLDO and the LDS size kDspectLds: facppg_train_plan.h)
 struct DspectArgs {
   const uint4* A;                  // condt image: M = 640, KG = nl * 32
   const bf16_t* dpre; long dpre_one, dpre_bs;   // layer i at dpre + i * dpre_one (elements); [B][HALO + Lr + HALO][512]
@@ -1084,19 +1034,11 @@ __global__ __launch_bounds__(640) void k_dspect(DspectArgs p) {
     *dst = o;
   }
 }
-int dspect_launch(DspectArgs& a, hipStream_t s) {
-  a.ntiles = 2 * ((a.L + 63) / 64) * a.B;
-  const int per = (a.ntiles + 7) / 8;
-  {
-    static std::atomic<unsigned long long> attr_devices{0};
-    int dev = 0;
-    FACPPG_HIP_CHECK(hipGetDevice(&dev));
-    if (dev >= 64 || !((attr_devices.load(std::memory_order_relaxed) >> dev) & 1ull)) {
-      FACPPG_HIP_CHECK(hipFuncSetAttribute((const void*)k_dspect, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kDspectLds));
-      if (dev < 64) attr_devices.fetch_or(1ull << dev, std::memory_order_relaxed);
-    }
-  }
-  k_dspect<<<dim3(8 * per), 640, kDspectLds, s>>>(a);
+int dspect_launch(DspectArgs& a, const WnStackPlan& p, hipStream_t s) {
+  a.ntiles = p.dspect_ntiles;
+  static std::atomic<unsigned long long> lds_devices{0};
+  if (int rc = ensure_dynamic_lds(lds_devices, p.dspect_lds, (const void*)k_dspect)) return rc;
+  k_dspect<<<dim3(p.dspect_grid), 640, p.dspect_lds, s>>>(a);
   FACPPG_HIP_CHECK(hipGetLastError());
   return FACPPG_OK;
 }
@@ -1125,7 +1067,7 @@ struct WgradArgs {
   int nsplit;        // the B * ceil(L/64) position chunks are dealt to nsplit workgroups per output tile ...
   float* part;       // ... which leave partial sums [prob][split][M][K] here (nsplit > 1); k_wgrad_reduce adds them in order
 };
-constexpr int LDP = 64 + 8;   // LDS pitch (positions) of the transposed images
+// (LDP, the LDS pitch (positions) of the transposed images: facppg_train_plan.h)
 
 // 8 x 8 transpose of 16-bit elements held as r[pos][4 dwords] -> t[ch][4 dwords]
 __device__ __forceinline__ void transpose8x8(const uint4 (&r)[8], uint4 (&t)[8]) {
@@ -1398,7 +1340,6 @@ __global__ void k_wgrad_reduce(WgradArgs wa) {
 
 // The ordered sums of SEVERAL k_wgrad / k_wgrad2 launches' partials in one launch (a flow's tap, conditioning and res/skip products
 // each leave theirs in a region of their own): same sums in the same order as k_wgrad_reduce per launch.
-constexpr int MAXRED = 48;
 struct ReduceProb { const float* part; float* out; size_t pstride; long o_sm, o_sk; int nsplit, M, K; };
 struct ReduceSet {
   ReduceProb p[MAXRED];
@@ -1446,106 +1387,46 @@ int reduce_launch(ReduceSet& rs, hipStream_t s) {
   return FACPPG_OK;
 }
 
-constexpr int WG_MAXSPLIT = 8;
-// launches one batch of problems that share (M, K) tile counts; partial buffer: nprob * nsplit * maxM * maxK floats
-// 256 x 256 tiles (k_wgrad2) when they give >= 32 tiles and every workgroup then has >= 24 chunks of positions; FACPPG_WGRAD_TILE=128|256 forces
-// the split count of a k_wgrad2 launch and whether the launch is the one to use (shared with facppg_wn_bf16_launch_plan)
-bool wgrad2_wanted(int nprob, int maxM, int maxK, int B, int L, size_t part_bytes, int* ns_out = nullptr) {
-  const int tiles = ((maxK + 255) / 256) * ((maxM + 255) / 256) * nprob;
-  const int nall = B * ((L + 63) / 64);
-  int ns = std::max(1, std::min(std::min(256 / std::max(tiles, 1), 8), nall));      // one workgroup per CU (144 KB of LDS each): never more than 256; every split gets a chunk
-  while (ns > 1 && (size_t)nprob * ns * maxM * maxK * 4 > part_bytes) --ns;
-  if (ns_out) *ns_out = ns;
-  const char* e = getenv("FACPPG_WGRAD_TILE");
-  return e ? atoi(e) == 256 : (tiles >= 32 && nall / ns >= 24);
-}
-int wgrad2_launch(WgradArgs& wa, int nprob, int maxM, int maxK, float* part, size_t part_bytes, hipStream_t s, bool* done, ReduceSet* defer = nullptr) {
-  *done = false;
-  const int tk = (maxK + 255) / 256, tm = (maxM + 255) / 256;
-  int ns = 1;
-  if (!wgrad2_wanted(nprob, maxM, maxK, wa.B, wa.L, part_bytes, &ns)) return FACPPG_OK;
-  wa.nsplit = ns; wa.part = part; wa.pstride = (size_t)maxM * maxK;
-  wa.tiles_k = tk; wa.tiles_m = tm; wa.ngroups = nprob * ns; wa.xcd_map = 1;
-  constexpr size_t kLds = (size_t)2 * 2 * 256 * LDP * sizeof(bf16_t);   // 147 456 B
-  {
-    static std::atomic<unsigned long long> attr_devices{0};
-    int dev = 0;
-    FACPPG_HIP_CHECK(hipGetDevice(&dev));
-    if (dev >= 64 || !((attr_devices.load(std::memory_order_relaxed) >> dev) & 1ull)) {
-      FACPPG_HIP_CHECK(hipFuncSetAttribute((const void*)k_wgrad2, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLds));
-      if (dev < 64) attr_devices.fetch_or(1ull << dev, std::memory_order_relaxed);
-    }
-  }
-  k_wgrad2<<<dim3(8 * ((wa.ngroups + 7) / 8) * tk * tm), 512, kLds, s>>>(wa);
-  if (ns > 1) {
-    if (defer) defer->add(wa, nprob);
-    else k_wgrad_reduce<<<dim3((maxM * maxK + 255) / 256, nprob), 256, 0, s>>>(wa);
-  }
-  FACPPG_HIP_CHECK(hipGetLastError());
-  *done = true;
-  return FACPPG_OK;
-}
-
+// launches one batch of problems that share (M, K) tile counts the way plan_wgrad decided: k_wgrad2 (256 x 256 tiles) or k_wgrad
+// (128 x 128); partial buffer: p.part_floats floats.
 // defer: the partials' ordered sum is left to the caller's reduce_launch (one launch for several of these)
-int wgrad_launch(WgradArgs& wa, int nprob, int maxM, int maxK, float* part, size_t part_bytes, hipStream_t s, ReduceSet* defer = nullptr) {
-  FACPPG_REQUIRE(maxM % 128 == 0 && maxK % 128 == 0, FACPPG_EINVAL, "k_wgrad: M and K must be multiples of 128 (got %d, %d)", maxM, maxK);
+int wgrad_launch(WgradArgs& wa, const WgradPlan& p, int nprob, int maxM, int maxK, float* part, hipStream_t s, ReduceSet* defer = nullptr) {
+  FACPPG_REQUIRE(p.rc == FACPPG_OK, p.rc, "%s", p.msg);
   FACPPG_REQUIRE(!defer || defer->n + nprob <= MAXRED, FACPPG_EINVAL, "too many deferred weight-gradient problems");
-  {
-    bool done = false;
-    if (int rc = wgrad2_launch(wa, nprob, maxM, maxK, part, part_bytes, s, &done, defer)) return rc;
-    if (done) return FACPPG_OK;
-  }
-  const int tiles = ((maxK + 127) / 128) * ((maxM + 127) / 128) * nprob;
-  const int nall = wa.B * ((wa.L + 63) / 64);
-  // about ONE workgroup per CU (two fit, 73 KB of LDS each): measured at batch 3 / 12, whole step, aiming at 64 / 128 / 256 / 384 /
-  // 512 / 768 / 1536 / 3072 workgroups: 11.48 / 11.23 / 11.09 / 11.18 / 11.31 / 11.53 / 11.99 / 12.93 ms and 24.42 / 23.43 / 22.46 /
-  // 22.55 / 22.66 / 23.06 / 23.12 / 24.26 ms -- every further split adds a 64 KB partial tile per workgroup and a longer reduction
-  int ns = (256 + tiles - 1) / tiles;
-  ns = std::max(1, std::min(std::min(ns, WG_MAXSPLIT), nall));
-  while (ns > 1 && (size_t)nprob * ns * maxM * maxK * 4 > part_bytes) --ns;
-  wa.nsplit = ns; wa.part = part; wa.pstride = (size_t)maxM * maxK;
-  constexpr size_t kWgradLds = (size_t)2 * 2 * 128 * LDP * sizeof(bf16_t);   // 73 728 B
-  {
-    // > 64 KB of dynamic LDS needs the attribute on EVERY device the kernel runs on (one bit per device; a second thread
-    // setting it again is harmless)
-    static std::atomic<unsigned long long> attr_devices{0};
-    int dev = 0;
-    FACPPG_HIP_CHECK(hipGetDevice(&dev));
-    if (dev >= 64 || !((attr_devices.load(std::memory_order_relaxed) >> dev) & 1ull)) {
-      FACPPG_HIP_CHECK(hipFuncSetAttribute((const void*)k_wgrad<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kWgradLds));
-      FACPPG_HIP_CHECK(hipFuncSetAttribute((const void*)k_wgrad<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kWgradLds));
-      if (dev < 64) attr_devices.fetch_or(1ull << dev, std::memory_order_relaxed);
-    }
-  }
-  {
-    const char* e_map = getenv("FACPPG_WGRAD_NO_XCD_MAP");
-    const bool no_map = e_map && e_map[0] == '1';
-    wa.tiles_k = (maxK + 127) / 128; wa.tiles_m = (maxM + 127) / 128; wa.ngroups = nprob * ns; wa.xcd_map = no_map ? 0 : 1;
+  wa.nsplit = p.ns; wa.part = part; wa.pstride = p.pstride;
+  wa.tiles_k = p.tiles_k; wa.tiles_m = p.tiles_m; wa.ngroups = p.ngroups; wa.xcd_map = p.xcd_map;
+  const dim3 grid(p.grid[0], p.grid[1], p.grid[2]);
+  // > 64 KB of dynamic LDS needs the attribute on EVERY device the kernel runs on (ensure_dynamic_lds)
+  if (p.tile == 256) {
+    static std::atomic<unsigned long long> lds_devices{0};
+    if (int rc = ensure_dynamic_lds(lds_devices, p.lds, (const void*)k_wgrad2)) return rc;
+    k_wgrad2<<<grid, 512, p.lds, s>>>(wa);
+  } else {
+    static std::atomic<unsigned long long> lds_devices{0};
+    if (int rc = ensure_dynamic_lds(lds_devices, p.lds, (const void*)k_wgrad<false>, (const void*)k_wgrad<true>)) return rc;
     const char* spath = stamps_path("FACPPG_WGRAD_STAMPS", s);
     if (spath) {
       FACPPG_HIP_CHECK(hipMalloc(&wa.stamps, 64 * 24 * 8));
       FACPPG_HIP_CHECK(hipMemsetAsync(wa.stamps, 0, 64 * 24 * 8, s));
-    }
-    const dim3 grid = wa.xcd_map ? dim3(8 * ((wa.ngroups + 7) / 8) * wa.tiles_k * wa.tiles_m) : dim3(wa.tiles_k, wa.tiles_m, nprob * ns);
-    if (spath) k_wgrad<true><<<grid, 256, kWgradLds, s>>>(wa);
-    else k_wgrad<false><<<grid, 256, kWgradLds, s>>>(wa);
-    if (spath) {
+      k_wgrad<true><<<grid, 256, p.lds, s>>>(wa);
       unsigned long long h[64 * 24];
       FACPPG_HIP_CHECK(hipMemcpyAsync(h, wa.stamps, sizeof(h), hipMemcpyDeviceToHost, s));
       FACPPG_HIP_CHECK(hipStreamSynchronize(s));
       FACPPG_HIP_CHECK(hipFree(wa.stamps));
       wa.stamps = nullptr;
       if (FILE* f = fopen(spath, "a")) {
-        fprintf(f, "launch wgrad nprob %d M %d K %d nsplit %d\n", nprob, maxM, maxK, ns);
+        fprintf(f, "launch wgrad nprob %d M %d K %d nsplit %d\n", nprob, maxM, maxK, p.ns);
         for (int t = 0; t < 64; ++t) {
           for (int j = 0; j < 24; ++j) fprintf(f, "%llu ", j == 23 ? h[t * 24 + j] : (h[t * 24 + j] ? h[t * 24 + j] - h[t * 24] : 0ull));
           fprintf(f, "\n");
         }
         fclose(f);
       }
+    } else {
+      k_wgrad<false><<<grid, 256, p.lds, s>>>(wa);
     }
   }
-  if (ns > 1) {
+  if (p.ns > 1) {
     if (defer) defer->add(wa, nprob);
     else k_wgrad_reduce<<<dim3((maxM * maxK + 255) / 256, nprob), 256, 0, s>>>(wa);
   }
@@ -1556,7 +1437,7 @@ int wgrad_launch(WgradArgs& wa, int nprob, int maxM, int maxK, float* part, size
 // out[m] = sum_{b, n < L} y[b][row0 + n][m]  (bias gradients).  Stage 1: workgroup (channel tile, row slice, problem)
 // sums its slice of the B*L rows (4 row lanes x 64 channels per wavefront-row); stage 2 adds the slices in index
 // order -- a fixed summation order whatever the grid, so the result is bit-reproducible.
-constexpr int CS_SLICES = 256, MAXCS = 16;
+// (CS_SLICES row slices per problem, MAXCS problems per launch: facppg_train_plan.h)
 struct ColsumProb { const void* y; long bs; int ld, row0, M; float* out; float* out2; };   // out2: optional second copy of the sums
 // part [prob][CS_SLICES][1024]; bc: further copies of problem bc_prob's sums (the skip half of every layer's res_skip bias gradient
 // is the column sum of the same dskip)
@@ -2003,42 +1884,7 @@ __global__ __launch_bounds__(256) void k_up_wgrad(const float* __restrict__ mel,
     for (int i = 0; i < NM; ++i) dW[((size_t)i * NM + m) * ksize + k] = acc[i];
 }
 
-// ---- layouts of the caller-owned buffers -------------------------------------------------------------------------
-struct StateLayout { size_t h, ts, acts, skip, total; size_t h_one, ts_one, acts_one; };
-StateLayout state_layout(int nl, int B, int Lr) {
-  StateLayout s;
-  const int Lp = HALO + Lr + HALO;
-  size_t off = 0;
-  auto take = [&](size_t bytes) { size_t o = off; off += (bytes + 255) / 256 * 256; return o; };
-  s.h_one = (size_t)B * Lp * C * 2; s.ts_one = (size_t)B * Lr * 2 * C * 2; s.acts_one = (size_t)B * Lr * C * 2;
-  s.h = take(s.h_one * (nl + 1)); s.ts = take(s.ts_one * nl); s.acts = take(s.acts_one * nl); s.skip = take((size_t)B * Lr * C * 4);
-  s.total = off;
-  return s;
-}
-struct ScratchLayout { size_t w1, w2, rst, int_, condt, dpre, dh, dskip, part, cspart, wgpart, wgpart_bytes, total; size_t w1_one, w2_one, rst_one, int_one, dpre_one, dh_one; };
-constexpr int K1 = 3 * C + NCOND;   // 1408
-#ifndef FACPPG_SMALL_PARTS
-#define FACPPG_SMALL_PARTS 256
-#endif
-constexpr int SMALL_PARTS = FACPPG_SMALL_PARTS;   // partial sums of the <= 8-channel weight gradients (one block each)
-ScratchLayout scratch_layout(int nl, int B, int Lr) {
-  ScratchLayout s;
-  const int Lp = HALO + Lr + HALO;
-  size_t off = 0;
-  auto take = [&](size_t bytes) { size_t o = off; off += (bytes + 255) / 256 * 256; return o; };
-  s.w1_one = (size_t)16 * (K1 / 16) * 64 * 16; s.w2_one = (size_t)16 * (C / 16) * 64 * 16;
-  s.rst_one = (size_t)8 * (2 * C / 16) * 64 * 16; s.int_one = (size_t)8 * (3 * 2 * C / 16) * 64 * 16;
-  s.dpre_one = (size_t)B * Lp * 2 * C * 2; s.dh_one = (size_t)B * Lr * C * 2;
-  s.w1 = take(s.w1_one * nl); s.w2 = take(s.w2_one * nl); s.rst = take(s.rst_one * nl); s.int_ = take(s.int_one * nl);
-  s.condt = take((size_t)(NCOND / 32) * (nl * 2 * C / 16) * 64 * 16);
-  s.dpre = take(s.dpre_one * nl); s.dh = take(s.dh_one * (nl + 1)); s.dskip = take(s.dh_one);
-  s.part = take((size_t)SMALL_PARTS * 9 * C * 4);
-  s.cspart = take((size_t)MAXCS * CS_SLICES * 1024 * 4);
-  s.wgpart_bytes = (size_t)3 * nl * 5 * (2 * C) * C * 4;      // 5 splits of the largest batch (3 taps x layers x [512 x 256]; k_wgrad2)
-  s.wgpart = take(s.wgpart_bytes);
-  s.total = off;
-  return s;
-}
+// (the layouts of the caller-owned buffers -- state, packed images, work, scratch -- and SMALL_PARTS: facppg_train_plan.h)
 
 // collects pack jobs and launches them as one grid (blockIdx.y = job)
 struct Packer {
@@ -2094,17 +1940,45 @@ extern "C" size_t facppg_wn_bf16_state_bytes(int n_layers, int B, int L) {
   if (n_layers < 1 || n_layers > 8 || B <= 0 || L <= 0) return 0;
   return state_layout(n_layers, B, pad_len(L)).total;
 }
+// the two host-only diagnostics: what the entry points below would launch, from the plan functions they execute
+extern "C" int facppg_train_bf16_launch_plan(int n_layers, int B, int L, facppg_train_launch_report* out) {
+  FACPPG_REQUIRE(out && n_layers >= 1 && n_layers <= 8 && B > 0 && L > 0, FACPPG_EINVAL, "bad argument");
+  const TrainTuning t = train_tuning_from_env();
+  const WnStackPlan p = plan_wn_stack(t, n_layers, B, L);
+  const WnWgradPlans w = plan_wn_wgrads(t, n_layers, B, L, wgpart_bytes(n_layers));
+  const EdgePlan e = plan_edges(t, B, L);
+  facppg_train_launch_report r = {};
+  r.tile_positions = p.tile; r.fused_fwd = p.fused_fwd; r.fused_bwd = p.fused_bwd; r.fused_workgroups = p.fused_grid;
+  const BgemmShape* g[5] = {&p.gate, &p.resskip, &p.resskip_last, &p.gate_bwd, &p.conv_bwd};
+  for (int i = 0; i < 5; ++i) { r.gemm_cols[i] = g[i]->cols; r.gemm_workgroups[i] = g[i]->grid; }
+  r.dspect_bgemm = p.dspect_bgemm;
+  r.dspect_cols = p.dspect_bgemm ? p.dspect_acc.cols : 0;
+  r.dspect_workgroups = p.dspect_bgemm ? p.dspect_acc.grid : p.dspect_grid;
+  r.dspect_lds_bytes = p.dspect_bgemm ? 0 : (int32_t)p.dspect_lds;
+  const WgradPlan* wp[3] = {&w.taps, &w.cond, &w.resskip};
+  for (int i = 0; i < 3; ++i) {
+    r.wgrad_tile[i] = wp[i]->tile; r.wgrad_splits[i] = wp[i]->ns; r.wgrad_workgroups[i] = (int32_t)wp[i]->workgroups();
+    r.wgrad_xcd_map[i] = wp[i]->xcd_map;
+  }
+  r.pack_per_step = t.pack_per_step; r.edge_nchunk = e.nchunk; r.edge_n_parts = e.n_parts; r.upsample_gemm = t.upsample_gemm;
+  r.fwd_lds_bytes = (int32_t)p.fwd_lds; r.bwd_lds_bytes = (int32_t)p.bwd_lds;
+  r.wgrad_lds_bytes = (int32_t)kWgradLds; r.wgrad2_lds_bytes = (int32_t)kWgrad2Lds;
+  *out = r;
+  return FACPPG_OK;
+}
 extern "C" int facppg_wn_bf16_launch_plan(int n_layers, int B, int L) {
   if (n_layers < 1 || n_layers > 8 || B <= 0 || L <= 0) return FACPPG_EINVAL;
-  int plan = tile_positions(B, L) << 8;
-  if (fused_fwd_enabled(B, L)) plan |= 1;
-  if (fused_bwd_enabled(B, L) && n_layers > 1) plan |= 2;
-  if (wgrad2_wanted(n_layers * 3, 2 * C, C, B, L, scratch_layout(n_layers, B, pad_len(L)).wgpart_bytes)) plan |= 4;
+  const TrainTuning t = train_tuning_from_env();
+  const WnStackPlan p = plan_wn_stack(t, n_layers, B, L);
+  int plan = p.tile << 8;
+  if (p.fused_fwd) plan |= 1;
+  if (p.fused_bwd) plan |= 2;
+  if (plan_wgrad(t, n_layers * 3, 2 * C, C, B, L, wgpart_bytes(n_layers)).tile == 256) plan |= 4;
   return plan;
 }
 extern "C" size_t facppg_wn_bf16_scratch_bytes(int n_layers, int B, int L) {
   if (n_layers < 1 || n_layers > 8 || B <= 0 || L <= 0) return 0;
-  return scratch_layout(n_layers, B, pad_len(L)).total + 2 * C * 4 * 8;
+  return scratch_layout(n_layers, B, pad_len(L)).total + scratch_bias_bytes();
 }
 
 extern "C" int facppg_spect_to_bf16(const float* spect_dev, int B, int channels, int L, int ld, void* out_dev, void* stream) {
@@ -2213,17 +2087,12 @@ UpDims up_dims(int B, int T, int nm, int hop, int ksize, int L) {
 struct UpWs { size_t fold, aimg, out, total; };
 UpWs up_ws(const UpDims& d, bool backward) {   // forward: Wfold | A(melshift) | out;  backward: dWfold | A(melshift^T) | dup
   UpWs w;
-  size_t off = 0;
-  auto take = [&](size_t bytes) { size_t o = off; off += (bytes + 255) / 256 * 256; return o; };
-  w.fold = take((size_t)round_up(d.K, 32) * d.N * 4);
-  w.aimg = take(packed_a_float4s(backward ? d.K : d.rows, backward ? d.rows : d.K) * 16);
-  w.out = take((size_t)d.rows * d.N * 4);
-  w.total = off;
+  Carve c;
+  w.fold = c.take((size_t)round_up(d.K, 32) * d.N * 4);
+  w.aimg = c.take(packed_a_float4s(backward ? d.K : d.rows, backward ? d.rows : d.K) * 16);
+  w.out = c.take((size_t)d.rows * d.N * 4);
+  w.total = c.off;
   return w;
-}
-bool upsample_gemm() {
-  const char* e = getenv("FACPPG_UPSAMPLE_GEMM");
-  return !(e && e[0] == '0');
 }
 
 extern "C" size_t facppg_upsample_forward_workspace_bytes(int B, int T, int n_mel, int hop, int ksize, int L) {
@@ -2240,7 +2109,7 @@ extern "C" int facppg_upsample_regroup_bf16(const float* mel_dev, const float* u
   hipStream_t s = (hipStream_t)stream_;
   const UpDims d = up_dims(B, T, n_mel, hop, ksize, L);
   FACPPG_HIP_CHECK(hipMemsetAsync(spect_pm_dev, 0, (size_t)B * d.Lr * n_mel * 8 * 2, s));   // rows >= L are zero
-  if (!upsample_gemm() || !ws_dev) {
+  if (!train_tuning_from_env().upsample_gemm || !ws_dev) {
     k_up_fwd<<<dim3((d.Tq + UQ - 1) / UQ, n_mel, B), 256, (size_t)n_mel * (UQ + UMAXJ) * 4, s>>>(mel_dev, up_w_dev, up_b_dev, (bf16_t*)spect_pm_dev, T, d.Tq,
                                                                                               n_mel, hop, ksize, d.Lr, L * 8);
     FACPPG_HIP_CHECK(hipGetLastError());
@@ -2264,7 +2133,7 @@ extern "C" int facppg_upsample_regroup_bf16(const float* mel_dev, const float* u
 }
 
 extern "C" size_t facppg_upsample_backward_workspace_bytes(int B, int T, int n_mel, int hop, int ksize, int L) {
-  const size_t cs = (size_t)MAXCS * CS_SLICES * 1024 * 4;
+  const size_t cs = cspart_bytes();
   if (B <= 0 || T <= 0 || n_mel <= 0 || hop <= 0 || ksize <= 0 || L <= 0) return cs;
   return cs + up_ws(up_dims(B, T, n_mel, hop, ksize, L), true).total;
 }
@@ -2273,12 +2142,12 @@ extern "C" int facppg_upsample_regroup_backward(const float* mel_dev, const floa
                                                 int L, float* d_up_w_dev, float* d_up_b_dev, void* ws_dev, size_t ws_bytes, void* stream_) {
   FACPPG_REQUIRE(mel_dev && dspect_pm_dev && d_up_w_dev && d_up_b_dev && ws_dev, FACPPG_EINVAL, "NULL argument");
   FACPPG_REQUIRE(B > 0 && T > 0 && L > 0 && n_mel == 80 && hop % 8 == 0 && hop > 0, FACPPG_EUNSUPPORTED, "upsample backward: n_mel must be 80, hop a multiple of 8");
-  const size_t cs = (size_t)MAXCS * CS_SLICES * 1024 * 4;
+  const size_t cs = cspart_bytes();
   FACPPG_REQUIRE(ws_bytes >= cs, FACPPG_EWORKSPACE, "workspace too small");
   hipStream_t s = (hipStream_t)stream_;
   const UpDims d = up_dims(B, T, n_mel, hop, ksize, L);
   const UpWs w = up_ws(d, true);
-  if (upsample_gemm() && ws_bytes >= cs + w.total && (ksize + hop - 1) / hop <= UMAXJ) {
+  if (train_tuning_from_env().upsample_gemm && ws_bytes >= cs + w.total && (ksize + hop - 1) / hop <= UMAXJ) {
     char* Wk = (char*)ws_dev + cs;
     float* fold = (float*)(Wk + w.fold);
     float4* aimg = (float4*)(Wk + w.aimg);
@@ -2352,49 +2221,64 @@ __global__ void k_add2_flows(AddBatchN ab, int n) {
 // ---- the stack's launches, shared by the stand-alone WN entry points (facppg_wn_forward_bf16 / _backward_bf16) and the whole-model
 // group entry points (facppg_glow_bf16_*): where the packed operand images, the saved state and the gradients in flight live is
 // the caller's business.
-struct WnPacked {   // bf16 A-operand images of one flow's stack (+ the summed gate biases), see pack_flow_images
+struct WnPacked {   // bf16 A-operand images of one flow's stack (+ the summed gate biases), see add_forward_images / add_backward_images
   const uint4* w1; size_t w1_one; const uint4* w2; size_t w2_one; const uint4* rst; size_t rst_one; const uint4* int_; size_t int_one;
   const uint4* condt; const float* b1;
 };
+WnPacked packed_view(const char* P, const ImageLayout& il, const float* b1) {
+  WnPacked pw;
+  pw.w1 = (const uint4*)(P + il.w1); pw.w1_one = il.w1_one; pw.w2 = (const uint4*)(P + il.w2); pw.w2_one = il.w2_one;
+  pw.rst = (const uint4*)(P + il.rst); pw.rst_one = il.rst_one; pw.int_ = (const uint4*)(P + il.int_); pw.int_one = il.int_one;
+  pw.condt = (const uint4*)(P + il.condt); pw.b1 = b1;
+  return pw;
+}
 struct WnWork {     // gradients in flight of one flow's backward + the partial-sum buffers of its reductions
   char* dpre; size_t dpre_one; char* dh; size_t dh_one; bf16_t* dskip; float* cspart; float* wgpart; size_t wgpart_bytes;
   int wgpart_regions;    // 3: a region of wgpart_bytes per weight-gradient launch of a flow -> ONE ordered reduce for the three; 1: one shared region
 };
+// L: a WorkLayout (three weight-gradient regions) or a ScratchLayout (one)
+template <class L>
+WnWork work_view(char* W, const L& l, int wgpart_regions) {
+  WnWork wk;
+  wk.dpre = W + l.dpre; wk.dpre_one = l.dpre_one; wk.dh = W + l.dh; wk.dh_one = l.dh_one; wk.dskip = (bf16_t*)(W + l.dskip);
+  wk.cspart = (float*)(W + l.cspart); wk.wgpart = (float*)(W + l.wgpart); wk.wgpart_bytes = l.wgpart_bytes; wk.wgpart_regions = wgpart_regions;
+  return wk;
+}
 
 // forward image jobs of one flow: K order tap 0 | tap 1 | tap 2 | cond, gate-interleaved rows; res/skip rows as they are
-void add_forward_images(Packer& pk, const facppg_wn_weights* wts, int nl, char* w1, size_t w1_one, char* w2, size_t w2_one) {
+void add_forward_images(Packer& pk, const facppg_wn_weights* wts, int nl, char* P, const ImageLayout& il) {
   for (int i = 0; i < nl; ++i) {
     const int last = i == nl - 1;
-    uint4* d1 = (uint4*)(w1 + w1_one * i);
+    uint4* d1 = (uint4*)(P + il.w1 + il.w1_one * i);
     pk.add(wts->in_w[i], d1, 2 * C, K1 / 16, 0, C, 3, (long)C * 3, 3, 1, 0, 1);
     pk.add(wts->cond_w[i], d1, 2 * C, K1 / 16, 3 * C, NCOND, 1, NCOND, 1, 0, 0, 1);
-    pk.add(wts->rs_w[i], (uint4*)(w2 + w2_one * i), last ? C : 2 * C, C / 16, 0, C, 1, C, 1, 0, 0, 0);
+    pk.add(wts->rs_w[i], (uint4*)(P + il.w2 + il.w2_one * i), last ? C : 2 * C, C / 16, 0, C, 1, C, 1, 0, 0, 0);
   }
 }
 // transposed images for the backward
-void add_backward_images(Packer& pk, const facppg_wn_weights* wts, int nl, char* rst, size_t rst_one, char* int_, size_t int_one, uint4* condt) {
+void add_backward_images(Packer& pk, const facppg_wn_weights* wts, int nl, char* P, const ImageLayout& il) {
   for (int i = 0; i < nl; ++i) {
     const int last = i == nl - 1;
     // dacts[c] = sum_r Wrs[r][c] * [dh_next (res rows) | dskip (skip rows)][r]; last layer: skip rows only
-    pk.add(wts->rs_w[i], (uint4*)(rst + rst_one * i), C, (last ? C : 2 * C) / 16, 0, last ? C : 2 * C, 1, 1, C, 0, 0, 0);
+    pk.add(wts->rs_w[i], (uint4*)(P + il.rst + il.rst_one * i), C, (last ? C : 2 * C) / 16, 0, last ? C : 2 * C, 1, 1, C, 0, 0, 0);
     // dh[m] += sum_{tap,o} Win[o][m][tap] * dpre[n - (tap-1) d][o]
-    pk.add(wts->in_w[i], (uint4*)(int_ + int_one * i), C, 3 * 2 * C / 16, 0, 2 * C, 3, 3, (long)C * 3, 1, 0, 0);
+    pk.add(wts->in_w[i], (uint4*)(P + il.int_ + il.int_one * i), C, 3 * 2 * C / 16, 0, 2 * C, 3, 3, (long)C * 3, 1, 0, 0);
     // dspect[j] = sum_{i,o} Wcond_i[o][j] * dpre_i[o]: one image, K = nl * 512
-    pk.add(wts->cond_w[i], condt, NCOND, nl * 2 * C / 16, i * 2 * C, 2 * C, 1, 1, NCOND, 0, 0, 0);
+    pk.add(wts->cond_w[i], (uint4*)(P + il.condt), NCOND, nl * 2 * C / 16, i * 2 * C, 2 * C, 1, 1, NCOND, 0, 0, 0);
   }
 }
 
 // the nl layers of one stack from h_0 (already in `S`) to the skip sum (glow.py:158-174)
-int wn_layers_forward(const facppg_wn_weights* wts, int nl, const WnPacked& pw, const void* spect_pm_dev, int B, int L, char* S, hipStream_t s) {
+int wn_layers_forward(const WnStackPlan& plan, const facppg_wn_weights* wts, int nl, const WnPacked& pw, const void* spect_pm_dev, int B, int L,
+                      char* S, hipStream_t s) {
   const int Lr = pad_len(L), Lp = HALO + Lr + HALO;
   const StateLayout st = state_layout(nl, B, Lr);
-  const bool fused = fused_fwd_enabled(B, L);
   for (int i = 0; i < nl; ++i) {
     const int last = i == nl - 1, d = 1 << i;
     const bf16_t* h_in = (const bf16_t*)(S + st.h + st.h_one * i);
     const uint4* A1 = (const uint4*)((const char*)pw.w1 + pw.w1_one * i);
     const uint4* A2 = (const uint4*)((const char*)pw.w2 + pw.w2_one * i);
-    if (fused) {
+    if (plan.fused_fwd) {
       WnFwdArgs f;
       memset(&f, 0, sizeof(f));
       f.A1 = A1; f.A2 = A2;
@@ -2403,7 +2287,7 @@ int wn_layers_forward(const facppg_wn_weights* wts, int nl, const WnPacked& pw, 
       f.b1 = pw.b1 + 2 * C * i; f.b2 = wts->rs_b[i];
       f.acts = (bf16_t*)(S + st.acts + st.acts_one * i); f.ts = (bf16_t*)(S + st.ts + st.ts_one * i); f.skip = (float*)(S + st.skip);
       f.L = L; f.Lr = Lr; f.B = B; f.d = d; f.first = i == 0; f.last = last;
-      if (int rc = wn_fwd_launch(f, s)) return rc;
+      if (int rc = wn_fwd_launch(f, plan, s)) return rc;
       continue;
     }
     BGemmArgs g;
@@ -2413,14 +2297,14 @@ int wn_layers_forward(const facppg_wn_weights* wts, int nl, const WnPacked& pw, 
     g.seg[3] = Seg{(const bf16_t*)spect_pm_dev, (long)Lr * NCOND, NCOND, 0, NCOND};
     g.mode = EP_GATE; g.bias = pw.b1 + 2 * C * i; g.Lr = Lr;
     g.acts = (bf16_t*)(S + st.acts + st.acts_one * i); g.ts = (bf16_t*)(S + st.ts + st.ts_one * i);
-    if (int rc = bgemm_launch(g, s)) return rc;
+    if (int rc = bgemm_launch(g, plan.gate, s)) return rc;
     BGemmArgs r;
     memset(&r, 0, sizeof(r));
     r.A = A2; r.KG = C / 16; r.M = last ? C : 2 * C; r.N = L; r.B = B; r.nseg = 1;
     r.seg[0] = Seg{g.acts, (long)Lr * C, C, 0, C};
     r.mode = EP_RESSKIP; r.bias = wts->rs_b[i]; r.Lr = Lr; r.h_in = h_in; r.h_out = (bf16_t*)(S + st.h + st.h_one * (i + 1));
     r.h_bs = (long)Lp * C; r.h_row0 = HALO; r.skip = (float*)(S + st.skip); r.first = i == 0; r.last = last;
-    if (int rc = bgemm_launch(r, s)) return rc;
+    if (int rc = bgemm_launch(r, last ? plan.resskip_last : plan.resskip, s)) return rc;
   }
   return FACPPG_OK;
 }
@@ -2435,7 +2319,9 @@ extern "C" int facppg_wn_forward_bf16(const facppg_wn_weights* wts, int n_in, in
   const StateLayout st = state_layout(nl, B, Lr);
   const ScratchLayout sc = scratch_layout(nl, B, Lr);
   FACPPG_REQUIRE(state_bytes >= st.total, FACPPG_EWORKSPACE, "state has %zu bytes, need %zu", state_bytes, st.total);
-  FACPPG_REQUIRE(scratch_bytes >= sc.total + 2 * C * 4 * 8, FACPPG_EWORKSPACE, "scratch has %zu bytes, need %zu", scratch_bytes, sc.total + 2 * C * 4 * 8);
+  FACPPG_REQUIRE(scratch_bytes >= sc.total + scratch_bias_bytes(), FACPPG_EWORKSPACE, "scratch has %zu bytes, need %zu", scratch_bytes,
+                 sc.total + scratch_bias_bytes());
+  const WnStackPlan plan = plan_wn_stack(train_tuning_from_env(), nl, B, L);
   hipStream_t s = (hipStream_t)stream_;
   char* S = (char*)state_dev;
   char* W = (char*)scratch_dev;
@@ -2450,28 +2336,24 @@ extern "C" int facppg_wn_forward_bf16(const facppg_wn_weights* wts, int n_in, in
   }
   {
     Packer pk;
-    add_forward_images(pk, wts, nl, W + sc.w1, sc.w1_one, W + sc.w2, sc.w2_one);
+    add_forward_images(pk, wts, nl, W, sc);
     if (int rc = pk.launch(s)) return rc;
     AddBatch ab;
     for (int i = 0; i < nl; ++i) { ab.a[i] = wts->in_b[i]; ab.b[i] = wts->cond_b[i]; }
     k_add2<<<dim3(2, nl), 256, 0, s>>>(ab, b1, 2 * C);
   }
   k_t_start<<<dim3((L + 31) / 32, B), 256, 0, s>>>(a0_dev, wts->start_w, wts->start_b, (bf16_t*)(S + st.h), n_in, L, Lp);
-  WnPacked pw;
-  memset(&pw, 0, sizeof(pw));
-  pw.w1 = (const uint4*)(W + sc.w1); pw.w1_one = sc.w1_one; pw.w2 = (const uint4*)(W + sc.w2); pw.w2_one = sc.w2_one; pw.b1 = b1;
-  if (int rc = wn_layers_forward(wts, nl, pw, spect_pm_dev, B, L, S, s)) return rc;
+  if (int rc = wn_layers_forward(plan, wts, nl, packed_view(W, sc, b1), spect_pm_dev, B, L, S, s)) return rc;
   k_t_end<<<dim3((L + 31) / 32, B), 256, 0, s>>>((const float*)(S + st.skip), wts->end_w, wts->end_b, out_dev, 2 * n_in, L, Lr);
   FACPPG_HIP_CHECK(hipGetLastError());
   return FACPPG_OK;
 }
 
 // The data-gradient chain of one stack, from dskip (already formed from d(out) by the end conv's backward) down to dh_0.
-int wn_layers_backward_data(int nl, const WnPacked& pw, const char* S, const WnWork& wk, int B, int L, hipStream_t s) {
+int wn_layers_backward_data(const WnStackPlan& plan, int nl, const WnPacked& pw, const char* S, const WnWork& wk, int B, int L, hipStream_t s) {
   const int Lr = pad_len(L), Lp = HALO + Lr + HALO;
   const StateLayout st = state_layout(nl, B, Lr);
   bf16_t* dskip = wk.dskip;
-  const bool fused = fused_bwd_enabled(B, L);
   auto rst = [&](int i) { return (const uint4*)((const char*)pw.rst + pw.rst_one * i); };
   auto int_ = [&](int i) { return (const uint4*)((const char*)pw.int_ + pw.int_one * i); };
   auto gate_bwd_launch = [&](int i) -> int {      // dpre_i = gate'(ts_i) * Wrs_i^T [dh_{i+1} ; dskip]
@@ -2484,7 +2366,7 @@ int wn_layers_backward_data(int nl, const WnPacked& pw, const char* S, const WnW
     else { g.nseg = 2; g.seg[0] = Seg{dh_next, (long)Lr * C, C, 0, C}; g.seg[1] = Seg{dskip, (long)Lr * C, C, 0, C}; }
     g.mode = EP_BWD_GATE; g.Lr = Lr; g.ts = (bf16_t*)(S + st.ts + st.ts_one * i); g.dpre = (bf16_t*)(wk.dpre + wk.dpre_one * i);
     g.dpre_bs = (long)Lp * 2 * C;
-    return bgemm_launch(g, s);
+    return bgemm_launch(g, plan.gate_bwd, s);
   };
   auto conv_bwd_launch = [&](int i) -> int {      // dh_i = dh_{i+1} + sum_tap Win_i^T dpre_i(shifted)
     const int last = i == nl - 1, d = 1 << i;
@@ -2495,9 +2377,9 @@ int wn_layers_backward_data(int nl, const WnPacked& pw, const char* S, const WnW
     for (int tp = 0; tp < 3; ++tp) t.seg[tp] = Seg{dpre, (long)Lp * 2 * C, 2 * C, HALO - (tp - 1) * d, 2 * C};
     t.mode = EP_BWD_CONV; t.Lr = Lr; t.dh_next = last ? nullptr : (const bf16_t*)(wk.dh + wk.dh_one * (i + 1));
     t.dh_out = (bf16_t*)(wk.dh + wk.dh_one * i);
-    return bgemm_launch(t, s);
+    return bgemm_launch(t, plan.conv_bwd, s);
   };
-  if (fused && nl > 1) {
+  if (plan.fused_bwd) {
     if (int rc = gate_bwd_launch(nl - 1)) return rc;
     for (int i = nl - 1; i >= 1; --i) {           // conv backward of layer i + gate backward of layer i-1 in one launch
       WnBwdArgs f;
@@ -2508,7 +2390,7 @@ int wn_layers_backward_data(int nl, const WnPacked& pw, const char* S, const WnW
       f.dh_out = (bf16_t*)(wk.dh + wk.dh_one * i); f.dskip = dskip;
       f.ts = (const bf16_t*)(S + st.ts + st.ts_one * (i - 1)); f.dpre_out = (bf16_t*)(wk.dpre + wk.dpre_one * (i - 1));
       f.L = L; f.Lr = Lr; f.B = B; f.d = 1 << i;
-      if (int rc = wn_bwd_launch(f, s)) return rc;
+      if (int rc = wn_bwd_launch(f, plan, s)) return rc;
     }
     if (int rc = conv_bwd_launch(0)) return rc;
   } else {
@@ -2521,23 +2403,22 @@ int wn_layers_backward_data(int nl, const WnPacked& pw, const char* S, const WnW
 }
 
 // the conditioning gradient of all layers of one stack: dspect (+)= [Wcond_0^T | ... ] [dpre_0; ...]
-int wn_layers_backward_dspect(int nl, const WnPacked& pw, const WnWork& wk, float* dspect_pm_dev, int accumulate_dspect, int B, int L,
-                              hipStream_t s) {
+int wn_layers_backward_dspect(const WnStackPlan& plan, int nl, const WnPacked& pw, const WnWork& wk, float* dspect_pm_dev, int accumulate_dspect,
+                              int B, int L, hipStream_t s) {
   const int Lr = pad_len(L), Lp = HALO + Lr + HALO;
-  const char* e_ds = getenv("FACPPG_TRAIN_DSPECT_BGEMM");     // =1: the k_bgemm<EP_ACC_F32> launch (bit-equality test, A/B timing)
-  if (!(e_ds && e_ds[0] == '1')) {  // dspect over all layers at once
+  if (!plan.dspect_bgemm) {  // dspect over all layers at once
     DspectArgs c;
     memset(&c, 0, sizeof(c));
     c.A = pw.condt; c.dpre = (const bf16_t*)wk.dpre; c.dpre_one = (long)(wk.dpre_one / 2); c.dpre_bs = (long)Lp * 2 * C;
     c.out = dspect_pm_dev; c.nl = nl; c.L = L; c.Lr = Lr; c.B = B; c.accumulate = accumulate_dspect != 0;
-    if (int rc = dspect_launch(c, s)) return rc;
+    if (int rc = dspect_launch(c, plan, s)) return rc;
   } else {
     BGemmArgs c;
     memset(&c, 0, sizeof(c));
     c.A = pw.condt; c.KG = nl * 2 * C / 16; c.M = NCOND; c.N = L; c.B = B; c.nseg = nl;
     for (int i = 0; i < nl; ++i) c.seg[i] = Seg{(const bf16_t*)(wk.dpre + wk.dpre_one * i), (long)Lp * 2 * C, 2 * C, HALO, 2 * C};
     c.mode = EP_ACC_F32; c.Lr = Lr; c.outf = dspect_pm_dev; c.ldo = NCOND; c.accumulate = accumulate_dspect != 0;
-    if (int rc = bgemm_launch(c, s)) return rc;
+    if (int rc = bgemm_launch(c, plan.dspect_acc, s)) return rc;
   }
   return FACPPG_OK;
 }
@@ -2545,8 +2426,8 @@ int wn_layers_backward_dspect(int nl, const WnPacked& pw, const WnWork& wk, floa
 // Weight and bias gradients of the three convs of every layer: NT products over positions, batched over layers (x taps); bias
 // gradients as column sums.
 // (s: the NT products and their ordered reduce; s_bias: the column sums -- the same stream, or a parallel branch)
-int wn_layers_backward_weights(const facppg_wn_grads* gr, int nl, const char* S, const WnWork& wk, const void* spect_pm_dev, int B, int L,
-                               hipStream_t s, hipStream_t s_bias) {
+int wn_layers_backward_weights(const WnWgradPlans& plans, const facppg_wn_grads* gr, int nl, const char* S, const WnWork& wk,
+                               const void* spect_pm_dev, int B, int L, hipStream_t s, hipStream_t s_bias) {
   const int Lr = pad_len(L), Lp = HALO + Lr + HALO;
   const StateLayout st = state_layout(nl, B, Lr);
   bf16_t* dskip = wk.dskip;
@@ -2565,7 +2446,7 @@ int wn_layers_backward_weights(const facppg_wn_grads* gr, int nl, const char* S,
     ReduceSet* defer = wk.wgpart_regions >= 3 ? &rs : nullptr;
     float* region[3];
     for (int r = 0; r < 3; ++r) region[r] = defer ? (float*)((char*)wk.wgpart + wk.wgpart_bytes * r) : wk.wgpart;
-    if (int rc = wgrad_launch(wa, nl * 3, 2 * C, C, region[0], wk.wgpart_bytes, s, defer)) return rc;
+    if (int rc = wgrad_launch(wa, plans.taps, nl * 3, 2 * C, C, region[0], s, defer)) return rc;
     memset(&wa.prob, 0, sizeof(wa.prob));
     for (int i = 0; i < nl; ++i) {
       WgradProb& p = wa.prob[i];
@@ -2573,7 +2454,7 @@ int wn_layers_backward_weights(const facppg_wn_grads* gr, int nl, const char* S,
       p.x = (const bf16_t*)spect_pm_dev; p.x_bs = (long)Lr * NCOND; p.ldx = NCOND; p.x_row0 = 0;
       p.out = gr->cond_w[i]; p.o_sm = NCOND; p.o_sk = 1; p.M = 2 * C; p.K = NCOND;
     }
-    if (int rc = wgrad_launch(wa, nl, 2 * C, NCOND, region[1], wk.wgpart_bytes, s, defer)) return rc;
+    if (int rc = wgrad_launch(wa, plans.cond, nl, 2 * C, NCOND, region[1], s, defer)) return rc;
     memset(&wa.prob, 0, sizeof(wa.prob));
     for (int i = 0; i < nl; ++i) {
       const int last = i == nl - 1;
@@ -2584,7 +2465,7 @@ int wn_layers_backward_weights(const facppg_wn_grads* gr, int nl, const char* S,
       p.x = (const bf16_t*)(S + st.acts + st.acts_one * i); p.x_bs = (long)Lr * C; p.ldx = C; p.x_row0 = 0;
       p.out = gr->rs_w[i]; p.o_sm = C; p.o_sk = 1; p.K = C;
     }
-    if (int rc = wgrad_launch(wa, nl, 2 * C, C, region[2], wk.wgpart_bytes, s, defer)) return rc;
+    if (int rc = wgrad_launch(wa, plans.resskip, nl, 2 * C, C, region[2], s, defer)) return rc;
     if (defer)
       if (int rc = reduce_launch(rs, s)) return rc;
   }
@@ -2630,14 +2511,16 @@ extern "C" int facppg_wn_backward_bf16(const facppg_wn_weights* wts, const facpp
   const ScratchLayout sc = scratch_layout(nl, B, Lr);
   FACPPG_REQUIRE(state_bytes >= st.total, FACPPG_EWORKSPACE, "state has %zu bytes, need %zu", state_bytes, st.total);
   FACPPG_REQUIRE(scratch_bytes >= sc.total, FACPPG_EWORKSPACE, "scratch has %zu bytes, need %zu", scratch_bytes, sc.total);
+  const TrainTuning tuning = train_tuning_from_env();
+  const WnStackPlan plan = plan_wn_stack(tuning, nl, B, L);
+  const WnWgradPlans wgplans = plan_wn_wgrads(tuning, nl, B, L, sc.wgpart_bytes);
   hipStream_t s = (hipStream_t)stream_;
   const char* S = (const char*)state_dev;
   char* W = (char*)scratch_dev;
   const int nout = 2 * n_in;
-  uint4* condt = (uint4*)(W + sc.condt);
   {
     Packer pk;
-    add_backward_images(pk, wts, nl, W + sc.rst, sc.rst_one, W + sc.int_, sc.int_one, condt);
+    add_backward_images(pk, wts, nl, W, sc);
     if (int rc = pk.launch(s)) return rc;
   }
   bf16_t* dskip = (bf16_t*)(W + sc.dskip);
@@ -2655,14 +2538,10 @@ extern "C" int facppg_wn_backward_bf16(const facppg_wn_weights* wts, const facpp
     k_small_wgrad_sum<<<dim3(C / 16, 9), 256, 0, s>>>(part, SMALL_PARTS, nout, gr->end_w, C, 1, nullptr);
     k_small_rowsum<<<nout, 256, 0, s>>>(dout_dev, gr->end_b, nout, B, L);
   }
-  WnPacked pw;
-  memset(&pw, 0, sizeof(pw));
-  pw.rst = (const uint4*)(W + sc.rst); pw.rst_one = sc.rst_one; pw.int_ = (const uint4*)(W + sc.int_); pw.int_one = sc.int_one; pw.condt = condt;
-  WnWork wk;
-  wk.dpre = W + sc.dpre; wk.dpre_one = sc.dpre_one; wk.dh = W + sc.dh; wk.dh_one = sc.dh_one; wk.dskip = dskip;
-  wk.cspart = (float*)(W + sc.cspart); wk.wgpart = (float*)(W + sc.wgpart); wk.wgpart_bytes = sc.wgpart_bytes; wk.wgpart_regions = 1;
-  if (int rc = wn_layers_backward_data(nl, pw, S, wk, B, L, s)) return rc;
-  if (int rc = wn_layers_backward_dspect(nl, pw, wk, dspect_pm_dev, accumulate_dspect, B, L, s)) return rc;
+  const WnPacked pw = packed_view(W, sc, nullptr);
+  const WnWork wk = work_view(W, sc, 1);
+  if (int rc = wn_layers_backward_data(plan, nl, pw, S, wk, B, L, s)) return rc;
+  if (int rc = wn_layers_backward_dspect(plan, nl, pw, wk, dspect_pm_dev, accumulate_dspect, B, L, s)) return rc;
   const bf16_t* dh0 = (const bf16_t*)(W + sc.dh);
   k_t_start_bwd<<<dim3((L + 31) / 32, B), 256, 0, s>>>(dh0, wts->start_w, da0_dev, n_in, L, Lr);
   {  // start conv: weight [256][n_in] and bias [256] gradients
@@ -2670,7 +2549,7 @@ extern "C" int facppg_wn_backward_bf16(const facppg_wn_weights* wts, const facpp
     k_small_wgrad_part<true><<<SMALL_PARTS, 256, 0, s>>>(a0_dev, dh0, (long)Lr * C, 0, part, n_in, B, L, SMALL_PARTS);
     k_small_wgrad_sum<<<dim3(C / 16, 9), 256, 0, s>>>(part, SMALL_PARTS, n_in, gr->start_w, 1, n_in, gr->start_b);
   }
-  return wn_layers_backward_weights(gr, nl, S, wk, spect_pm_dev, B, L, s, s);
+  return wn_layers_backward_weights(wgplans, gr, nl, S, wk, spect_pm_dev, B, L, s, s);
 }
 
 // ================================================================================================================
@@ -3083,56 +2962,6 @@ __global__ __launch_bounds__(64) void k_logdet_batch(LogdetBatch lb) {
   if (threadIdx.x == 0) lb.out[blockIdx.x][0] *= lb.scale[blockIdx.x];
 }
 
-// what one flow's stack keeps packed for a whole step: both directions' bf16 operand images and the summed gate biases
-struct PackedLayout { size_t w1, w2, rst, int_, condt, b1, total; size_t w1_one, w2_one, rst_one, int_one; };
-PackedLayout packed_layout(int nl) {
-  PackedLayout s;
-  size_t off = 0;
-  auto take = [&](size_t bytes) { size_t o = off; off += (bytes + 255) / 256 * 256; return o; };
-  s.w1_one = (size_t)16 * (K1 / 16) * 64 * 16; s.w2_one = (size_t)16 * (C / 16) * 64 * 16;
-  s.rst_one = (size_t)8 * (2 * C / 16) * 64 * 16; s.int_one = (size_t)8 * (3 * 2 * C / 16) * 64 * 16;
-  s.w1 = take(s.w1_one * nl); s.w2 = take(s.w2_one * nl); s.rst = take(s.rst_one * nl); s.int_ = take(s.int_one * nl);
-  s.condt = take((size_t)(NCOND / 32) * (nl * 2 * C / 16) * 64 * 16);
-  s.b1 = take((size_t)nl * 2 * C * 4);
-  s.total = off;
-  return s;
-}
-// gradients in flight of ONE flow's backward (the flows of a step take turns on it) + the reductions' partial buffers
-struct WorkLayout { size_t dpre, dh, dskip, cspart, wgpart, wgpart_bytes, total; size_t dpre_one, dh_one; };
-WorkLayout work_layout(int nl, int B, int Lr) {
-  WorkLayout s;
-  const int Lp = HALO + Lr + HALO;
-  size_t off = 0;
-  auto take = [&](size_t bytes) { size_t o = off; off += (bytes + 255) / 256 * 256; return o; };
-  s.dpre_one = (size_t)B * Lp * 2 * C * 2; s.dh_one = (size_t)B * Lr * C * 2;
-  s.dpre = take(s.dpre_one * nl); s.dh = take(s.dh_one * (nl + 1)); s.dskip = take(s.dh_one);
-  s.cspart = take((size_t)MAXCS * CS_SLICES * 1024 * 4);
-  s.wgpart_bytes = (size_t)3 * nl * 5 * (2 * C) * C * 4;      // per weight-gradient launch of a flow (three regions: one ordered reduce)
-  s.wgpart = take(s.wgpart_bytes * 3);
-  s.total = off;
-  return s;
-}
-// When the bf16 operand images of a flow's stack are formed.  Measured (round 6): all flows at the start of the step (one launch per
-// flow, 12 instead of 24) leaves every layer launch fetching its 2 - 3 MB of weights from HBM milliseconds after they were written
-// (k_wn_fwd 38.6 -> 42.7 us, k_wn_bwd 30.1 -> 32.4 at batch 12; 18.1 -> 22.6 at batch 3: +0.5 ms per step); packed right in front of
-// the flow's stack, per direction, they are still in the L2s / the Infinity Cache when the layers read them.  FACPPG_TRAIN_PACK=step: the former.
-bool pack_per_step() {
-  const char* e = getenv("FACPPG_TRAIN_PACK");
-  return e && !strcmp(e, "step");
-}
-int edge_chunks(int B, int L) {   // chunks of 32 positions a backward edge workgroup walks: at most ~512 workgroups (two per CU)
-  const int nblk = (L + 31) / 32;
-  const char* e = getenv("FACPPG_EDGE_WGS");
-  const int target = e && atoi(e) > 0 ? atoi(e) : 512;
-  return std::max(1, (B * nblk + target - 1) / target);
-}
-WnPacked packed_view(const char* P, const PackedLayout& pl) {
-  WnPacked pw;
-  pw.w1 = (const uint4*)(P + pl.w1); pw.w1_one = pl.w1_one; pw.w2 = (const uint4*)(P + pl.w2); pw.w2_one = pl.w2_one;
-  pw.rst = (const uint4*)(P + pl.rst); pw.rst_one = pl.rst_one; pw.int_ = (const uint4*)(P + pl.int_); pw.int_one = pl.int_one;
-  pw.condt = (const uint4*)(P + pl.condt); pw.b1 = (const float*)(P + pl.b1);
-  return pw;
-}
 int check_glow_flows(const facppg_glow_flow* f, int n, int nl, int B, int L, bool backward) {
   FACPPG_REQUIRE(f && n >= 1 && n <= MAXGF, FACPPG_EINVAL, "1..%d flows per group call (got %d)", MAXGF, n);
   for (int k = 0; k < n; ++k) {
@@ -3170,8 +2999,7 @@ extern "C" int facppg_glow_bf16_layout(int n_layers, int B, int L, facppg_glow_b
   out->packed_bytes_per_flow = packed_layout(n_layers).total;
   out->state_bytes_per_flow = (state_layout(n_layers, B, Lr).total + 255) / 256 * 256;
   out->work_bytes = work_layout(n_layers, B, Lr).total;
-  const int nchunk = edge_chunks(B, L);
-  out->n_parts = B * (((L + 31) / 32 + nchunk - 1) / nchunk);
+  out->n_parts = plan_edges(train_tuning_from_env(), B, L).n_parts;
   out->part_floats = EPART;
   return FACPPG_OK;
 }
@@ -3190,12 +3018,12 @@ extern "C" int facppg_glow_bf16_begin(const facppg_wn_weights* wts, int n_flows,
   const StateLayout st = state_layout(nl, B, Lr);
   const size_t st_stride = (st.total + 255) / 256 * 256;
   const WorkLayout wl = work_layout(nl, B, Lr);
-  if (pack_per_step())
+  if (train_tuning_from_env().pack_per_step)
     for (int k = 0; k < n_flows; ++k) {
       char* P = (char*)packed_dev + pl.total * k;
       Packer pk;
-      add_forward_images(pk, &wts[k], nl, P + pl.w1, pl.w1_one, P + pl.w2, pl.w2_one);
-      add_backward_images(pk, &wts[k], nl, P + pl.rst, pl.rst_one, P + pl.int_, pl.int_one, (uint4*)(P + pl.condt));
+      add_forward_images(pk, &wts[k], nl, P, pl);
+      add_backward_images(pk, &wts[k], nl, P, pl);
       if (int rc = pk.launch(s)) return rc;
     }
   for (int k0 = 0; k0 < n_flows; k0 += ADD_FLOWS) {
@@ -3234,6 +3062,8 @@ extern "C" int facppg_glow_bf16_group_forward(const facppg_glow_flow* flows, int
   hipStream_t s = (hipStream_t)stream_;
   const int Lr = pad_len(L), Lp = HALO + Lr + HALO;
   const PackedLayout pl = packed_layout(nl);
+  const TrainTuning tuning = train_tuning_from_env();
+  const WnStackPlan plan = plan_wn_stack(tuning, nl, B, L);
   {
     LogdetBatch lb;
     for (int k = 0; k < n; ++k) { lb.w[k] = flows[k].conv_w; lb.out[k] = flows[k].logdet; lb.c[k] = flows[k].c; lb.scale[k] = flows[k].ld_scale; }
@@ -3248,13 +3078,13 @@ extern "C" int facppg_glow_bf16_group_forward(const facppg_glow_flow* flows, int
     a.audio_in = audio_in_dev; a.audio_out = audio_out_dev; a.in_bs = in_bs; a.out_bs = out_bs;
     k_edge_fwd<<<dim3((L + 31) / 32, B), 256, 0, s>>>(a);
     if (k < n) {
-      if (!pack_per_step()) {
-        char* P = (char*)flows[k].packed;
+      char* P = (char*)flows[k].packed;
+      if (!tuning.pack_per_step) {
         Packer pk;
-        add_forward_images(pk, flows[k].w, nl, P + pl.w1, pl.w1_one, P + pl.w2, pl.w2_one);
+        add_forward_images(pk, flows[k].w, nl, P, pl);
         if (int rc = pk.launch(s)) return rc;
       }
-      if (int rc = wn_layers_forward(flows[k].w, nl, packed_view((const char*)flows[k].packed, pl), spect_pm_dev, B, L, (char*)flows[k].state, s))
+      if (int rc = wn_layers_forward(plan, flows[k].w, nl, packed_view(P, pl, (const float*)(P + pl.b1)), spect_pm_dev, B, L, (char*)flows[k].state, s))
         return rc;
     }
   }
@@ -3274,40 +3104,41 @@ extern "C" int facppg_glow_bf16_group_backward(const facppg_glow_flow* flows, in
   const int Lr = pad_len(L);
   const PackedLayout pl = packed_layout(nl);
   const WorkLayout wl = work_layout(nl, B, Lr);
+  const TrainTuning tuning = train_tuning_from_env();
+  const WnStackPlan plan = plan_wn_stack(tuning, nl, B, L);
+  const WnWgradPlans wgplans = plan_wn_wgrads(tuning, nl, B, L, wl.wgpart_bytes);
+  const EdgePlan edges = plan_edges(tuning, B, L);
   char* W = (char*)work_dev;
-  WnWork wk;
-  wk.dpre = W + wl.dpre; wk.dpre_one = wl.dpre_one; wk.dh = W + wl.dh; wk.dh_one = wl.dh_one; wk.dskip = (bf16_t*)(W + wl.dskip);
-  wk.cspart = (float*)(W + wl.cspart); wk.wgpart = (float*)(W + wl.wgpart); wk.wgpart_bytes = wl.wgpart_bytes; wk.wgpart_regions = 3;
-  const int nchunk = edge_chunks(B, L), gx = ((L + 31) / 32 + nchunk - 1) / nchunk;
+  const WnWork wk = work_view(W, wl, 3);
   for (int k = n; k >= 0; --k) {
     EdgeBwdArgs a;
     memset(&a, 0, sizeof(a));
-    a.has_hi = k < n; a.has_lo = k > 0; a.L = L; a.Lr = Lr; a.nchunk = nchunk;
+    a.has_hi = k < n; a.has_lo = k > 0; a.L = L; a.Lr = Lr; a.nchunk = edges.nchunk;
     if (a.has_hi) a.hi = edge_flow(flows[k], nl, B, Lr);
     if (a.has_lo) a.lo = edge_flow(flows[k - 1], nl, B, Lr);
     a.dh0 = (const bf16_t*)(W + wl.dh); a.dskip = wk.dskip; a.d_out = d_audio_out_dev; a.d_in = d_audio_in_dev; a.d_out_bs = d_out_bs; a.d_in_bs = d_in_bs;
-    k_edge_bwd<<<dim3(gx, B), 256, 0, s>>>(a);
+    k_edge_bwd<<<dim3(edges.gx, B), 256, 0, s>>>(a);
     if (k > 0) {
       const facppg_glow_flow& f = flows[k - 1];
-      if (!pack_per_step()) {
-        char* P = (char*)f.packed;
+      char* P = (char*)f.packed;
+      if (!tuning.pack_per_step) {
         Packer pk;
-        add_backward_images(pk, f.w, nl, P + pl.rst, pl.rst_one, P + pl.int_, pl.int_one, (uint4*)(P + pl.condt));
+        add_backward_images(pk, f.w, nl, P, pl);
         if (int rc = pk.launch(s)) return rc;
       }
-      const WnPacked pw = packed_view((const char*)f.packed, pl);
-      if (int rc = wn_layers_backward_data(nl, pw, (const char*)f.state, wk, B, L, s)) return rc;
+      const WnPacked pw = packed_view(P, pl, (const float*)(P + pl.b1));
+      if (int rc = wn_layers_backward_data(plan, nl, pw, (const char*)f.state, wk, B, L, s)) return rc;
       // (Round 6 experiment: the conditioning gradient, the weight-gradient products and the bias column sums as three parallel
       // branches -- side streams forked / joined by events, parallel branches of the captured graph -- measured SLOWER: 8.63 -> 9.50 ms
       // at batch 3, 15.0 -> 15.6 at batch 12; a fork + two joins per flow cost more cross-queue latency than the overlap returns.)
-      if (int rc = wn_layers_backward_dspect(nl, pw, wk, dspect_pm_dev, accumulate_dspect || k < n, B, L, s)) return rc;
-      if (int rc = wn_layers_backward_weights(f.g, nl, (const char*)f.state, wk, spect_pm_dev, B, L, s, s)) return rc;
+      if (int rc = wn_layers_backward_dspect(plan, nl, pw, wk, dspect_pm_dev, accumulate_dspect || k < n, B, L, s)) return rc;
+      if (int rc = wn_layers_backward_weights(wgplans, f.g, nl, (const char*)f.state, wk, spect_pm_dev, B, L, s, s)) return rc;
     }
   }
   {
     EdgeSumArgs sa;
     memset(&sa, 0, sizeof(sa));
-    sa.nparts = B * gx;
+    sa.nparts = edges.n_parts;
     for (int k = 0; k < n; ++k) {
       const facppg_glow_flow& f = flows[k];
       sa.f[k] = EdgeSumFlow{f.part, f.g->end_w, f.g->end_b, f.g->start_w, f.g->start_b, f.d_conv_w, f.logdet + 1, f.g_logdet, f.ld_scale, f.c};

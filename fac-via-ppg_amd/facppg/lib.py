@@ -52,6 +52,16 @@ class TacoLaunchReport(ctypes.Structure):
                                        "bilstm_kind", "bilstm_legacy")]
 
 
+class TrainLaunchReport(ctypes.Structure):
+    """facppg_train_launch_report (include/facppg.h): what facppg_train_bf16_launch_plan says the bf16 training calls would launch."""
+    _fields_ = [(n, ctypes.c_int32) for n in ("tile_positions", "fused_fwd", "fused_bwd", "fused_workgroups")] + \
+        [("gemm_cols", ctypes.c_int32 * 5), ("gemm_workgroups", ctypes.c_int32 * 5)] + \
+        [(n, ctypes.c_int32) for n in ("dspect_bgemm", "dspect_cols", "dspect_workgroups", "dspect_lds_bytes")] + \
+        [(n, ctypes.c_int32 * 3) for n in ("wgrad_tile", "wgrad_splits", "wgrad_workgroups", "wgrad_xcd_map")] + \
+        [(n, ctypes.c_int32) for n in ("pack_per_step", "edge_nchunk", "edge_n_parts", "upsample_gemm", "fwd_lds_bytes", "bwd_lds_bytes",
+                                       "wgrad_lds_bytes", "wgrad2_lds_bytes")]
+
+
 class TacoAttentionBackwardArgs(ctypes.Structure):
     """facppg_taco_attention_backward_args (include/facppg.h): twelve inputs, four outputs, all device pointers."""
     _fields_ = [(n, ctypes.c_void_p) for n in (
@@ -143,6 +153,7 @@ def _declare(lib):
         "facppg_wn_bf16_state_bytes": (sz, [c.c_int, c.c_int, c.c_int]),
         "facppg_wn_bf16_scratch_bytes": (sz, [c.c_int, c.c_int, c.c_int]),
         "facppg_wn_bf16_launch_plan": (c.c_int, [c.c_int, c.c_int, c.c_int]),
+        "facppg_train_bf16_launch_plan": (c.c_int, [c.c_int, c.c_int, c.c_int, c.POINTER(TrainLaunchReport)]),
         "facppg_spect_to_bf16": (c.c_int, [vp, c.c_int, c.c_int, c.c_int, c.c_int, vp, vp]),
         "facppg_posmajor_to_f32": (c.c_int, [vp, c.c_int, c.c_int, c.c_int, vp, c.c_int, vp]),
         "facppg_wn_forward_bf16": (c.c_int, [c.POINTER(WnWeights), c.c_int, c.c_int, vp, vp, c.c_int, c.c_int, vp, vp, sz, vp, sz, vp]),

@@ -290,6 +290,37 @@ size_t facppg_wn_bf16_scratch_bytes(int n_layers, int B, int L);  /* per-call sc
  * bit 2: 256 x 256 weight-gradient tiles (k_wgrad2) for the tap and conditioning products; bits 8..15: positions per tile of the fused
  * launches (64 or 32).  Negative: bad argument. */
 int facppg_wn_bf16_launch_plan(int n_layers, int B, int L);
+/* The same decision in full, for the stand-alone calls above and the group calls (facppg_glow_bf16_*) alike: the host-side plan
+ * alone, from the very functions the calls plan with (csrc/facppg_train_plan.h) -- no handle, no device.  The environment switches
+ *  count as in the calls, which read them once per call.  FACPPG_EINVAL where facppg_wn_bf16_launch_plan is
+ * negative, or out is NULL. */
+typedef struct facppg_train_launch_report {
+  int32_t tile_positions;       /* positions per tile of the fused layer launches: 64 or 32 */
+  int32_t fused_fwd;            /* one launch per layer forward (k_wn_fwd) instead of two k_bgemm */
+  int32_t fused_bwd;            /* one launch per layer in the backward chain (k_wn_bwd); never for a one-layer stack */
+  int32_t fused_workgroups;     /* of a fused launch */
+  /* the k_bgemm launches of the two-launch layers: gate, res/skip, res/skip of the last layer, gate backward, transposed conv */
+  int32_t gemm_cols[5];         /* columns per tile: 128 or 64 */
+  int32_t gemm_workgroups[5];
+  int32_t dspect_bgemm;         /* conditioning gradient: 0 k_dspect, 1 k_bgemm (FACPPG_TRAIN_DSPECT_BGEMM=1) */
+  int32_t dspect_cols;          /* k_bgemm: columns per tile; k_dspect: 0 */
+  int32_t dspect_workgroups;
+  int32_t dspect_lds_bytes;     /* dynamic LDS (k_bgemm: 0) */
+  /* the weight-gradient products of one stack: taps (3 n_layers problems), conditioning, res/skip (n_layers each) */
+  int32_t wgrad_tile[3];        /* 256 (k_wgrad2) or 128 (k_wgrad) */
+  int32_t wgrad_splits[3];      /* position splits per output tile; > 1: partial sums and an ordered reduce */
+  int32_t wgrad_workgroups[3];
+  int32_t wgrad_xcd_map[3];     /* workgroups dealt to the XCDs by (problem, split); 0: FACPPG_WGRAD_NO_XCD_MAP=1 on 128-tiles */
+  int32_t pack_per_step;        /* FACPPG_TRAIN_PACK=step */
+  int32_t edge_nchunk;          /* 32-position chunks a backward edge workgroup walks */
+  int32_t edge_n_parts;         /* facppg_glow_bf16_sizes.n_parts */
+  int32_t upsample_gemm;        /* the upsampler as MFMA products where a workspace is passed (FACPPG_UPSAMPLE_GEMM=0: never) */
+  int32_t fwd_lds_bytes;        /* dynamic LDS of k_wn_fwd / k_wn_bwd at tile_positions, of k_wgrad and of k_wgrad2 */
+  int32_t bwd_lds_bytes;
+  int32_t wgrad_lds_bytes;
+  int32_t wgrad2_lds_bytes;
+} facppg_train_launch_report;
+int facppg_train_bf16_launch_plan(int n_layers, int B, int L, facppg_train_launch_report* out);
 /* fp32 channel-major [B][channels][ld] (first L columns) -> bf16 position-major [B][Lr][channels], rows >= L zero */
 int facppg_spect_to_bf16(const float* spect_dev, int B, int channels, int L, int ld, void* out_dev, void* stream);
 /* fp32 position-major [B][Lr][channels] -> fp32 channel-major [B][channels][ld] (first L columns) */
