@@ -261,7 +261,7 @@ class ConditioningStream(object):
         #  encoder: asked once per (step limit, layout), not per utterance)
         lk = (dev, steps, cap, self.half, self.split)
         if self.layout_key != lk:
-            lay = self.waveglow.seed_layout(cap, dev, arithmetic=self.SPLIT) if self.split else self.waveglow.seed_layout(cap, dev) + (4,)
+            lay = self.waveglow.seed_layout(cap, dev, block_tiles=True, **self._kind())
             self.layout = lay + (L.facppg_taco_postnet_stream_workspace_bytes(self.tacotron._handle(dev), cap),)
             self.layout_key = lk
         self.tqp, self.margin, seed_bytes, self.max_block_tiles, post_ws_bytes = self.layout
@@ -360,7 +360,7 @@ class ConditioningStream(object):
         the side stream."""
         dev = self.dev
         self.cuts = self.plan(self.steps, self.Tin)
-        self.wg_handle = self.waveglow._split_handle(dev) if self.split else self.waveglow._handle(dev)
+        self.wg_handle = self.waveglow.handle(dev, **self._kind())
         f_prev = 0
         lpw = max(1, int(os.environ.get("FACPPG_STREAM_LPW", "1")))
         # The seed passes take the CUs the decoder leaves except `spare` of them, ONE workgroup per CU that holds the CU's whole LDS
@@ -594,7 +594,8 @@ def _acoustic(ppgs, tacotron, seed, dropout_masks, utterance_seeds, step_limits,
 def _checked_arithmetic(arithmetic):
     """The ``vocoder_arithmetic`` of a call -> what WaveGlow.infer takes as ``arithmetic`` (None: the module's own path);
     an unknown value is refused here, before any model runs."""
-    if arithmetic not in (None, "fp32", "bf16x3"):
+    from waveglow.glow import WaveGlow
+    if arithmetic not in WaveGlow.ARITHMETICS:
         from facppg.lib import FacppgError
         raise FacppgError("vocoder_arithmetic=%r: expected None, 'fp32' or 'bf16x3'" % (arithmetic,))
     return None if arithmetic == "fp32" else arithmetic
@@ -629,8 +630,7 @@ def _vocode(mel_post, tout, waveglow, denoiser, sigma, strength, seed, z, uttera
     elif split_first:
         if wg_seeds is not None:
             z = waveglow.draw_noise(wg_seeds, tout[0], mel_post.device)
-        waveglow._require_split_module("infer_seeded")
-        h = waveglow._checked_split_handle(mel_post.device)
+        h = waveglow.handle(mel_post.device, arithmetic)
         melp = waveglow.mel_pad(mel_post[:, :, :tout[0]], handle=h, arithmetic=arithmetic)
         audio = waveglow.infer_seeded(melp, tout[0], None, 0, sigma=sigma, z=z, seed=seed, handle=h, arithmetic=arithmetic)
     else:

@@ -16,6 +16,7 @@ Extensions over the reference signature (all optional, defaults = reference beha
     utterance_seeds  B integers: the noise of utterance b depends on utterance_seeds[b] alone
              (facppg_wg_draw_noise), so the batch reproduces B batch-1 calls with the same seeds
 """
+import collections
 import os
 
 import torch
@@ -850,6 +851,41 @@ def _infer_side_stream(device):
     return _INFER_SIDE_STREAMS[key]
 
 
+class _Kind(collections.namedtuple("_Kind", (
+        "name slot ws_slot dtype mel_dtype mel_rows takes_order max_block_tiles "
+        "create destroy workspace_bytes infer seed_layout mel_pad cond_seed infer_seeded last_launch_shape"))):
+    """One vocoder kind of WaveGlow's inference, everything the host side needs to know to tell it from the others:
+      slot             the __dict__ key its handle tuple lives under (fp32 and fp16 share one: a module is one or the other);
+      ws_slot          the key of its grow-only workspace in _facppg_ws;
+      dtype            of its audio and of z;
+      mel_dtype, mel_rows  its seeded mel buffer: position-major [Tqp, n_mel] (frame q at ROW margin + q), or -- the fp32 kind alone --
+                       channel-major [n_mel, Tqp], which its mel_pad entry fills whole (the others convert frame ranges);
+      takes_order      its infer entry takes the K order of the gate GEMMs (cond_first);
+      max_block_tiles  the widest cond_seed block; None: its seed-layout query reports it (one more out-argument);
+      the rest         the names of its C entry points (include/facppg.h), looked up by fn()."""
+    __slots__ = ()
+
+    def fn(self, entry):
+        return getattr(_lib.load(), getattr(self, entry))
+
+
+# fp32 and fp16 by the precision of the module (WaveGlow._precision), the split-bf16 kind by the ``arithmetic`` that asks for it
+_KINDS = {
+    torch.float32: _Kind("fp32", "_facppg_handle", 0, torch.float32, torch.float32, False, False, 4,
+                         "facppg_wg_create", "facppg_wg_destroy", "facppg_wg_workspace_bytes", "facppg_wg_infer", "facppg_wg_seed_layout",
+                         "facppg_wg_mel_pad", "facppg_wg_cond_seed", "facppg_wg_infer_seeded", "facppg_wg_last_launch_shape"),
+    torch.float16: _Kind("fp16", "_facppg_handle", 0, torch.float16, torch.float16, True, True, 4,
+                         "facppg_wg_create_f16", "facppg_wg_destroy", "facppg_wg_workspace_bytes", "facppg_wg_infer_f16_order",
+                         "facppg_wg_seed_layout_f16", "facppg_wg_mel_pad_f16", "facppg_wg_cond_seed_f16", "facppg_wg_infer_seeded_f16",
+                         "facppg_wg_last_launch_shape"),
+    "bf16x3": _Kind("bf16x3", "_facppg_split_handle", "bf16x3", torch.float32, torch.float32, True, False, None,
+                    "facppg_wg_split_create", "facppg_wg_split_destroy", "facppg_wg_split_workspace_bytes", "facppg_wg_split_infer",
+                    "facppg_wg_split_seed_layout", "facppg_wg_split_mel_pad", "facppg_wg_split_cond_seed", "facppg_wg_split_infer_seeded",
+                    "facppg_wg_split_last_launch_shape"),
+}
+_SPLIT = _KINDS["bf16x3"]
+
+
 class WaveGlow(torch.nn.Module):
     """glow.py:178-303."""
 
@@ -920,26 +956,23 @@ class WaveGlow(torch.nn.Module):
         being rebuilt -- first use, another device -- while the split one is still valid)."""
         self.__dict__.pop("_facppg_prepared", None)
         self.__dict__.pop("_facppg_cond_stream", None)    # its buffers belong to the handle's weights and device
-        h = self.__dict__.pop("_facppg_handle", None)
-        if h is not None:
-            _lib.load().facppg_wg_destroy(h[0])
-        hs = None if keep_split else self.__dict__.pop("_facppg_split_handle", None)
-        if hs is not None:
-            _lib.load().facppg_wg_split_destroy(hs[0])
+        for kind in (_KINDS[torch.float32],) if keep_split else (_KINDS[torch.float32], _SPLIT):
+            h = self.__dict__.pop(kind.slot, None)
+            if h is not None:
+                kind.fn("destroy")(h[0])
         self.__dict__.pop("_facppg_ws", None)
 
     def last_launch_shape(self, arithmetic=None):
         """(frames per tile, waves per workgroup, workgroups per launch) of the WN-layer kernels of the most recent
         infer() -- which instantiation of the fused layer kernel ran (facppg_wg_last_launch_shape); arithmetic="bf16x3": of the
         most recent infer(arithmetic="bf16x3") or infer_seeded(arithmetic="bf16x3") (facppg_wg_split_last_launch_shape)."""
-        split = self._check_arithmetic(arithmetic)
-        h = self.__dict__.get("_facppg_split_handle" if split else "_facppg_handle")
+        kind = _SPLIT if self._check_arithmetic(arithmetic) else _KINDS[torch.float32]    # (fp16: the fp32 kind's slot and query)
+        h = self.__dict__.get(kind.slot)
         if h is None:
             raise _lib.FacppgError("last_launch_shape: no inference has run on this model yet")
         c = _lib.ctypes
         tile, waves, tiles = c.c_int(0), c.c_int(0), c.c_int(0)
-        query = _lib.load().facppg_wg_split_last_launch_shape if split else _lib.load().facppg_wg_last_launch_shape
-        _lib.check(query(h[0], c.byref(tile), c.byref(waves), c.byref(tiles)))
+        _lib.check(kind.fn("last_launch_shape")(h[0], c.byref(tile), c.byref(waves), c.byref(tiles)))
         return tile.value, waves.value, tiles.value
 
     def last_layer_schedule(self):
@@ -960,28 +993,45 @@ class WaveGlow(torch.nn.Module):
         self._release()
         return super(WaveGlow, self).train(mode)
 
-    def _handle(self, device):
-        h = self.__dict__.get("_facppg_handle")
-        if h is not None and h[1] == device and h[2].unchanged():
-            return h[0]
-        hs = self.__dict__.get("_facppg_split_handle")
-        self._release(keep_split=hs is not None and hs[2].unchanged())
+    def _build(self, device, kind):
+        """Pack the live weights into a new handle of ``kind`` for ``device`` and store its tuple: (handle, device, WeightIdentity),
+        and in the slot the fp32 and fp16 kinds share the precision it was built for."""
         L = _lib.load()
         cfg = self._config()
-        prec = self._precision()
-        create = L.facppg_wg_create_f16 if prec == torch.float16 else L.facppg_wg_create
         blob = self._flat_weights().to(device).contiguous()
         if blob.numel() != L.facppg_wg_weight_count(cfg):
             raise _lib.FacppgError("weight blob has %d values, library expects %d (unsupported config: %s)" % (
                 blob.numel(), L.facppg_wg_weight_count(cfg), L.facppg_last_error().decode()))
         out = _lib.ctypes.c_void_p()
         with torch.cuda.device(device):
-            _lib.check(create(cfg, _lib.ptr(blob), blob.numel(), device.index,
-                              _lib.current_stream(device), _lib.ctypes.byref(out)))
-        self.__dict__["_facppg_handle"] = (out, device, _lib.WeightIdentity(self), prec)
+            _lib.check(kind.fn("create")(cfg, _lib.ptr(blob), blob.numel(), device.index,
+                                         _lib.current_stream(device), _lib.ctypes.byref(out)))
+        self.__dict__[kind.slot] = (out, device, _lib.WeightIdentity(self)) + (() if kind is _SPLIT else (kind.dtype,))
         return out
 
+    def _handle(self, device):
+        """The module's own handle (fp32 or fp16 images, by _precision()) for ``device``: the stored one while WeightIdentity finds
+        the weights unchanged -- ONE walk --, else built now; a split handle that is still valid survives the rebuild."""
+        h = self.__dict__.get("_facppg_handle")
+        if h is not None and h[1] == device and h[2].unchanged():
+            return h[0]
+        hs = self.__dict__.get(_SPLIT.slot)
+        self._release(keep_split=hs is not None and hs[2].unchanged())
+        return self._build(device, _KINDS[self._precision()])
+
+    def _split_handle(self, device):
+        """The split-bf16 handle for ``device``: lives beside the fp32 one, validated by WeightIdentity in the same way and dropped
+        by everything that drops it (_release)."""
+        h = self.__dict__.get(_SPLIT.slot)
+        if h is not None and h[1] == device and h[2].unchanged():
+            return h[0]
+        if h is not None:              # its weights changed (or it is another device's): the fp32 handle's did too
+            self._release()
+        return self._build(device, _SPLIT)
+
     ARITHMETICS = (None, "fp32", "bf16x3")
+    _SPLIT_NEEDS = ("WaveGlow.%s: arithmetic='bf16x3' splits fp32 operands: an all-fp32 module and an fp32 mel "
+                    "(a .half() module runs the fp16 kernels)")
 
     @classmethod
     def _check_arithmetic(cls, arithmetic):
@@ -990,63 +1040,54 @@ class WaveGlow(torch.nn.Module):
             raise _lib.FacppgError("WaveGlow: arithmetic=%r: expected None, 'fp32' or 'bf16x3'" % (arithmetic,))
         return arithmetic == "bf16x3"
 
-    def _split_handle(self, device):
-        """The split-bf16 handle (facppg_wg_split_create) for ``device``: lives beside the fp32 one, validated by WeightIdentity
-        in the same way and dropped by everything that drops it (_release)."""
-        h = self.__dict__.get("_facppg_split_handle")
-        if h is not None and h[1] == device and h[2].unchanged():
-            return h[0]
-        if h is not None:              # its weights changed (or it is another device's): the fp32 handle's did too
-            self._release()
-        L = _lib.load()
-        cfg = self._config()
-        blob = self._flat_weights().to(device).contiguous()
-        if blob.numel() != L.facppg_wg_weight_count(cfg):
-            raise _lib.FacppgError("weight blob has %d values, library expects %d (unsupported config: %s)" % (
-                blob.numel(), L.facppg_wg_weight_count(cfg), L.facppg_last_error().decode()))
-        out = _lib.ctypes.c_void_p()
-        with torch.cuda.device(device):
-            _lib.check(L.facppg_wg_split_create(cfg, _lib.ptr(blob), blob.numel(), device.index,
-                                                _lib.current_stream(device), _lib.ctypes.byref(out)))
-        self.__dict__["_facppg_split_handle"] = (out, device, _lib.WeightIdentity(self))
-        return out
+    def _kind(self, who, arithmetic, handle=None):
+        """(kind, split) of a call: "bf16x3" = the split kind -- of an all-fp32 module, anything else is refused (a ``handle`` passed
+        in was built from one) --, None / "fp32" = the module's own: the precision its handle was built for, or, before there is a
+        handle, _precision() (which refuses a module that is neither all fp32 nor all fp16).  No device is touched and no handle
+        validated; the parameters are walked only where there is no handle to ask."""
+        if self._check_arithmetic(arithmetic):
+            if handle is None and self._precision() != torch.float32:
+                raise _lib.FacppgError(self._SPLIT_NEEDS % who)
+            return _SPLIT, True
+        cur = self.__dict__.get("_facppg_handle")     # (a handle built for another precision than the upsampler's now is stale)
+        return _KINDS[cur[3] if cur is not None and cur[3] == self.upsample.weight.dtype else self._precision()], False
 
-    def _checked_split_handle(self, dev):
-        """The split handle for ``dev``: the one prepare(dev, "bf16x3") just validated (the token is consumed), or validated now."""
+    def _valid_handle(self, dev, kind):
+        return self._split_handle(dev) if kind is _SPLIT else self._handle(dev)
+
+    def _resolve(self, who, dev, handle, kind):
+        """The handle of ``kind`` a method runs on: ``handle`` -- the module's current one of that kind, anything else is refused --
+        or, with None, the module's handle for ``dev``, validated or built now."""
+        if handle is None:
+            return self._valid_handle(dev, kind)
+        cur = self.__dict__.get(kind.slot)
+        if cur is None or cur[0] is not handle:
+            raise _lib.FacppgError("WaveGlow.%s: the handle passed in is not this module's current %sone (its weights changed since)"
+                                   % (who, "split-bf16 " if kind is _SPLIT else ""))
+        return handle
+
+    def _checked_handle(self, dev, kind):
+        """The handle of ``kind`` for ``dev``: the one prepare() just validated (the token is consumed), or validated now."""
         pre = self.__dict__.pop("_facppg_prepared", None)
-        cur = self.__dict__.get("_facppg_split_handle")
-        return pre[0] if (pre is not None and pre[1] == dev and cur is not None and cur[0] is pre[0]) else self._split_handle(dev)
+        cur = self.__dict__.get(kind.slot)
+        if pre is not None and pre[1] == dev and cur is not None and cur[0] is pre[0]:
+            return pre[0]
+        return self._valid_handle(dev, kind)
 
-    def _infer_split(self, spect, sigma, z, lengths, seed, utterance_seeds):
-        """infer(arithmetic="bf16x3"): one launch sequence of facppg_wg_split_infer, the arguments normalised by _infer_args."""
-        dev = spect.device
-        h = self._checked_split_handle(dev)
-        spect = spect.contiguous()
-        B, _, T = spect.shape
-        hop = self.upsample.stride[0]
-        zt, lengths, seed, utterance_seeds = self._infer_args(B, T, torch.float32, z, lengths, seed, utterance_seeds, dev)
-        if utterance_seeds is not None:
-            zt = self.draw_noise(utterance_seeds, T, dev)
-        lt = _lib.upload(lengths, torch.int32, dev) if isinstance(lengths, list) else lengths
-        audio = (torch.empty if lt is None else torch.zeros)(B, T * hop, dtype=torch.float32, device=dev)
-        L = _lib.load()
-        nbytes = L.facppg_wg_split_workspace_bytes(h, B, T)
+    def handle(self, device, arithmetic=None):
+        """The packed-weight handle of the call's kind for ``device``, to pass to the seeded methods as ``handle=`` (they then
+        validate nothing): the one prepare() just validated -- the token is consumed -- or validated (ONE walk) or built now."""
+        return self._checked_handle(device, self._kind("handle", arithmetic)[0])
+
+    def _workspace(self, h, kind, B, T, dev, slot=None):
+        """The kind's grow-only workspace for a batch of B x T frames (slot: 1 for the second half-batch of _infer_two_groups)."""
+        nbytes = kind.fn("workspace_bytes")(h, B, T)
+        slot = kind.ws_slot if slot is None else slot
         wss = self.__dict__.setdefault("_facppg_ws", {})
-        ws = wss.get("bf16x3")
+        ws = wss.get(slot)
         if ws is None or ws.numel() < nbytes or ws.device != dev:
-            ws = wss["bf16x3"] = torch.empty(nbytes, dtype=torch.uint8, device=dev)
-        with torch.cuda.device(dev):
-            _lib.check(L.facppg_wg_split_infer(h, _lib.ptr(spect), _lib.ptr(lt), _lib.ptr(zt), seed & 0xFFFFFFFFFFFFFFFF, float(sigma),
-                                               B, T, _lib.ptr(audio), _lib.ptr(ws), ws.numel(), _lib.current_stream(dev)))
-        return audio
-
-    def _half_handle(self, h):
-        """Whether ``h`` -- the module's current handle -- holds fp16 images: _precision() as it was when the handle was built
-        (any change of a parameter since then makes _handle() build a new one)."""
-        cur = self.__dict__.get("_facppg_handle")
-        if cur is None or cur[0] is not h:
-            raise _lib.FacppgError("WaveGlow: the handle passed in is not this module's current one (its weights changed since)")
-        return cur[3] == torch.float16
+            ws = wss[slot] = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+        return ws
 
     def _precision(self):
         """The inference precision of the module: the dtype of its WN and upsample parameters -- all fp32 (facppg_wg_create)
@@ -1192,12 +1233,7 @@ class WaveGlow(torch.nn.Module):
         N = audio.shape[1]
         hop = self.upsample.stride[0]
         h = self._handle(dev)
-        nbytes = L.facppg_wg_workspace_bytes(h, B, (N + hop - 1) // hop)
-        wss = self.__dict__.setdefault("_facppg_ws", {})
-        ws = wss.get(0)
-        if ws is None or ws.numel() < nbytes or ws.device != dev:
-            ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
-            wss[0] = ws
+        ws = self._workspace(h, _KINDS[torch.float32], B, (N + hop - 1) // hop, dev)
         Lg = N // self.n_group
         z = torch.empty(B, self.n_group, Lg, device=dev)
         log_s_flat = torch.empty(L.facppg_wg_log_s_count(h, B, N), device=dev)
@@ -1246,7 +1282,7 @@ class WaveGlow(torch.nn.Module):
                 best = (cost, tiles / 512.0 * full, tiles)
         return 1.0 - best[1] / best[0] if best[0] and best[2] > 512 else 0.0
 
-    def _infer_two_groups(self, spect, sigma, zt, lengths, seed, utterance_seeds):
+    def _infer_two_groups(self, h, kind, spect, sigma, zt, lengths, seed, utterance_seeds):
         """A ragged batch as TWO interleaved half-batches, the second on a side stream.  Utterances are independent and every
         one is computed exactly as in its own batch-1 call, so the split changes no bit of the result; what it changes is
         the tail of every layer launch: a launch runs in rounds of 512 workgroup slots and its last, partial round leaves
@@ -1283,145 +1319,93 @@ class WaveGlow(torch.nn.Module):
             else:
                 z_g = None
             a = torch.zeros(len(idx), Tg * hop, dtype=torch.float32, device=dev)
-            ws = self._infer_workspace(len(idx), Tg, dev, gi)
+            ws = self._workspace(h, kind, len(idx), Tg, dev, gi)
             parts.append((it, lt, Tg, mel_g, z_g, a, ws))
         side.wait_stream(cur)
         for gi, (it, lt, Tg, mel_g, z_g, a, ws) in enumerate(parts):
             with torch.cuda.stream(side if gi else cur):
-                self._infer_launch(mel_g, lt, z_g, (seed + 0x9E3779B97F4A7C15 * gi) & 0x7FFFFFFFFFFFFFFF, sigma, a, ws)
+                self._infer_launch(h, kind, mel_g, lt, z_g, (seed + 0x9E3779B97F4A7C15 * gi) & 0x7FFFFFFFFFFFFFFF, sigma, a, ws)
         cur.wait_stream(side)
         for it, lt, Tg, mel_g, z_g, a, ws in parts:
             out[:, :Tg * hop].index_copy_(0, it, a)
         return out
 
-    def _infer_workspace(self, B, T, dev, slot, handle=None):
-        nbytes = _lib.load().facppg_wg_workspace_bytes(self._resolve(dev, handle)[0], B, T)
-        wss = self.__dict__.setdefault("_facppg_ws", {})
-        ws = wss.get(slot)
-        if ws is None or ws.numel() < nbytes or ws.device != dev:
-            ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
-            wss[slot] = ws
-        return ws
-
-    def _infer_launch(self, spect, lt, zt, seed, sigma, audio, ws, handle=None, cond_first=False):
-        """The launch sequence of one batch on the current stream; no host-side waits.  fp16 images: facppg_wg_infer_f16_order,
-        which takes the K order of the gate GEMMs (cond_first)."""
+    @staticmethod
+    def _infer_launch(h, kind, spect, lt, zt, seed, sigma, audio, ws, cond_first=False):
+        """The launch sequence of one batch on the current stream; no host-side waits.  cond_first: the K order of the gate GEMMs,
+        for the kind whose entry point takes one."""
         dev = spect.device
         B, _, T = spect.shape
-        h, dt, _ = self._resolve(dev, handle)
-        L = _lib.load()
-        order = (1 if cond_first else 0,) if dt == torch.float16 else ()
+        order = (1 if cond_first else 0,) if kind.takes_order else ()
         with torch.cuda.device(dev):
-            _lib.check((L.facppg_wg_infer_f16_order if order else L.facppg_wg_infer)(
-                h, _lib.ptr(spect), _lib.ptr(lt), _lib.ptr(zt), seed & 0xFFFFFFFFFFFFFFFF, float(sigma), B, T, *order, _lib.ptr(audio),
-                _lib.ptr(ws), ws.numel(), _lib.current_stream(dev)))
+            _lib.check(kind.fn("infer")(h, _lib.ptr(spect), _lib.ptr(lt), _lib.ptr(zt), seed & 0xFFFFFFFFFFFFFFFF, float(sigma), B, T,
+                                        *order, _lib.ptr(audio), _lib.ptr(ws), ws.numel(), _lib.current_stream(dev)))
 
-    # ---- seeded inference of ONE utterance: the conditioning part of every layer's gate GEMM formed ahead of time
-    # (seed layout, cond seed, infer seeded): the C entry points by the precision of the handle's weight images
-    _SEEDED_ENTRY = {torch.float32: ("facppg_wg_seed_layout", "facppg_wg_cond_seed", "facppg_wg_infer_seeded"),
-                     torch.float16: ("facppg_wg_seed_layout_f16", "facppg_wg_cond_seed_f16", "facppg_wg_infer_seeded_f16")}
-
-    def _resolve(self, dev, handle=None):
-        """(handle, dtype of its weight images, its _SEEDED_ENTRY functions) of ``handle`` -- the module's current one, anything else
-        is refused -- or, with None, of the module's handle for ``dev`` (validated or built now)."""
-        h = handle if handle is not None else self._handle(dev)
-        dt = torch.float16 if self._half_handle(h) else torch.float32
-        L = _lib.load()
-        return h, dt, [getattr(L, name) for name in self._SEEDED_ENTRY[dt]]
-
-    def _seed_layout(self, h, layout, T):
+    # ---- seeded inference of ONE utterance: the conditioning part of every layer's gate GEMM formed ahead of time (seed layout,
+    # mel pad / convert, cond seed, infer seeded).  Every method: the call's kind (_kind), what can be refused without a device, the
+    # handle (_resolve), the kind's entry point.
+    @staticmethod
+    def _seed_layout(h, kind, T):
+        """(Tqp, margin, seed_bytes, max_block_tiles) of the kind for T frames."""
         c = _lib.ctypes
-        tqp, mg, nb = c.c_int(), c.c_int(), c.c_size_t()
-        _lib.check(layout(h, int(T), c.byref(tqp), c.byref(mg), c.byref(nb)))
-        return tqp.value, mg.value, nb.value
-
-    # ---- the same on split-bf16 operands (arithmetic="bf16x3"): the split handle and the facppg_wg_split_* entry points
-    def _require_split_module(self, who):
-        if self._precision() != torch.float32:
-            raise _lib.FacppgError("WaveGlow.%s: arithmetic='bf16x3' splits fp32 operands: an all-fp32 module (a .half() module "
-                                   "runs the fp16 kernels)" % who)
-
-    def _resolve_split(self, who, dev, handle=None):
-        """The split handle the seeded methods run on: ``handle`` -- the module's current split handle, anything else is refused --
-        or, with None, the module's split handle for ``dev`` (validated or built now).  All-fp32 modules only."""
-        if handle is None:
-            self._require_split_module(who)
-            return self._split_handle(dev)
-        cur = self.__dict__.get("_facppg_split_handle")
-        if cur is None or cur[0] is not handle:
-            raise _lib.FacppgError("WaveGlow.%s: the handle passed in is not this module's current split-bf16 one (its weights "
-                                   "changed since)" % who)
-        return handle
-
-    def _split_seed_layout(self, h, T):
-        c = _lib.ctypes
-        tqp, mg, nb, bt = c.c_int(), c.c_int(), c.c_size_t(), c.c_int()
-        _lib.check(_lib.load().facppg_wg_split_seed_layout(h, int(T), c.byref(tqp), c.byref(mg), c.byref(nb), c.byref(bt)))
+        tqp, mg, nb, bt = c.c_int(), c.c_int(), c.c_size_t(), c.c_int(kind.max_block_tiles or 0)
+        reported = (c.byref(bt),) if kind.max_block_tiles is None else ()
+        _lib.check(kind.fn("seed_layout")(h, int(T), c.byref(tqp), c.byref(mg), c.byref(nb), *reported))
         return tqp.value, mg.value, nb.value, bt.value
 
     @staticmethod
-    def _check_split_mel_buffer(who, melp):
-        if melp.dtype != torch.float32:
-            raise _lib.FacppgError("%s: arithmetic='bf16x3' reads an fp32 mel buffer [Tqp, n_mel], this one is %s" % (who, melp.dtype))
+    def _check_mel_buffer(who, melp, kind):
+        if melp.dtype != kind.mel_dtype:
+            raise _lib.FacppgError(("%s: arithmetic='bf16x3' reads an fp32 mel buffer [Tqp, n_mel], this one is %s" if kind is _SPLIT
+                                    else "%%s: the module is %s, its mel buffer is %%s" % kind.name) % (who, melp.dtype))
 
-    def seed_layout(self, T, device, arithmetic=None):
+    def seed_layout(self, T, device, arithmetic=None, block_tiles=False):
         """(Tqp, margin, seed_bytes) for an utterance of T frames: the zero-margined mel buffer is [n_mel, Tqp] with frame q at
-        column margin + q; the seed buffer has seed_bytes bytes (facppg_wg_seed_layout).  arithmetic="bf16x3": (Tqp, margin,
-        seed_bytes, max_block_tiles) of the split path -- the mel buffer is fp32 [Tqp, n_mel], frame q at ROW margin + q, and
-        cond_seed takes block_tiles up to max_block_tiles (facppg_wg_split_seed_layout)."""
-        if self._check_arithmetic(arithmetic):
-            return self._split_seed_layout(self._resolve_split("seed_layout", device), T)
-        h, _, (layout, _, _) = self._resolve(device)
-        return self._seed_layout(h, layout, T)
+        column margin + q -- of a .half() module fp16 [Tqp, n_mel], frame q at ROW margin + q --; the seed buffer has seed_bytes bytes.
+        arithmetic="bf16x3", or block_tiles=True for any kind: (Tqp, margin, seed_bytes, max_block_tiles) -- cond_seed takes
+        block_tiles up to max_block_tiles; the split path's mel buffer is fp32 [Tqp, n_mel]."""
+        kind, split = self._kind("seed_layout", arithmetic)
+        layout = self._seed_layout(self._resolve("seed_layout", device, None, kind), kind, T)
+        return layout if split or block_tiles else layout[:3]
 
     def mel_pad(self, mel, handle=None, arithmetic=None):
         """mel [1, n_mel, T] -> the zero-margined [n_mel, Tqp] buffer cond_seed / infer_seeded read; of a .half() module: an fp32
         (or half) mel -> the fp16 [Tqp, n_mel] buffer, rounded to nearest even.  arithmetic="bf16x3": an fp32 mel -> the fp32
         [Tqp, n_mel] buffer of the split path."""
-        split = self._check_arithmetic(arithmetic)
-        dev = mel.device
-        T = mel.shape[2]
+        kind, split = self._kind("mel_pad", arithmetic, handle)
+        dev, T = mel.device, mel.shape[2]
         if split:
             if mel.dtype != torch.float32:
                 raise _lib.FacppgError("WaveGlow.mel_pad: arithmetic='bf16x3' takes an fp32 mel (got %s)" % mel.dtype)
             _lib.require_cuda(mel, "WaveGlow.mel_pad: mel")
-            h = self._resolve_split("mel_pad", dev, handle)
-            out = torch.zeros(self._split_seed_layout(h, T)[0], mel.shape[1], dtype=torch.float32, device=dev)
-            self.mel_convert(mel[0].contiguous(), T, 0, T, out, handle=h, arithmetic=arithmetic)
+        h = self._resolve("mel_pad", dev, handle, kind)
+        tqp = self._seed_layout(h, kind, T)[0]
+        if kind.mel_rows:
+            out = torch.zeros(tqp, mel.shape[1], dtype=kind.mel_dtype, device=dev)
+            self.mel_convert(mel[0].float().contiguous(), T, 0, T, out, handle=h, arithmetic=arithmetic)
             return out
-        h, dt, (layout, _, _) = self._resolve(dev, handle)
-        tqp = self._seed_layout(h, layout, T)[0]
-        if dt == torch.float16:
-            out = torch.zeros(tqp, mel.shape[1], dtype=torch.float16, device=dev)
-            self.mel_convert(mel[0].float(), T, 0, T, out, handle=h)
-            return out
-        out = torch.empty(mel.shape[1], tqp, dtype=torch.float32, device=dev)
+        out = torch.empty(mel.shape[1], tqp, dtype=kind.mel_dtype, device=dev)
         m = mel[0]
         with torch.cuda.device(dev):
-            _lib.check(_lib.load().facppg_wg_mel_pad(h, _lib.ptr(m), T, m.stride(0), _lib.ptr(out), _lib.current_stream(dev)))
+            _lib.check(kind.fn("mel_pad")(h, _lib.ptr(m), T, m.stride(0), _lib.ptr(out), _lib.current_stream(dev)))
         return out
 
     def mel_convert(self, mel, T, frame0, nframes, melp, skip=None, handle=None, arithmetic=None):
         """Frames [frame0, frame0 + nframes) of the fp32 ``mel`` [n_mel, >= frame0 + nframes] (row stride mel.stride(0)) into the
-        fp16 zero-margined ``melp`` [Tqp, n_mel] laid out for T frames (k_cc_mel_cvt), on the current stream.  .half() modules.
-        arithmetic="bf16x3" (all-fp32 modules): into the split path's fp32 ``melp`` [Tqp, n_mel] (the same kernel, for fp32)."""
-        split = self._check_arithmetic(arithmetic)
+        zero-margined ``melp`` [Tqp, n_mel] laid out for T frames (k_cc_mel_cvt), on the current stream: a .half() module's fp16
+        buffer, or with arithmetic="bf16x3" (all-fp32 modules) the split path's fp32 one (the same kernel, for fp32).  The fp32
+        kind's channel-major buffer is filled whole, by mel_pad."""
+        kind, _ = self._kind("mel_convert", arithmetic, handle)
+        if mel.dtype != torch.float32 or mel.stride(1) != 1:
+            raise _lib.FacppgError("mel_convert: fp32 rows in (got %s)" % mel.dtype)
+        if not kind.mel_rows:
+            raise _lib.FacppgError("mel_convert: fp32 rows in, the fp16 mel buffer out (an fp32 module's buffer is channel-major: mel_pad)")
+        self._check_mel_buffer("mel_convert", melp, kind)
         dev = melp.device
-        if split:
-            if mel.dtype != torch.float32 or mel.stride(1) != 1:
-                raise _lib.FacppgError("mel_convert: fp32 rows in (got %s)" % mel.dtype)
-            self._check_split_mel_buffer("mel_convert", melp)
-            h = self._resolve_split("mel_convert", dev, handle)
-            with torch.cuda.device(dev):
-                _lib.check(_lib.load().facppg_wg_split_mel_pad(h, _lib.ptr(mel), int(T), mel.stride(0), int(frame0), int(nframes),
-                                                               _lib.ptr(melp), _lib.ptr(skip), _lib.current_stream(dev)))
-            return
-        if mel.dtype != torch.float32 or melp.dtype != torch.float16 or mel.stride(1) != 1:
-            raise _lib.FacppgError("mel_convert: fp32 rows in, the fp16 mel buffer out")
+        h = self._resolve("mel_convert", dev, handle, kind)
         with torch.cuda.device(dev):
-            _lib.check(_lib.load().facppg_wg_mel_pad_f16(self._resolve(dev, handle)[0], _lib.ptr(mel), int(T),
-                                                         mel.stride(0), int(frame0), int(nframes), _lib.ptr(melp), _lib.ptr(skip),
-                                                         _lib.current_stream(dev)))
+            _lib.check(kind.fn("mel_pad")(h, _lib.ptr(mel), int(T), mel.stride(0), int(frame0), int(nframes), _lib.ptr(melp),
+                                          _lib.ptr(skip), _lib.current_stream(dev)))
 
     def cond_seed(self, melp, T, frame0, nframes, seeds, block_tiles=1, layers_per_workgroup=4, skip=None, handle=None, flows=None,
                   max_workgroups=0, counter=None, arithmetic=None):
@@ -1432,25 +1416,16 @@ class WaveGlow(torch.nn.Module):
         its fp16 mel buffer (mel_pad / mel_convert) and forms the raw conditioning sums, no bias (k16_cond_seed).
         arithmetic="bf16x3" (all-fp32 modules): the split path's fp32 mel buffer, the raw sums of the split products
         (ks_cond_seed); block_tiles at most seed_layout's max_block_tiles."""
-        split = self._check_arithmetic(arithmetic)
+        kind, _ = self._kind("cond_seed", arithmetic, handle)
+        self._check_mel_buffer("cond_seed", melp, kind)
         dev = melp.device
         f0, nf = flows if flows is not None else (0, 0)
-        if split:
-            self._check_split_mel_buffer("cond_seed", melp)
-            h, seed_fn = self._resolve_split("cond_seed", dev, handle), _lib.load().facppg_wg_split_cond_seed
-        else:
-            h, dt, (_, seed_fn, _) = self._resolve(dev, handle)
-            self._check_mel_buffer("cond_seed", melp, dt)
+        h = self._resolve("cond_seed", dev, handle, kind)
         with torch.cuda.device(dev):
-            _lib.check(seed_fn(h, _lib.ptr(melp), int(T), int(frame0),
+            _lib.check(kind.fn("cond_seed")(h, _lib.ptr(melp), int(T), int(frame0),
                        int(nframes), int(block_tiles), int(layers_per_workgroup), int(f0), int(nf), _lib.ptr(seeds),
                        seeds.numel() * seeds.element_size(), _lib.ptr(skip), int(max_workgroups), _lib.ptr(counter),
                        _lib.current_stream(dev)))
-
-    @staticmethod
-    def _check_mel_buffer(who, melp, dt):
-        if melp.dtype != dt:
-            raise _lib.FacppgError("%s: the module is %s, its mel buffer is %s" % (who, "fp16" if dt == torch.float16 else "fp32", melp.dtype))
 
     def infer_seeded(self, melp, T, seeds, seeded_frames, sigma=1.0, z=None, seed=None, handle=None, T_layout=None, flow_events=None,
                      arithmetic=None):
@@ -1461,53 +1436,35 @@ class WaveGlow(torch.nn.Module):
         arithmetic="bf16x3" (all-fp32 modules, the split path's fp32 ``melp``): fp32 audio on split-bf16 operands in the
         conditioning-first K order -- the same bits whichever tiles were seeded (seeded_frames may be 0, ``seeds`` then None), in
         the last bits not those of infer(arithmetic="bf16x3"), which sums the taps first."""
-        split = self._check_arithmetic(arithmetic)
+        kind, split = self._kind("infer_seeded", arithmetic, handle)
+        self._check_mel_buffer("infer_seeded", melp, kind)
         T_layout = T if T_layout is None else int(T_layout)
         dev = melp.device
-        if split:
-            self._check_split_mel_buffer("infer_seeded", melp)
-            h, dt, infer_fn = self._resolve_split("infer_seeded", dev, handle), torch.float32, _lib.load().facppg_wg_split_infer_seeded
-            if seeds is None and int(seeded_frames) == 0:
-                seeds = melp                       # (never read: no tile starts from a seed)
-        else:
-            h, dt, (_, _, infer_fn) = self._resolve(dev, handle)
-            self._check_mel_buffer("infer_seeded", melp, dt)
-        zt, _, seed, _ = self._infer_args(1, T, dt, z, None, seed, None, dev)
-        if split:
-            nbytes = _lib.load().facppg_wg_split_workspace_bytes(h, 1, T_layout)
-            wss = self.__dict__.setdefault("_facppg_ws", {})
-            ws = wss.get("bf16x3")
-            if ws is None or ws.numel() < nbytes or ws.device != dev:
-                ws = wss["bf16x3"] = torch.empty(nbytes, dtype=torch.uint8, device=dev)
-        else:
-            ws = self._infer_workspace(1, T_layout, dev, 0, h)
-        audio = torch.empty(1, T * self.upsample.stride[0], dtype=dt, device=dev)
+        h = self._resolve("infer_seeded", dev, handle, kind)
+        if split and seeds is None and int(seeded_frames) == 0:
+            seeds = melp                           # (never read: no tile starts from a seed)
+        zt, _, seed, _ = self._infer_args(1, T, kind.dtype, z, None, seed, None, dev)
+        ws = self._workspace(h, kind, 1, T_layout, dev)
+        audio = torch.empty(1, T * self.upsample.stride[0], dtype=kind.dtype, device=dev)
         evs = None
         if flow_events:
             evs = (_lib.ctypes.c_void_p * self.n_flows)()
             for k, ev in flow_events.items():
                 evs[k] = ev.cuda_event
         with torch.cuda.device(dev):
-            _lib.check(infer_fn(h, _lib.ptr(melp), T_layout, int(T), _lib.ptr(seeds), int(seeded_frames), _lib.ptr(zt),
-                                seed & 0xFFFFFFFFFFFFFFFF, float(sigma), _lib.ptr(audio), _lib.ptr(ws), ws.numel(),
-                                evs, _lib.current_stream(dev)))
+            _lib.check(kind.fn("infer_seeded")(h, _lib.ptr(melp), T_layout, int(T), _lib.ptr(seeds), int(seeded_frames), _lib.ptr(zt),
+                                               seed & 0xFFFFFFFFFFFFFFFF, float(sigma), _lib.ptr(audio), _lib.ptr(ws), ws.numel(),
+                                               evs, _lib.current_stream(dev)))
         return audio
 
     def prepare(self, device, arithmetic=None):
         """Validate (or build) the packed weights for ``device`` NOW and remember that for the next ``infer`` on this thread's
         next call: the check walks ~1000 tensors (0.4 ms of host time); facppg.pipeline runs it while the acoustic model's
-        decoder keeps the GPU busy instead of between the two models.  Single use: the next infer() -- whatever path it takes --
-        consumes it, and it is only honoured while the handle it validated is still the model's handle.  arithmetic: the one that
-        infer() will be called with (its handle is the one validated)."""
-        split = self._check_arithmetic(arithmetic)
-        self.__dict__["_facppg_prepared"] = (self._split_handle(device) if split else self._handle(device), device)
-
-    def _checked_handle(self, dev):
-        pre = self.__dict__.pop("_facppg_prepared", None)
-        cur = self.__dict__.get("_facppg_handle")
-        if pre is not None and pre[1] == dev and cur is not None and cur[0] is pre[0]:
-            return pre[0]
-        return self._handle(dev)
+        decoder keeps the GPU busy instead of between the two models.  Single use: the next infer() or handle() -- whatever path
+        it takes -- consumes it, and it is only honoured while the handle it validated is still the model's handle.  arithmetic:
+        the one that infer() will be called with (its handle is the one validated)."""
+        kind = _SPLIT if self._check_arithmetic(arithmetic) else _KINDS[torch.float32]      # (either precision: the module's own handle)
+        self.__dict__["_facppg_prepared"] = (self._valid_handle(device, kind), device)
 
     def _infer_args(self, B, T, dtype, z, lengths, seed, utterance_seeds, device=None):
         """The arguments infer() and infer_seeded() share, checked and normalised -> (z, lengths, seed, utterance_seeds):
@@ -1560,46 +1517,49 @@ class WaveGlow(torch.nn.Module):
         contractions on the bf16 MFMA with every fp32 operand split into two bf16 terms and three partial products accumulated
         in fp32 (facppg_wg_split_infer): fp32 mel in, fp32 audio out, relative RMS ~7e-6 against the fp32 path; one launch
         sequence (no groups=, no cond_first); an utterance gets the same bits in any batch."""
+        # the refusals, every one before a device is touched: the split kind's (whose kind needs no device to be known) in front of
+        # the device check, the module's own kinds' behind it
         if self._check_arithmetic(arithmetic):
             if groups is not None or cond_first:
                 raise _lib.FacppgError("WaveGlow.infer: arithmetic='bf16x3' runs one launch sequence in its own K order; "
                                        "it takes neither groups= nor cond_first=True")
-            if spect.dtype != torch.float32 or self._precision() != torch.float32:
-                raise _lib.FacppgError("WaveGlow.infer: arithmetic='bf16x3' splits fp32 operands: an all-fp32 module and an fp32 mel "
-                                       "(a .half() module runs the fp16 kernels)")
+            if spect.dtype != torch.float32:
+                raise _lib.FacppgError(self._SPLIT_NEEDS % "infer")
+            kind, groups = self._kind("infer", arithmetic)[0], 1
             _lib.require_cuda(spect, "WaveGlow.infer: spect")
-            return self._infer_split(spect, sigma, z, lengths, seed, utterance_seeds)
-        _lib.require_cuda(spect, "WaveGlow.infer: spect")
-        if spect.dtype != torch.float32 or self.upsample.weight.dtype != torch.float32:
-            if self._precision() != torch.float16:
-                raise _lib.FacppgError("WaveGlow.infer: fp32 only for this module (its WN / upsample parameters are fp32; "
-                                       "got a %s mel) -- .half() the module for half inference" % spect.dtype)
-            if spect.dtype != torch.float16:
-                raise _lib.FacppgError("WaveGlow.infer: the module is fp16 (.half()), the mel must be fp16 too (got %s)" % spect.dtype)
-            if groups not in (None, 1):
-                raise _lib.FacppgError("WaveGlow.infer: groups=%r: the fp16 path runs one launch sequence (groups=1)" % (groups,))
-            groups = 1
-        elif cond_first:
-            raise _lib.FacppgError("WaveGlow.infer: cond_first=True is the K order of a .half() module's kernels; the fp32 path sums "
-                                   "the conditioning chunks first already")
+        else:
+            _lib.require_cuda(spect, "WaveGlow.infer: spect")
+            kind = self._kind("infer", arithmetic)[0]
+            if spect.dtype != kind.dtype:
+                raise _lib.FacppgError(
+                    "WaveGlow.infer: the module is fp16 (.half()), the mel must be fp16 too (got %s)" % spect.dtype if kind.takes_order else
+                    "WaveGlow.infer: fp32 only for this module (its WN / upsample parameters are fp32; got a %s mel) -- .half() the "
+                    "module for half inference" % spect.dtype)
+            if kind.takes_order:
+                if groups not in (None, 1):
+                    raise _lib.FacppgError("WaveGlow.infer: groups=%r: the fp16 path runs one launch sequence (groups=1)" % (groups,))
+                groups = 1
+            elif cond_first:
+                raise _lib.FacppgError("WaveGlow.infer: cond_first=True is the K order of a .half() module's kernels; the fp32 path "
+                                       "sums the conditioning chunks first already")
         dev = spect.device
-        h = self._checked_handle(dev)   # (ONE validity check of the packed weights per call -- it walks ~1000 tensors -- or none:
-        spect = spect.contiguous()      #  prepare(); consumed HERE so that no path -- two half-batches included -- leaves the token behind)
+        h = self._checked_handle(dev, kind)   # (ONE validity check of the packed weights per call -- it walks ~1000 tensors -- or none:
+        spect = spect.contiguous()            #  prepare(); consumed HERE so that no path -- two half-batches included -- leaves the token behind)
         B, _, T = spect.shape
         hop = self.upsample.stride[0]
-        zt, lengths, seed, utterance_seeds = self._infer_args(B, T, spect.dtype, z, lengths, seed, utterance_seeds, dev)
+        zt, lengths, seed, utterance_seeds = self._infer_args(B, T, kind.dtype, z, lengths, seed, utterance_seeds, dev)
         host_lengths = isinstance(lengths, list)
-        if groups is None:
+        if groups is None:                    # (the fp32 kind alone gets this far undecided)
             groups = 2 if (host_lengths and B >= 4 and self._tail_loss(lengths, hop) >= 0.03) else 1
         if groups == 2:
             if not host_lengths or B < 2:
                 raise _lib.FacppgError("WaveGlow.infer: groups=2 needs B >= 2 utterances and their lengths as a host list")
-            return self._infer_two_groups(spect, sigma, zt, lengths, seed, utterance_seeds)   # (draws the noise per half-batch)
-        if utterance_seeds is not None:
-            zt = self.draw_noise(utterance_seeds, T, dev).to(spect.dtype)
+            return self._infer_two_groups(h, kind, spect, sigma, zt, lengths, seed, utterance_seeds)   # (draws the noise per half-batch)
+        if utterance_seeds is not None:       # (drawn on the module's fp32 / fp16 handle for every kind: the same noise)
+            zt = self.draw_noise(utterance_seeds, T, dev).to(kind.dtype)
         lt = _lib.upload(lengths, torch.int32, dev) if host_lengths else lengths
-        audio = (torch.empty if lt is None else torch.zeros)(B, T * hop, dtype=spect.dtype, device=dev)
-        self._infer_launch(spect, lt, zt, seed, sigma, audio, self._infer_workspace(B, T, dev, 0, h), h, cond_first)
+        audio = (torch.empty if lt is None else torch.zeros)(B, T * hop, dtype=kind.dtype, device=dev)
+        self._infer_launch(h, kind, spect, lt, zt, seed, sigma, audio, self._workspace(h, kind, B, T, dev), cond_first)
         return audio
 
     @staticmethod
