@@ -263,6 +263,10 @@ def _declare(lib):
         "facppg_join_segments": (c.c_int, [vp, c.c_int, vp, vp, c.c_int, c.c_int, vp, vp]),
         "facppg_ppg_dtw_workspace_bytes": (sz, [c.c_int, c.c_int, c.c_int, c.c_int, c.c_int]),
         "facppg_ppg_dtw": (c.c_int, [vp, vp, vp, c.c_int, vp, vp, vp, c.c_int, c.c_int, c.c_int, c.c_int, vp, vp, vp, vp, sz, vp]),
+        "facppg_mel_dtw_workspace_bytes": (sz, [c.c_int, c.c_int, c.c_int, c.c_int, c.c_int, c.c_int]),
+        "facppg_mel_dtw": (c.c_int, [vp, vp, vp, c.c_int, vp, vp, vp, c.c_int, c.c_int, c.c_int, vp, c.c_int, c.c_int, vp, vp, vp, sz, vp]),
+        "facppg_attention_path_workspace_bytes": (sz, [c.c_int, c.c_int, c.c_int]),
+        "facppg_attention_path": (c.c_int, [vp, vp, vp, c.c_int, vp, vp, c.c_int, c.c_int, vp, vp, vp, sz, vp]),
         "facppg_tdnn_forward_batch_padded_strided": (c.c_int, [vp, vp, vp, vp, c.c_int, vp, c.c_int, c.c_int, sz, vp, vp, sz, vp]),
         "facppg_f0_workspace_bytes": (sz, [c.POINTER(F0Config), c.c_int]),
         "facppg_f0_nccf_batch": (c.c_int, [c.POINTER(F0Config), vp, vp, vp, vp, vp, c.c_int, vp, vp]),

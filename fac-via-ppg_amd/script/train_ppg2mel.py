@@ -1,9 +1,11 @@
 """The reference's src/script/train_ppg2mel.py on the HIP kernels: ``load_model`` (:113-119, imported by
 generate_synthesis.py:20), ``warm_start_model`` (:122-127), ``load_checkpoint`` / ``save_checkpoint`` (:130-150),
 ``validate`` (:152-177), which scores a checkpoint on held-out data through the teacher-forced ``Tacotron2.forward`` and
-``Tacotron2Loss``, and ``finetune``: the body of the training loop (:199-276) for one GPU with EVAL-MODE semantics, on the
-backward pass of ``Tacotron2.forward(..., differentiable=True)``.  ``train`` itself is not built: training-mode BatchNorm and
-the training-mode dropouts have no kernels."""
+``Tacotron2Loss``, ``validate_free_running``, which scores it the way it converts -- the free-running decoder's mels against the
+targets by a mel-cepstral DTW, and what its attention did (no counterpart in the reference) --, and ``finetune``: the body of
+the training loop (:199-276) for one GPU with EVAL-MODE semantics, on the backward pass of
+``Tacotron2.forward(..., differentiable=True)``.  ``train`` itself is not built: training-mode BatchNorm and the training-mode
+dropouts have no kernels."""
 import math
 import os
 import time
@@ -53,7 +55,7 @@ def save_checkpoint(model, optimizer, learning_rate, iteration, filepath):
 
 
 def finetune(model, hparams, trainset, collate_fn, steps, output_directory=None, valset=None, checkpoint_path=None,
-             warm_start=False, step_seeds=None, step_masks=None, optimizer=None, logger=None, log=print):
+             warm_start=False, step_seeds=None, step_masks=None, optimizer=None, logger=None, log=print, free_running=False):
     """Fit ``model`` to ``trainset`` for ``steps`` optimiser steps: the body of the reference's training loop
     (train_ppg2mel.py:199-276) on one GPU -- Adam (``waveglow.optim.Adam``, one HIP launch per step) with
     ``hparams.learning_rate`` / ``weight_decay``, zero_grad -> parse_batch -> forward -> Tacotron2Loss -> backward ->
@@ -75,11 +77,16 @@ def finetune(model, hparams, trainset, collate_fn, steps, output_directory=None,
     checkpoint_path / warm_start   initialise from a checkpoint's weights (warm start) or resume it: weights, optimiser state,
                  iteration (and its learning rate when ``hparams.use_saved_learning_rate``)
     optimizer    None (built here) or the optimiser to use and resume into
-    Returns a dict: losses and grad_norms (pre-clip) per step, iteration (the next one), optimizer, learning_rate."""
+    free_running True: next to ``validate``, every checkpoint is also scored the way it converts (``validate_free_running`` on
+                 ``valset``, which it therefore needs); the training steps do not depend on it
+    Returns a dict: losses and grad_norms (pre-clip) per step, iteration (the next one), optimizer, learning_rate, and
+    free_running: a list of (iteration, validate_free_running's result), empty without the flag."""
     from common.loss_function import Tacotron2Loss
     from waveglow.optim import Adam
     if hparams.fp16_run:
         raise NotImplementedError("finetune: fp16_run is not built (README.md:53 of the reference: FP16 does not work)")
+    if free_running and valset is None:
+        raise ValueError("finetune: free_running=True scores the checkpoints on a valset, and none was given")
     if any(not p.is_cuda for p in model.parameters()):
         raise ValueError("finetune: the model must be on the GPU (there is no CPU path): load_model(hparams)")
     if step_seeds is not None and step_masks is not None:
@@ -103,7 +110,7 @@ def finetune(model, hparams, trainset, collate_fn, steps, output_directory=None,
     if len(batches) == 0:
         raise ValueError("finetune: the training set yields no batch")
     model.eval()
-    losses, norms, done = [], [], 0
+    losses, norms, free_runs, done = [], [], [], 0
     while done < steps:
         for batch in batches:
             if done == steps:
@@ -137,10 +144,14 @@ def finetune(model, hparams, trainset, collate_fn, steps, output_directory=None,
                 if valset is not None:
                     validate(model, criterion, valset, iteration, hparams.batch_size, 1, collate_fn, logger, False, 0)
                     model.eval()                                  # (validate leaves train() mode, as the reference does)
+                    if free_running:
+                        free_runs.append((iteration, validate_free_running(model, valset, hparams.batch_size, logger=logger,
+                                                                           iteration=iteration)))
                 save_checkpoint(model, optimizer, learning_rate, iteration, os.path.join(output_directory, "checkpoint_{}".format(iteration)))
             iteration += 1
             done += 1
-    return {"losses": losses, "grad_norms": norms, "iteration": iteration, "optimizer": optimizer, "learning_rate": learning_rate}
+    return {"losses": losses, "grad_norms": norms, "iteration": iteration, "optimizer": optimizer, "learning_rate": learning_rate,
+            "free_running": free_runs}
 
 
 def validate(model, criterion, valset, iteration, batch_size, n_gpus, collate_fn, logger, distributed_run, rank):
@@ -176,6 +187,76 @@ def validate(model, criterion, valset, iteration, batch_size, n_gpus, collate_fn
         if logger is not None:
             logger.log_validation(mean_loss, model, targets, outputs, iteration)
     return mean_loss
+
+
+FREE_RUNNING_FIELDS = ("mcd", "stretch", "frames", "target_frames", "stopped", "first", "last", "back", "max_jump", "longest_stall",
+                       "visited", "focus", "coverage", "end_gap")
+
+
+def validate_free_running(model, valset, batch_size, seed=0, n_cep=13, band=0, step_factor=None, logger=None, iteration=0, rank=0):
+    """Score ``model`` on ``valset`` the way it converts: the decoder runs FREE (``Tacotron2.inference``, prenet dropouts on), where it
+    can skip, repeat or babble up to its step limit -- none of which the teacher-forced loss of ``validate`` sees.  No counterpart
+    in the reference.
+
+    valset[k] = (ppg [L_in, n_symbols], acoustic [L_out, n_feat]) is taken IN ORDER in batches of ``batch_size``, padded here (the
+    collate function sorts by length and so loses k).  Utterance k is decoded with ``utterance_seeds = seed + k``: its result does
+    not depend on the batch size.  Its step limit is ``max_decoder_steps``, with ``step_factor`` min(that, ceil(step_factor *
+    L_out)).  ``mel_post`` is scored against the target mel by ``facppg.score.mel_dtw`` (n_cep, band: this build's own
+    mel-cepstral DTW, values compare within this build only) and the alignments by ``facppg.score.attention_path``.
+    Returns a dict: per utterance, in valset order, the arrays mcd, stretch, frames, target_frames, stopped (frames < limit: the
+    gate ended the utterance, not the limit) and attention_path's first, last, back, max_jump, longest_stall, visited, focus,
+    coverage, end_gap; and the aggregates mean_mcd, stopped_share, mean_coverage.
+    The model is in eval mode during the pass and is put back into the mode it was found in.  Rank 0 prints one line."""
+    import numpy as np
+    from facppg import score
+    if int(batch_size) < 1:
+        raise ValueError("validate_free_running: batch_size must be at least 1 (got %r)" % (batch_size,))
+    if step_factor is not None and not float(step_factor) > 0.0:
+        raise ValueError("validate_free_running: step_factor must be positive (got %r)" % (step_factor,))
+    n = len(valset)
+    if n == 0:
+        raise ValueError("validate_free_running: the validation set is empty")
+    dev = next(model.parameters()).device
+    max_steps = int(model.decoder.max_decoder_steps)
+    rows = {name: [] for name in FREE_RUNNING_FIELDS}
+    was_training = model.training
+    model.eval()
+    try:
+        with torch.no_grad():
+            for at in range(0, n, int(batch_size)):
+                items = [valset[k] for k in range(at, min(at + int(batch_size), n))]
+                B = len(items)
+                ppgs, mels = [torch.as_tensor(p).float() for p, _ in items], [torch.as_tensor(m).float() for _, m in items]
+                tin, ttgt = [int(p.shape[0]) for p in ppgs], [int(m.shape[0]) for m in mels]
+                x = torch.zeros(B, ppgs[0].shape[1], max(tin))
+                y = torch.zeros(B, mels[0].shape[1], max(ttgt))
+                for b in range(B):
+                    x[b, :, :tin[b]] = ppgs[b].t()
+                    y[b, :, :ttgt[b]] = mels[b].t()
+                limits = [max_steps if step_factor is None else max(1, min(max_steps, int(math.ceil(float(step_factor) * t)))) for t in ttgt]
+                out = model.inference(x.to(dev), lengths=tin, utterance_seeds=[int(seed) + k for k in range(at, at + B)], step_limits=limits)
+                frames = [int(v) for v in out.out_lengths]
+                dtw = score.mel_dtw(out[1], frames, y.to(dev), ttgt, n_cep=n_cep, band=band)
+                path = score.attention_path(out[3], frames, tin)
+                rows["mcd"].append(dtw["mcd"])
+                rows["stretch"].append(dtw["stretch"])
+                rows["frames"].append(np.asarray(frames, dtype=np.int32))
+                rows["target_frames"].append(np.asarray(ttgt, dtype=np.int32))
+                rows["stopped"].append(np.asarray(frames) < np.asarray(limits))
+                for name in FREE_RUNNING_FIELDS[5:]:
+                    rows[name].append(path[name])
+    finally:
+        model.train(was_training)
+    result = {name: np.concatenate(parts) for name, parts in rows.items()}
+    result["mean_mcd"] = float(result["mcd"].mean())
+    result["stopped_share"] = float(result["stopped"].mean())
+    result["mean_coverage"] = float(result["coverage"].mean())
+    if rank == 0:
+        print("Free-running {}: MCD {:.4f} dB, stopped {:.3f}, coverage {:.3f}".format(iteration, result["mean_mcd"], result["stopped_share"],
+                                                                                     result["mean_coverage"]))
+        if logger is not None and hasattr(logger, "log_free_running"):
+            logger.log_free_running(result, iteration)
+    return result
 
 
 def train(*args, **kwargs):

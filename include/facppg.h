@@ -998,6 +998,59 @@ int facppg_ppg_dtw(const float* a_dev, const int32_t* la_dev, const int32_t* la_
                    void* ws_dev, size_t ws_bytes, void* stream);
 
 /* ------------------------------------------------------------------------------------
+ * Free-running validation (facppg.score.mel_dtw / attention_path, script.train_ppg2mel.validate_free_running): the decoder's
+ * free-running mels against the target mels by a mel-cepstral DTW, and a summary of what its attention did.  The reference has
+ * NO counterpart: its validate() (train_ppg2mel.py:152-177) is teacher-forced only.  THE SCORE IS THIS BUILD'S OWN DEFINITION --
+ * a DTW over an orthonormal DCT of natural-log mels, c0 left out -- as the F0 track below is; its values compare within this
+ * build only, not with MCD figures computed from WORLD or SPTK cepstra.
+ *
+ * facppg_mel_dtw: a_dev [B][M][Ta_max] and b_dev [B][M][Tb_max], fp32 log-mels, frames contiguous (the layout of
+ * Tacotron2.inference's mel_post and of the padded targets); pair p is a[p][:][0 .. la[p]) against b[p][:][0 .. lb[p]), and
+ * nothing behind a length is read (it may hold NaN).  basis_dev [K][M] fp32, any matrix (facppg.score.cepstral_basis: rows 1 .. K
+ * of the orthonormal DCT-II).  Per pair, with Ta = la[p], Tb = lb[p]:
+ *   projection     ca[k][i] = sum_m basis[k][m] a[m][i]: one fp32 fma chain from 0 with m increasing,
+ *                  acc = fma(basis[k][m], a[m][i], acc); cb likewise
+ *   local distance d(i,j) = sqrtf(s), s one fp32 fma chain from 0 with k increasing: diff = ca[k][i] - cb[k][j] (an fp32
+ *                  subtraction), s = fma(diff, diff, s).  DIRECT differences on purpose: |a|^2 + |b|^2 - 2 a.b loses about
+ *                  eps |a|^2 in s when two frames are close, which is the case a validation score is about
+ *   band, recurrence, tie order, N(i,j)   exactly facppg_ppg_dtw's above: m = max(Ta - 1, Tb - 1, 1), (i,j) admissible iff
+ *                  band == 0 or |i (Tb - 1) - j (Ta - 1)| <= band m in 64-bit integers; C(0,0) = d(0,0), else C(i,j) = d(i,j) +
+ *                  min over the admissible predecessors (i-1,j-1), (i-1,j), (i,j-1) tried in that order with a strict <; fp32
+ *                  additions; N(i,j) = N(pred) + 1, N(0,0) = 1
+ *   outputs        cost_dev[p] = C(Ta-1, Tb-1), steps_dev[p] = N(Ta-1, Tb-1)   ([B] each); no backtrace
+ * facppg.score.mel_dtw reports mcd = (10 sqrt(2) / ln 10) cost / steps in dB (the mels are NATURAL-log mels, what
+ * dynamic_range_compression produces).  Lengths come as a device copy (read by the kernels) next to a host copy (validated before
+ * the first launch).  Refused, and nothing is launched: a NULL pointer, B, M, K, Ta_max or Tb_max < 1, a length outside
+ * [1, T*_max], band 1 or band < 0 (FACPPG_EINVAL); M > 256, K > 64, B > 65535 (FACPPG_EUNSUPPORTED); a workspace smaller than
+ * facppg_mel_dtw_workspace_bytes, which holds the cepstra and B (Ta_max + Tb_max - 1) Ta_max distances (FACPPG_EWORKSPACE).
+ * Launches: two projections, one tiled distance kernel over all pairs, and facppg_ppg_dtw's own sweep (one workgroup per pair)
+ * per 1024 rows of the longest a; all on ``stream``, none cooperative, none waits on memory, no atomics.
+ *
+ * facppg_attention_path: align_dev [B][Tout_max][Tin_max] fp32, finite -- Tacotron2.inference's alignments; utterance p has
+ * T = tout[p] decoder steps over L = tin[p] input frames, and nothing behind T or L is read.  With pos[t] = arg max_{j < L}
+ * A[p][t][j] (the lowest j on a tie) and w[t] that maximum, stats_dev[p] holds six integers:
+ *   0 first          pos[0]
+ *   1 last           pos[T-1]
+ *   2 back           #{t >= 1 : pos[t] < pos[t-1]}
+ *   3 max_jump       max(0, max_{t >= 1} pos[t] - pos[t-1])
+ *   4 longest_stall  the longest run of consecutive equal pos (>= 1)
+ *   5 visited        the number of distinct values among pos[0 .. T)
+ * and focus_dev[p] = the mean of w[t], summed in float64 and rounded to fp32 once.  Refused, and nothing is launched: a NULL
+ * pointer, B, Tout_max or Tin_max < 1, a length outside [1, T*_max] (FACPPG_EINVAL); B > 65535 (FACPPG_EUNSUPPORTED); a workspace
+ * smaller than facppg_attention_path_workspace_bytes (FACPPG_EWORKSPACE).  Two launches on ``stream``, none cooperative, no
+ * atomics. */
+size_t facppg_mel_dtw_workspace_bytes(int B, int M, int K, int Ta_max, int Tb_max, int band);
+int facppg_mel_dtw(const float* a_dev, const int32_t* la_dev, const int32_t* la_host, int Ta_max,
+                   const float* b_dev, const int32_t* lb_dev, const int32_t* lb_host, int Tb_max,
+                   int B, int M, const float* basis_dev, int K, int band,
+                   float* cost_dev, int32_t* steps_dev, void* ws_dev, size_t ws_bytes, void* stream);
+size_t facppg_attention_path_workspace_bytes(int B, int Tout_max, int Tin_max);
+int facppg_attention_path(const float* align_dev, const int32_t* tout_dev, const int32_t* tout_host, int Tout_max,
+                          const int32_t* tin_dev, const int32_t* tin_host, int Tin_max, int B,
+                          int32_t* stats_dev /* [B][6] */, float* focus_dev /* [B] */,
+                          void* ws_dev, size_t ws_bytes, void* stream);
+
+/* ------------------------------------------------------------------------------------
  * F0 track on the device, and the reference's log-F0 input columns (hparams.is_append_f0: append_ppg,
  * src/common/data_utils.py:142-160, makes n_symbols = K + 3).  The reference takes its F0 from WORLD through pyworld
  * (utterance.py:33-38: harvest, 48-400 Hz, 5 ms shift), which does not exist in this image and cannot be reproduced here:
