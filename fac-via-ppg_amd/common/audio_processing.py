@@ -37,7 +37,9 @@ def window_sumsquare(window, n_frames, hop_length=200, win_length=800, n_fft=800
 
 def griffin_lim(magnitudes, stft_fn, n_iters=30):
     """Phase retrieval by alternating projections (audio_processing.py:91-107); unused on the
-    synthesis path, runs on stft_fn's (HIP) transform/inverse."""
+    synthesis path, runs on stft_fn's (HIP) transform/inverse.  The vocoder-free preview uses
+    STFT.griffin_lim instead (the same iteration as one device loop, with lengths, momentum and
+    device-drawn phases); this function stays as the reference wrote it."""
     angles = np.angle(np.exp(2j * np.pi * np.random.rand(*magnitudes.size()))).astype(np.float32)
     angles = torch.from_numpy(angles).to(magnitudes.device)
     signal = stft_fn.inverse(magnitudes, angles).squeeze(1)

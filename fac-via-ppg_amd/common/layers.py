@@ -91,3 +91,14 @@ class TacotronSTFT(torch.nn.Module):
         assert torch.min(y.data) >= -1
         assert torch.max(y.data) <= 1
         return self.stft_fn.mel(y, lengths)
+
+    def mel_to_magnitude(self, mel, lengths=None):
+        """log-mel [B, n_mel_channels, F] -> linear magnitude [B, filter_length/2 + 1, F] by the pseudo-inverse of this module's
+        mel basis, clamped at 0 (STFT.mel_to_magnitude: this build's own inversion, the reference has none); lengths: frame
+        counts per utterance, the frames behind them come out as zeros."""
+        return self.stft_fn.mel_to_magnitude(mel, lengths)
+
+    def griffin_lim(self, mel, lengths=None, **kw):
+        """A waveform for a log-mel without a vocoder: mel_to_magnitude, then STFT.griffin_lim (whose keywords ``kw`` are:
+        n_iters, momentum, init_phase, seed, utterance_seeds, return_convergence) -> [B, 1, hop * (F - 1)]."""
+        return self.stft_fn.griffin_lim(self.mel_to_magnitude(mel, lengths), lengths=lengths, **kw)

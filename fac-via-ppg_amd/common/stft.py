@@ -78,6 +78,7 @@ class STFT(torch.nn.Module):
         if h is not None:
             _lib.load().facppg_stft_destroy(h[0])
         self.__dict__.pop("_facppg_ws", None)
+        self.__dict__.pop("_facppg_pinv", None)
 
     def __del__(self):
         try:
@@ -89,6 +90,7 @@ class STFT(torch.nn.Module):
         d = dict(self.__dict__)
         d.pop("_facppg_handle", None)
         d.pop("_facppg_ws", None)
+        d.pop("_facppg_pinv", None)
         return d
 
     def _workspace(self, h, dev, B, N):
@@ -166,6 +168,157 @@ class STFT(torch.nn.Module):
         with torch.cuda.device(dev):
             _lib.check(_lib.load().facppg_stft_mel(h, _lib.ptr(x), _lib.ptr(self._lengths(lengths, B, N, dev)), B, N,
                                                    _lib.ptr(out), _lib.ptr(ws), ws.numel(), _lib.current_stream(dev)))
+        return out
+
+    # ------------------------------------------------------------ vocoder-free preview
+    def _frame_lengths(self, lengths, B, F, dev, what):
+        """``lengths`` as frame counts: None, a host list (checked here: B values in [2, F], each longer than the reflect
+        padding) or a tensor (trusted beyond its size, as _lengths trusts sample counts) -> int32 [B] on the device or None."""
+        if lengths is None:
+            return None
+        if torch.is_tensor(lengths):
+            if lengths.numel() != B:
+                raise _lib.FacppgError("%s: lengths must be B frame counts <= F" % what)
+            return lengths.to(device=dev, dtype=torch.int32).contiguous()
+        fb = [int(n) for n in lengths]
+        if len(fb) != B or max(fb) > F:
+            raise _lib.FacppgError("%s: lengths must be B frame counts <= F" % what)
+        for n in fb:
+            if n < 2 or self.hop_length * (n - 1) <= self.filter_length // 2:
+                raise _lib.FacppgError("%s: an utterance of %d frames has hop * (frames - 1) = %d samples, reflect padding needs more "
+                                       "than filter_length / 2 = %d" % (what, n, self.hop_length * (n - 1), self.filter_length // 2))
+        return _lib.upload(fb, torch.int32, dev)
+
+    @staticmethod
+    def derive_seeds(seed, B):
+        """B per-utterance phase seeds from one integer: SplitMix64 of seed + b (host arithmetic, 64 bits)."""
+        out, m = [], 0xFFFFFFFFFFFFFFFF
+        for b in range(B):
+            z = (int(seed) + (b + 1) * 0x9E3779B97F4A7C15) & m
+            z = ((z ^ (z >> 30)) * 0xBF58476D1CE4E5B9) & m
+            z = ((z ^ (z >> 27)) * 0x94D049BB133111EB) & m
+            out.append(z ^ (z >> 31))
+        return out
+
+    def _phase_seeds(self, B, dev, init_phase, seed, utterance_seeds, what):
+        """The rule of Tacotron2.inference: ``utterance_seeds`` (B integers; utterance b's draws depend on its own alone) or one
+        ``seed`` (B seeds derived on the host; None: drawn), never both, and neither next to ``init_phase``."""
+        if seed is not None and utterance_seeds is not None:
+            raise _lib.FacppgError("%s: seed and utterance_seeds are two ways to say the same thing -- give one" % what)
+        if init_phase is not None:
+            if seed is not None or utterance_seeds is not None:
+                raise _lib.FacppgError("%s: init_phase leaves nothing to draw -- give it without seed / utterance_seeds" % what)
+            return None
+        if utterance_seeds is not None:
+            if len(utterance_seeds) != B:
+                raise _lib.FacppgError("%s: utterance_seeds must be B integers" % what)
+            vals = [int(v) & 0xFFFFFFFFFFFFFFFF for v in utterance_seeds]
+        else:
+            if seed is None:
+                seed = int(torch.empty((), dtype=torch.int64).random_().item())
+            vals = self.derive_seeds(int(seed) & 0xFFFFFFFFFFFFFFFF, B)
+        # (uint64 bit patterns through int64: the kernels read them as uint64_t)
+        return _lib.upload([v - (1 << 64) if v >= (1 << 63) else v for v in vals], torch.int64, dev)
+
+    def _gl_workspace(self, h, dev, B, F):
+        nbytes = _lib.load().facppg_griffin_lim_workspace_bytes(h, B, max(F, 2))   # (mel_to_magnitude takes one frame too)
+        ws = self.__dict__.get("_facppg_ws")
+        if ws is None or ws.numel() < nbytes or ws.device != dev:
+            ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+            self.__dict__["_facppg_ws"] = ws
+        return ws
+
+    def griffin_lim(self, magnitudes, n_iters=30, momentum=0.0, lengths=None, init_phase=None, seed=None, utterance_seeds=None,
+                    return_convergence=False):
+        """Griffin-Lim with optional momentum as one device loop (facppg_griffin_lim, defined in include/facppg.h):
+        magnitudes [B, cutoff, F] -> [B, 1, hop * (F - 1)] (zeros behind hop * (lengths[b] - 1)), plus sc [B] with
+        ``return_convergence`` (|| |t_n| - M || / || M || at the last iteration; 1 for n_iters = 0).  momentum = 0 is the loop
+        of audio_processing.griffin_lim.  lengths: frame counts per utterance (list or tensor).  The starting phases are
+        ``init_phase`` [B, cutoff, F] or drawn on the device from ``utterance_seeds`` / ``seed`` (this build's own Philox
+        stream, not NumPy's: pass init_phase for the reference's draws); utterance b of a batch under utterance_seeds equals
+        its own batch-1 call."""
+        what = "STFT.griffin_lim"
+        _lib.require_cuda(magnitudes, what + ": magnitudes")
+        mag = magnitudes.float().contiguous()
+        if mag.dim() != 3 or mag.shape[1] != self.filter_length // 2 + 1:
+            raise _lib.FacppgError("%s: magnitudes must be [B, %d, F]" % (what, self.filter_length // 2 + 1))
+        B, cutoff, F = mag.shape
+        dev = mag.device
+        if B < 1 or F < 2:
+            raise _lib.FacppgError("%s: need at least one utterance of at least 2 frames, got B=%d F=%d" % (what, B, F))
+        seeds = self._phase_seeds(B, dev, init_phase, seed, utterance_seeds, what)
+        phi = None
+        if init_phase is not None:
+            phi = init_phase.to(dev).float().contiguous()
+            if phi.shape != mag.shape:
+                raise _lib.FacppgError("%s: init_phase must have the magnitudes' shape" % what)
+        if lengths is None and self.hop_length * (F - 1) <= self.filter_length // 2:
+            lengths = [F] * B               # (refused below with the reason)
+        lt = self._frame_lengths(lengths, B, F, dev, what)
+        h = self._handle(dev)
+        ws = self._gl_workspace(h, dev, B, F)
+        out = torch.empty(B, 1, self.hop_length * (F - 1), device=dev)
+        sc = torch.empty(B, device=dev) if return_convergence else None
+        with torch.cuda.device(dev):
+            _lib.check(_lib.load().facppg_griffin_lim(h, _lib.ptr(mag), _lib.ptr(lt), _lib.ptr(phi), _lib.ptr(seeds), int(n_iters),
+                                                      float(momentum), B, F, _lib.ptr(out), _lib.ptr(sc), _lib.ptr(ws), ws.numel(),
+                                                      _lib.current_stream(dev)))
+        return (out, sc) if return_convergence else out
+
+    def draw_phase(self, utterance_seeds, F, device):
+        """The phases griffin_lim(utterance_seeds=...) starts from, [B, cutoff, F] (facppg_griffin_lim_draw_phase)."""
+        dev = torch.device(device)
+        if dev.index is None:
+            dev = torch.device("cuda", torch.cuda.current_device())
+        B = len(utterance_seeds)
+        seeds = self._phase_seeds(B, dev, None, None, utterance_seeds, "STFT.draw_phase")
+        out = torch.empty(B, self.filter_length // 2 + 1, F, device=dev)
+        with torch.cuda.device(dev):
+            _lib.check(_lib.load().facppg_griffin_lim_draw_phase(self._handle(dev), _lib.ptr(seeds), B, F, _lib.ptr(out),
+                                                                 _lib.current_stream(dev)))
+        return out
+
+    def _mel_pinv(self, h, dev):
+        """pinv(mel_basis) [cutoff, n_mel]: float64 on the host, rounded to float32, handed to the handle once per device."""
+        if self._mel_basis_np is None:
+            raise _lib.FacppgError("mel_to_magnitude: this STFT was built without a mel basis")
+        cur = self.__dict__.get("_facppg_pinv")
+        if cur is None or cur[1] != dev or cur[2] is not h:
+            P = np.linalg.pinv(np.asarray(self._mel_basis_np, dtype=np.float64)).astype(np.float32)
+            t = torch.from_numpy(np.ascontiguousarray(P)).to(dev)
+            with torch.cuda.device(dev):
+                _lib.check(_lib.load().facppg_stft_set_mel_pinv(h, _lib.ptr(t), _lib.current_stream(dev)))
+            self.__dict__["_facppg_pinv"] = (t, dev, h)
+
+    def mel_to_magnitude(self, mel, lengths=None):
+        """log-mel [B, n_mel, F] (what ``mel`` makes) -> max(pinv(mel_basis) . exp(mel), 0) [B, cutoff, F], zeros at and behind
+        lengths[b] frames: this build's own mel inversion (include/facppg.h)."""
+        what = "mel_to_magnitude"
+        _lib.require_cuda(mel, what + ": mel")
+        if self._mel_basis_np is None:
+            raise _lib.FacppgError("mel_to_magnitude: this STFT was built without a mel basis")
+        x = mel.float().contiguous()
+        if x.dim() != 3 or x.shape[1] != self._mel_basis_np.shape[0]:
+            raise _lib.FacppgError("%s: mel must be [B, %d, F]" % (what, self._mel_basis_np.shape[0]))
+        B, n_mel, F = x.shape
+        dev = x.device
+        lt = None
+        if lengths is not None:
+            if torch.is_tensor(lengths):
+                lt = lengths.to(device=dev, dtype=torch.int32).contiguous()
+                ok = lt.numel() == B
+            else:
+                ok = len(lengths) == B and 0 <= min(int(n) for n in lengths) and max(int(n) for n in lengths) <= F
+                lt = _lib.upload([int(n) for n in lengths], torch.int32, dev) if ok else None
+            if not ok:
+                raise _lib.FacppgError("%s: lengths must be B frame counts <= F" % what)
+        h = self._handle(dev)
+        self._mel_pinv(h, dev)
+        ws = self._gl_workspace(h, dev, B, F)
+        out = torch.empty(B, self.filter_length // 2 + 1, F, device=dev)
+        with torch.cuda.device(dev):
+            _lib.check(_lib.load().facppg_mel_to_magnitude(h, _lib.ptr(x), _lib.ptr(lt), B, F, _lib.ptr(out), _lib.ptr(ws), ws.numel(),
+                                                           _lib.current_stream(dev)))
         return out
 
     def denoise(self, audio, bias_spec, strength, lengths=None):

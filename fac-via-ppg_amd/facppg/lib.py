@@ -202,6 +202,11 @@ def _declare(lib):
         "facppg_stft_inverse": (c.c_int, [vp, vp, vp, c.c_int, c.c_int, vp, vp, sz, vp]),
         "facppg_stft_mel": (c.c_int, [vp, vp, vp, c.c_int, c.c_int, vp, vp, sz, vp]),
         "facppg_denoise": (c.c_int, [vp, vp, vp, vp, f32, c.c_int, c.c_int, vp, vp, sz, vp]),
+        "facppg_stft_set_mel_pinv": (c.c_int, [vp, vp, vp]),
+        "facppg_mel_to_magnitude": (c.c_int, [vp, vp, vp, c.c_int, c.c_int, vp, vp, sz, vp]),
+        "facppg_griffin_lim_workspace_bytes": (sz, [vp, c.c_int, c.c_int]),
+        "facppg_griffin_lim": (c.c_int, [vp, vp, vp, vp, vp, c.c_int, f32, c.c_int, c.c_int, vp, vp, vp, sz, vp]),
+        "facppg_griffin_lim_draw_phase": (c.c_int, [vp, vp, c.c_int, c.c_int, vp, vp]),
         "facppg_taco_weight_count": (sz, [c.POINTER(TacoConfig)]),
         "facppg_taco_create": (c.c_int, [c.POINTER(TacoConfig), vp, sz, c.c_int, vp, c.POINTER(vp)]),
         "facppg_taco_destroy": (None, [vp]),

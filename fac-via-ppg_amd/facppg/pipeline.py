@@ -19,23 +19,43 @@ class Synthesizer(object):
     (utils.py:177-181) and once as pickled for the denoiser's bias estimate (generate_synthesis.py:58-61)."""
 
     def __init__(self, ppg2mel_path, waveglow_path, hparams=None, denoiser_mode='zeros', vocoder_arithmetic=None, vocoder_stream=None):
+        """waveglow_path None: a synthesizer without a vocoder (none trained yet for this speaker) -- it has the PPG -> mel model
+        and the hparams' TacotronSTFT, and offers preview / preview_wavs / preview_scored (Griffin-Lim on the device); every
+        method that needs the vocoder raises."""
         from common.hparams import create_hparams_stage
-        from common.utils import load_waveglow_model
+        from common.layers import TacotronSTFT
         from script.train_ppg2mel import load_model
-        from waveglow.denoiser import Denoiser
         self.hparams = hparams if hparams is not None else create_hparams_stage()
-        self.tacotron = load_model(self.hparams)
+        hp = self.hparams
+        self.tacotron = load_model(hp)
         self.tacotron.load_state_dict(torch.load(ppg2mel_path, weights_only=False)['state_dict'])
         self.tacotron.eval()
-        self.denoiser = Denoiser(torch.load(waveglow_path, weights_only=False)['model'].cuda(), mode=denoiser_mode)
-        self.waveglow = load_waveglow_model(waveglow_path)
+        # the analysis the model's mels were made with (common.data_utils.PPGMelLoader): what preview inverts
+        self.stft = TacotronSTFT(hp.filter_length, hp.hop_length, hp.win_length, hp.n_acoustic_feat_dims, hp.sampling_rate,
+                                 hp.mel_fmin, hp.mel_fmax)
+        self.stft.to(next(self.tacotron.parameters()).device)
+        self.denoiser = self.waveglow = None
+        self.vocoder_less = waveglow_path is None
+        if waveglow_path is not None:
+            from common.utils import load_waveglow_model
+            from waveglow.denoiser import Denoiser
+            self.denoiser = Denoiser(torch.load(waveglow_path, weights_only=False)['model'].cuda(), mode=denoiser_mode)
+            self.waveglow = load_waveglow_model(waveglow_path)
         # the vocoder's arithmetic of every call (WaveGlow.infer's ``arithmetic``); the denoiser's bias spectrum above is formed on
         # the fp32 path either way
         self.vocoder_arithmetic = _checked_arithmetic(vocoder_arithmetic)
         # synthesize()'s ``vocoder_stream`` of every one-utterance call (True: a "bf16x3" vocoder takes the streamed, conditioning-first path)
         self.vocoder_stream = _checked_stream(vocoder_stream)
 
+    def _vocoder(self, what):
+        """Refuses ``what`` on a synthesizer built without a vocoder, before any device work."""
+        if getattr(self, "vocoder_less", False):
+            from facppg.lib import FacppgError
+            raise FacppgError("Synthesizer.%s needs the vocoder, and this synthesizer was built without one (waveglow_path=None): "
+                              "use preview / preview_wavs / preview_scored, which make the waveform by Griffin-Lim" % what)
+
     def __call__(self, ppgs, sigma=0.6, strength=0.005, **kw):
+        self._vocoder("__call__")
         kw.setdefault("vocoder_arithmetic", self.vocoder_arithmetic)
         kw.setdefault("vocoder_stream", self.vocoder_stream)
         return synthesize(ppgs, self.tacotron, self.waveglow, self.denoiser, sigma=sigma, strength=strength, **kw)
@@ -43,8 +63,34 @@ class Synthesizer(object):
     def stream(self, jobs, sigma=0.6, strength=0.005, **kw):
         """synthesize_stream over this synthesizer's models: batch i+1's acoustic model under batch i's vocoder.  Jobs that carry
         ``wavs`` need ``ppg_deps`` (a ppg.DependenciesPPG)."""
+        self._vocoder("stream")
         kw.setdefault("vocoder_arithmetic", self.vocoder_arithmetic)
         return synthesize_stream(jobs, self.tacotron, self.waveglow, self.denoiser, sigma=sigma, strength=strength, **kw)
+
+    def preview(self, ppgs, **kw):
+        """facppg.pipeline.preview over this synthesizer's PPG -> mel model and TacotronSTFT: PPGs -> (waveforms, mel lengths)
+        without a vocoder.  Works with or without one loaded."""
+        return preview(ppgs, self.tacotron, self.stft, **kw)
+
+    def preview_wavs(self, wavs, ppg_deps=None, **kw):
+        """facppg.pipeline.preview_wavs over this synthesizer's models: teacher wavs (list of WaveData) -> (waveforms, mel
+        lengths), the PPGs kept on the device; ppg_deps as in convert()."""
+        _checked_wav_list(wavs, kw.get("ppgs"), "Synthesizer.preview_wavs")
+        return preview_wavs(wavs, self._deps(ppg_deps), self.tacotron, self.stft, **kw)
+
+    def preview_scored(self, wavs, ppg_deps=None, score_band=0, phones=False, **kw):
+        """preview_wavs() plus facppg.score.roundtrip of what it made, in convert_scored's return shape: (waveforms, mel lengths,
+        scores).  The waveforms are preview_wavs()'s for the same keywords, bit for bit."""
+        from facppg import score
+        _checked_wav_list(wavs, kw.get("ppgs"), "Synthesizer.preview_scored")
+        deps = self._deps(ppg_deps)
+        score.check_roundtrip_deps(deps, "Synthesizer.preview_scored")
+        host = not kw.pop("return_device", False)
+        audio, tout = self.preview_wavs(wavs, deps, return_device=True, **kw)
+        scores = score.roundtrip(wavs, audio, self.hparams.sampling_rate, deps, band=score_band, phones=phones)
+        if host:
+            audio = [a.cpu().numpy() for a in audio]
+        return audio, tout, scores
 
     def _deps(self, ppg_deps):
         """The PPG dependencies of a call that starts from audio: the caller's, else ppg.DependenciesPPG() read once."""
@@ -59,6 +105,7 @@ class Synthesizer(object):
         """synthesize_wavs over this synthesizer's models: teacher wavs (list of WaveData) -> (waveforms, mel lengths); the PPGs
         go from the front end to the encoder on the device.  ppg_deps: a ppg.DependenciesPPG (None: the default files, which
         are read only for a well-formed list of wavs)."""
+        self._vocoder("convert")
         _checked_wav_list(wavs, ppgs, "Synthesizer.convert")
         kw.setdefault("vocoder_arithmetic", self.vocoder_arithmetic)
         kw.setdefault("vocoder_stream", self.vocoder_stream)
@@ -71,6 +118,7 @@ class Synthesizer(object):
         monophone PPGs are aligned on the device; with ``phones`` the scores also say per teacher phone where it landed
         (facppg.align.phone_report).  Dependencies without the pdf -> monophone matrix are refused before anything runs."""
         from facppg import score
+        self._vocoder("convert_scored")
         _checked_wav_list(wavs, kw.get("ppgs"), "Synthesizer.convert_scored")
         deps = self._deps(ppg_deps)
         score.check_roundtrip_deps(deps, "Synthesizer.convert_scored")
@@ -86,6 +134,7 @@ class Synthesizer(object):
         generate_synthesis.py:86-98), the PPGs extracted here and kept on the device."""
         from common.feat import read_wav_kaldi
         from scipy.io import wavfile
+        self._vocoder("convert_file")
         wavs, tout = self.convert([read_wav_kaldi(utterance_path)], ppg_deps, sigma=sigma, strength=strength)
         wavfile.write(wav_path, fs, wavs[0].astype(np.float32)[:, None])
         return tout[0]
@@ -94,6 +143,7 @@ class Synthesizer(object):
         """synthesize_long_wavs over this synthesizer's models: teacher recordings of any length (list of WaveData) ->
         (waveforms, segment tables), cut at their pauses, converted in batches and joined on the device.  Keywords and defaults
         are synthesize_long_wavs's (the vocoder arithmetic defaults to the synthesizer's); ppg_deps as in convert()."""
+        self._vocoder("convert_long")
         _checked_wav_list(wavs, None, "Synthesizer.convert_long")
         kw.setdefault("vocoder_arithmetic", self.vocoder_arithmetic)
         return synthesize_long_wavs(wavs, self._deps(ppg_deps), self.tacotron, self.waveglow, self.denoiser, **kw)
@@ -103,6 +153,7 @@ class Synthesizer(object):
         does): ``utterance_path`` (a wav) -> ``wav_path`` (float32 [N, 1] at ``fs``).  Returns the recording's segment table."""
         from common.feat import read_wav_kaldi
         from scipy.io import wavfile
+        self._vocoder("convert_long_file")
         kw["return_device"] = False
         wavs, tables = self.convert_long([read_wav_kaldi(utterance_path)], **kw)
         wavfile.write(wav_path, fs, wavs[0].astype(np.float32)[:, None])
@@ -119,6 +170,7 @@ class Synthesizer(object):
         """One teacher utterance -> ``wav_path`` (float32 [N, 1] at ``fs``, generate_synthesis.py:90-98)."""
         from common.data_utils import get_ppg
         from scipy.io import wavfile
+        self._vocoder("synthesize_file")
         wavs, tout = self([get_ppg(utterance_path, ppg_deps)], sigma=sigma, strength=strength)
         wavfile.write(wav_path, fs, wavs[0].astype(np.float32)[:, None])
         return tout[0]
@@ -790,6 +842,57 @@ def synthesize_wavs(wavs, deps, tacotron, waveglow, denoiser=None, is_full_ppg=N
         timer.mark("front_end")
     return _synthesize(None, prepared, tacotron, waveglow, denoiser, sigma, strength, seed, dropout_masks, z, return_device, utterance_seeds,
                        step_limits, timer, arithmetic, vocoder_stream)
+
+
+def _preview_seeds(seed, utterance_seeds):
+    """The phase seeds of a preview next to its dropout seeds: the decoder draws from ``utterance_seeds[b]`` (or ``seed``), the
+    vocoder of synthesize() from utterance_seeds[b] + 1, Griffin-Lim's phases from utterance_seeds[b] + 2 (or seed + 2: STFT.griffin_lim
+    then derives one seed per utterance) -- so a corpus keyed by seed + 3 * i never shares a stream between stages."""
+    if utterance_seeds is not None:
+        return {"utterance_seeds": [int(v) + 2 for v in utterance_seeds]}
+    return {"seed": None if seed is None else int(seed) + 2}
+
+
+def _preview(ppgs, prepared, tacotron, stft, n_iters, momentum, seed, utterance_seeds, step_limits, dropout_masks, return_device):
+    if seed is not None and utterance_seeds is not None:
+        from facppg.lib import FacppgError
+        raise FacppgError("preview: seed and utterance_seeds are two ways to say the same thing -- give one")
+    hop = stft.stft_fn.hop_length
+    with torch.no_grad():
+        mel_post, tout = _acoustic(ppgs, tacotron, seed, dropout_masks, utterance_seeds, step_limits, prepared=prepared)
+        audio = stft.griffin_lim(mel_post, lengths=tout, n_iters=n_iters, momentum=momentum, **_preview_seeds(seed, utterance_seeds))[:, 0]
+    n = [(t - 1) * hop for t in tout]
+    if return_device:
+        return [audio[b, :n[b]] for b in range(len(tout))], tout
+    host = audio.cpu().numpy()
+    return [host[b, :n[b]].copy() for b in range(len(tout))], tout
+
+
+def preview(ppgs, tacotron, stft, n_iters=60, momentum=0.99, seed=None, utterance_seeds=None, step_limits=None, dropout_masks=None,
+            return_device=False, prepared=None):
+    """synthesize() without a vocoder: PPGs -> Tacotron2.inference -> TacotronSTFT.griffin_lim (the mel inverted to a linear
+    magnitude by the pseudo-inverse of the mel basis, then Griffin-Lim with momentum as one device loop).  Returns (list of float32
+    waveforms, list of mel lengths) in synthesize()'s shapes; utterance b has hop * (mel length - 1) samples (the inverse STFT
+    of its frames), hop fewer than the vocoder would make.  stft: a common.layers.TacotronSTFT on the model's device, with the
+    analysis parameters the model was trained on.
+    seed / utterance_seeds: as synthesize() -- the decoder's dropout draws come from them, and the starting phases from the same
+    values + 2 (the vocoder's noise of synthesize() takes + 1): with utterance_seeds, utterance b's waveform is that of its own
+    batch-1 call.  Giving both is refused.  step_limits, dropout_masks: as synthesize().  prepared: (x [B, D, Tmax] on the device,
+    lengths) in place of ``ppgs`` (ppg.compute_ppg_padded's result)."""
+    return _preview(ppgs, prepared, tacotron, stft, n_iters, momentum, seed, utterance_seeds, step_limits, dropout_masks, return_device)
+
+
+def preview_wavs(wavs, deps, tacotron, stft, is_full_ppg=None, n_iters=60, momentum=0.99, seed=None, utterance_seeds=None,
+                 step_limits=None, dropout_masks=None, return_device=False, ppgs=None, append_f0=None):
+    """preview() from teacher audio, the way synthesize_wavs() starts synthesize(): wavs (list of WaveData) go through the batch
+    front end of ``deps`` and their PPGs reach the encoder on the device; is_full_ppg and append_f0 follow synthesize_wavs's rules,
+    and the argument errors come before any device work."""
+    from ppg.compute_ppg import compute_ppg_padded
+    is_full_ppg = _checked_wavs(wavs, deps, tacotron, is_full_ppg, "preview_wavs", ppgs)
+    append_f0 = _checked_append_f0(deps, tacotron, is_full_ppg, append_f0, "preview_wavs")
+    with torch.no_grad():
+        prepared = compute_ppg_padded(wavs, deps, is_full_ppg=is_full_ppg, append_f0=append_f0)
+    return _preview(None, prepared, tacotron, stft, n_iters, momentum, seed, utterance_seeds, step_limits, dropout_masks, return_device)
 
 
 def _checked_job_source(job):

@@ -535,6 +535,55 @@ int facppg_denoise(facppg_stft* h, const float* audio_dev, const int32_t* n_vali
                    const float* bias_spec_dev, float strength, int B, int N, float* out_dev,
                    void* workspace_dev, size_t workspace_bytes, void* stream);
 
+/* Vocoder-free preview: a mel back to a linear magnitude, and Griffin-Lim on the device.  BOTH
+ * DEFINITIONS ARE THIS BUILD'S OWN: the reference has no mel inversion, and its griffin_lim
+ * (audio_processing.py:91-107) draws NumPy phases on the host.
+ *
+ * Mel to magnitude.  P = pinv(mel_basis) [cutoff][n_mel] (cutoff = filter_length/2+1) is computed
+ * by the caller on the host in float64, rounded to float32 and handed over once with
+ * facppg_stft_set_mel_pinv (a handle created without a mel basis refuses it; the table must stay
+ * alive until the stream has passed the call; nothing is synchronised).  Then
+ *   mag = max(P . exp(mel), 0)   [B][cutoff][F]
+ * for mel [B][n_mel][F] as facppg_stft_mel makes it (natural log of the clamped mel energies).
+ * n_frames_dev: NULL or [B] frame counts <= F; frames at or beyond n_frames[b] are written as
+ * zeros.  This is the pseudo-inverse seed of the usual NNLS inversion without the NNLS.
+ * Workspace: B * n_mel * F floats (facppg_griffin_lim_workspace_bytes(h, B, F) covers it for F >= 2). */
+int facppg_stft_set_mel_pinv(facppg_stft* h, const float* pinv_dev, void* stream);
+int facppg_mel_to_magnitude(facppg_stft* h, const float* mel_dev, const int32_t* n_frames_dev, int B,
+                            int F, float* mag_dev, void* workspace_dev, size_t workspace_bytes,
+                            void* stream);
+
+/* Griffin-Lim with optional momentum on magnitudes M = mag_dev [B][cutoff][F].  With
+ *   Pc(X) = STFT(ISTFT(X))   this build's transform and inverse: reflect padding at each utterance's
+ *                            own end, window sum-square normalisation, trim
+ *   Pm(Y) = M . Y / |Y|      a bin with Y = 0 gives (M, 0), as atan2(0, 0) = 0 does
+ * the call computes
+ *   c_0 = M . exp(i phi0)
+ *   for n = 1 .. n_iters:  t_n = Pc(c_{n-1});  y_n = t_n + alpha (t_n - t_{n-1})  (t_0 := t_1);  c_n = Pm(y_n)
+ *   out = ISTFT(c_{n_iters})          [B][hop*(F-1)], zeros behind hop*(n_frames[b]-1)
+ * 0 <= alpha < 1; alpha = 0 is the reference's loop up to the rounding of its atan2 / sincos
+ * (n_iters + 1 inverses; n_iters = 0 is one inverse).  No phase is ever formed inside the loop.
+ * n_frames_dev: NULL or [B] frame counts in [2, F] (values outside are clamped to [1, F]).  An
+ * utterance with hop*(n_frames[b]-1) <= filter_length/2 samples, which reflect padding cannot
+ * serve, takes the framing kernel's clamped reflection (as facppg_stft_transform documents for
+ * ragged batches); callers that know the lengths on the host should refuse it.
+ * phi0_dev [B][cutoff][F], or NULL: then the phases are drawn on the device, uniform in [-pi, pi)
+ * on a 2^-24 grid, by Philox4x32-10 keyed by seeds_dev[b] with the counter (frame, bin) -- a
+ * function of (seed, bin, frame) alone, so utterance b of a batch draws what its batch-1 call
+ * draws.  THIS IS NOT NumPy's STREAM; facppg_griffin_lim_draw_phase returns the same phases
+ * [B][cutoff][F] for inspection.
+ * sc_dev: NULL or [B]: sc[b] = || |t_n| - M ||_2 / || M ||_2 at the last iteration over utterance
+ * b's own frames, 0 where M = 0.  With n_iters = 0 there is no t_n and |t_0| := 0, so sc is 1
+ * (0 where M = 0).  Summed in float64 in a fixed order without atomics: the same bits in any batch.
+ * Nothing synchronises the stream. */
+size_t facppg_griffin_lim_workspace_bytes(const facppg_stft* h, int B, int F);
+int facppg_griffin_lim(facppg_stft* h, const float* mag_dev, const int32_t* n_frames_dev,
+                       const float* phi0_dev, const uint64_t* seeds_dev, int n_iters, float alpha,
+                       int B, int F, float* out_dev, float* sc_dev, void* workspace_dev,
+                       size_t workspace_bytes, void* stream);
+int facppg_griffin_lim_draw_phase(const facppg_stft* h, const uint64_t* seeds_dev, int B, int F,
+                                  float* phase_dev, void* stream);
+
 /* ------------------------------------------------------------------------------------
  * Tacotron2-style PPG -> mel model (src/common/model.py)
  * ---------------------------------------------------------------------------------- */
