@@ -1981,6 +1981,22 @@ extern "C" size_t facppg_wn_bf16_scratch_bytes(int n_layers, int B, int L) {
   return scratch_layout(n_layers, B, pad_len(L)).total + scratch_bias_bytes();
 }
 
+// host-only: where the stages live in the caller's buffers, from the two carves the entry points use
+extern "C" int facppg_wn_bf16_layout(int n_layers, int B, int L, facppg_wn_bf16_offsets* out) {
+  FACPPG_REQUIRE(out && n_layers >= 1 && n_layers <= 8 && B > 0 && L > 0, FACPPG_EINVAL, "bad argument");
+  const int Lr = pad_len(L);
+  const StateLayout st = state_layout(n_layers, B, Lr);
+  const ScratchLayout sc = scratch_layout(n_layers, B, Lr);
+  facppg_wn_bf16_offsets o = {};
+  o.Lr = Lr; o.Lp = HALO + Lr + HALO; o.halo = HALO;
+  o.h = st.h; o.h_stride = st.h_one; o.ts = st.ts; o.ts_stride = st.ts_one; o.acts = st.acts; o.acts_stride = st.acts_one;
+  o.skip = st.skip; o.skip_bytes = (size_t)B * Lr * C * 4; o.state_end = st.total;
+  o.dpre = sc.dpre; o.dpre_stride = sc.dpre_one; o.dh = sc.dh; o.dh_stride = sc.dh_one; o.dskip = sc.dskip; o.dskip_bytes = sc.dh_one;
+  o.grads_end = sc.part; o.scratch_end = sc.total;
+  *out = o;
+  return FACPPG_OK;
+}
+
 extern "C" int facppg_spect_to_bf16(const float* spect_dev, int B, int channels, int L, int ld, void* out_dev, void* stream) {
   FACPPG_REQUIRE(spect_dev && out_dev && B > 0 && channels > 0 && L > 0 && ld >= L, FACPPG_EINVAL, "bad argument");
   const int Lr = pad_len(L);

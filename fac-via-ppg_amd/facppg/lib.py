@@ -83,6 +83,13 @@ class WnGrads(ctypes.Structure):
     _fields_ = WnWeights._fields_
 
 
+class WnBf16Offsets(ctypes.Structure):
+    """facppg_wn_bf16_offsets (include/facppg.h): where facppg_wn_forward_bf16 / _backward_bf16 keep each stage in state and scratch."""
+    _fields_ = [(n, ctypes.c_int32) for n in ("Lr", "Lp", "halo", "reserved")] + \
+        [(n, ctypes.c_size_t) for n in ("h", "h_stride", "ts", "ts_stride", "acts", "acts_stride", "skip", "skip_bytes", "state_end",
+                                        "dpre", "dpre_stride", "dh", "dh_stride", "dskip", "dskip_bytes", "grads_end", "scratch_end")]
+
+
 class GlowBf16Sizes(ctypes.Structure):
     """facppg_glow_bf16_sizes (include/facppg.h)."""
     _fields_ = [("packed_bytes_per_flow", ctypes.c_size_t), ("state_bytes_per_flow", ctypes.c_size_t), ("work_bytes", ctypes.c_size_t),
@@ -153,6 +160,7 @@ def _declare(lib):
         "facppg_wn_bf16_state_bytes": (sz, [c.c_int, c.c_int, c.c_int]),
         "facppg_wn_bf16_scratch_bytes": (sz, [c.c_int, c.c_int, c.c_int]),
         "facppg_wn_bf16_launch_plan": (c.c_int, [c.c_int, c.c_int, c.c_int]),
+        "facppg_wn_bf16_layout": (c.c_int, [c.c_int, c.c_int, c.c_int, c.POINTER(WnBf16Offsets)]),
         "facppg_train_bf16_launch_plan": (c.c_int, [c.c_int, c.c_int, c.c_int, c.POINTER(TrainLaunchReport)]),
         "facppg_spect_to_bf16": (c.c_int, [vp, c.c_int, c.c_int, c.c_int, c.c_int, vp, vp]),
         "facppg_posmajor_to_f32": (c.c_int, [vp, c.c_int, c.c_int, c.c_int, vp, c.c_int, vp]),

@@ -284,6 +284,20 @@ int facppg_glow_bf16_group_backward(const facppg_glow_flow* flows, int n, int n_
 
 size_t facppg_wn_bf16_state_bytes(int n_layers, int B, int L);    /* saved activations of one stack (forward -> backward) */
 size_t facppg_wn_bf16_scratch_bytes(int n_layers, int B, int L);  /* per-call scratch (packed bf16 weight images, gradients in flight) */
+/* Where the saved activations and the gradients in flight live inside `state` and `scratch` of the two calls below: byte offsets
+ * of layer 0 and per-layer strides, from the carve the calls themselves use (csrc/facppg_train_plan.h) -- host-side only, for tests
+ * and tools that read the buffers stage by stage.  State: h [n_layers + 1][B][Lp][256] bf16 (positions at rows [halo, halo + L)),
+ * ts [n_layers][B][Lr][512] bf16, acts [n_layers][B][Lr][256] bf16, skip [B][Lr][256] fp32.  Scratch: dpre [n_layers][B][Lp][512]
+ * bf16 (rows as h), dh [n_layers + 1][B][Lr][256] bf16, dskip [B][Lr][256] bf16.  *_end: one past the last byte of the last piece
+ * (state_end = facppg_wn_bf16_state_bytes; the summed gate biases follow scratch_end).  FACPPG_EINVAL where the size queries return 0,
+ * or out is NULL. */
+typedef struct facppg_wn_bf16_offsets {
+  int32_t Lr, Lp, halo;         /* padded positions per item, rows of an h / dpre image, margin rows on either side */
+  int32_t reserved;
+  size_t h, h_stride, ts, ts_stride, acts, acts_stride, skip, skip_bytes, state_end;
+  size_t dpre, dpre_stride, dh, dh_stride, dskip, dskip_bytes, grads_end, scratch_end;
+} facppg_wn_bf16_offsets;
+int facppg_wn_bf16_layout(int n_layers, int B, int L, facppg_wn_bf16_offsets* out);
 /* Which launches facppg_wn_forward_bf16 / facppg_wn_backward_bf16 use for B items of L positions (glow.py:154-175 and its autograd
  * backward), after the FACPPG_TRAIN_FUSED_FWD / _BWD, FACPPG_TRAIN_TILE and FACPPG_WGRAD_TILE overrides -- a diagnostic, host-side only:
  * bit 0: one launch per layer forward (k_wn_fwd) instead of two; bit 1: one launch per layer in the backward chain (k_wn_bwd);
